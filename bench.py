@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — FS2 train-step throughput (BASELINE.json configs[1]) on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = one full `main_train_step` (forward, loss, backward, [RCCL gradient all-reduce], global-norm clip, Adam with the
@@ -474,6 +474,41 @@ def write_full_record(rec):
     return None
 
 
+STEP_OUTPUT_NAMES = ("mel", "pitch", "energy", "log_duration", "duration_rounded", "src_masks", "mel_masks", "mel_lens", "postnet_mel")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_arrays(out):
+    """What the timed step hands its caller, as host arrays: the loss values and the forward outputs of `main_train_step`'s tuple
+    (make_enqueue returns (losses, out); `out` is FastSpeech2._forward's 9-tuple).  Floating tensors as float32, integer and
+    boolean ones as float64 (exact)."""
+    losses, fwd = out
+    arrays = {"losses": losses}
+    arrays.update(zip(STEP_OUTPUT_NAMES, fwd))
+    res = {}
+    for name, t in arrays.items():
+        if not torch.is_tensor(t):
+            continue
+        t = t.detach().cpu()
+        res[name] = t.float().numpy() if t.is_floating_point() else t.double().numpy()
+    return res
+
+
+def dump_outputs(arrays, d, limit=DUMP_LIMIT_BYTES):
+    """`arrays` as d/<name>.npy, at most `limit` bytes in all.  An array over its equal share of the limit is replaced by a fixed sample
+    (seed 0) of its flattened elements, in index order, with the sampled flat indices beside it as d/<name>.index.npy (int64)."""
+    os.makedirs(d, exist_ok=True)
+    share = limit // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.nbytes + 128 > share:
+            k = max(1, (share - 256) // (a.itemsize + 8))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=min(k, a.size), replace=False)).astype(np.int64)
+            np.save(os.path.join(d, name + ".index.npy"), idx)
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def _time_loop(fn, n, sync=True):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -658,6 +693,8 @@ def main():
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the eager / grad_acc_step=4 / trainer-loop / DP-schedule legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed (losses and "
+                    "forward outputs) as DIR/<name>.npy")
     ap.add_argument("--dp1-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     from tts_king_amd.hostcpu import fit_torch_threads
@@ -774,6 +811,8 @@ def main():
     else:
         total_frames = float(frames)
     losses = out[0].cpu().tolist()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step_arrays(out), args.dump_outputs)
     ms = 1e3 * dt / args.steps
     value = total_frames * args.steps / dt
 

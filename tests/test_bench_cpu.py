@@ -69,3 +69,29 @@ def test_roofline_frac_follows_from_the_committed_rocprof_summary():
         if r.get("family") == "win_conv" and "frac_source" in r and r["frac_source"].startswith("profiles/"):
             gf = [f for f in r["families"] if f["family"] == "win_conv"][0]["gflop"]
             assert abs(r["frac"] - gf / prof["ms_per_step"] / 2500.0) <= 0.03 * r["frac"]
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """--dump-outputs: float32 / float64 .npy per array; an array over its share of the limit becomes a fixed sample of its flattened
+    elements with the sampled indices beside it, the same on every run."""
+    import numpy as np
+    import torch
+    mel = torch.arange(16 * 423 * 80, dtype=torch.float32).view(16, 423, 80).to(torch.bfloat16)
+    lens = torch.tensor([423, 400], dtype=torch.int64)
+    masks = torch.zeros(2, 5, dtype=torch.bool)
+    fwd = (mel, None, None, None, None, masks, None, lens, None)
+    arrays = bench.step_arrays((torch.ones(6), fwd))
+    assert set(arrays) == {"losses", "mel", "src_masks", "mel_lens"}
+    assert arrays["mel"].dtype == np.float32 and arrays["mel_lens"].dtype == np.float64 and arrays["src_masks"].dtype == np.float64
+    limit = 1 << 20
+    for d in ("a", "b"):
+        bench.dump_outputs(arrays, str(tmp_path / d), limit=limit)
+    total = sum(f.stat().st_size for f in (tmp_path / "a").iterdir())
+    assert total <= limit, total
+    assert sorted(f.name for f in (tmp_path / "a").iterdir()) == ["losses.npy", "mel.index.npy", "mel.npy", "mel_lens.npy", "src_masks.npy"]
+    idx = np.load(tmp_path / "a" / "mel.index.npy")
+    sample = np.load(tmp_path / "a" / "mel.npy")
+    assert np.array_equal(sample, arrays["mel"].reshape(-1)[idx]) and np.all(np.diff(idx) > 0)
+    for f in (tmp_path / "a").iterdir():
+        assert np.array_equal(np.load(f), np.load(tmp_path / "b" / f.name))
+    assert np.array_equal(np.load(tmp_path / "a" / "mel_lens.npy"), [423.0, 400.0])
