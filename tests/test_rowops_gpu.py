@@ -435,3 +435,121 @@ def test_optim_step_equals_separate_launches():
     for a, w in zip(*outs):
         assert torch.equal(a, w)
     assert int(outs[0][4][0]) == 4001 and int(outs[0][4][3]) == 2 and float(outs[0][5].abs().max()) == 0.0
+
+
+# ------------------------------------------------------------------------------------------------ bias-gradient column sums
+
+def _colsum_input(rows, C, ld, dt, seed):
+    """(rows, C) column slice at offset C of a (rows, ld) matrix — the layout of the q|k|v bias gradient's middle third."""
+    big = rnd(rows, ld, seed=seed).to(dt)
+    off = C if ld >= 2 * C else 0
+    return big, off
+
+
+@pytest.mark.parametrize("dt", [BF, torch.float32])
+@pytest.mark.parametrize("C,ld", [(4, 12), (80, 240), (256, 768), (1024, 1280)])
+def test_colsum_into_vs_fp64(C, ld, dt):
+    """ttsk_colsum + ttsk_colsum_finalize (every bias gradient of the step) against an fp64 column sum, at row counts on both
+    sides of the 16-row block and of the 256-block cap (rows > 4080), with a column slice of a wider matrix (ld > C), bf16 and
+    fp32 inputs, accumulate on and off.  Error bound: fp32 summation of at most 6768 terms, 2e-6 of the column's sum of |x|."""
+    from tts_king_amd import ops
+    for rows in (1, 15, 16, 17, 4080, 4081, 6768):
+        big, off = _colsum_input(rows, C, ld, dt, seed=rows + C)
+        x = big.to(DEV)[:, off:off + C]
+        assert x.stride(0) == ld
+        xs = big[:, off:off + C].double()
+        ref = xs.sum(0)
+        bound = 2e-6 * xs.abs().sum(0) + 1e-7
+        for acc in (False, True):
+            dst0 = rnd(C, seed=3) if acc else torch.full((C,), 777.0)
+            got = ops.colsum_into(x, dst0.to(DEV), accumulate=acc).cpu().double()
+            want = ref + (dst0.double() if acc else 0.0)
+            err = (got - want).abs()
+            assert bool((err <= bound + (1e-6 * dst0.double().abs() if acc else 0.0)).all()), (rows, C, acc, float(err.max()))
+
+
+@pytest.mark.parametrize("nblk,ncols,ld", [(1, 4, 4), (15, 80, 96), (16, 256, 768), (17, 1024, 1024), (64, 80, 80), (65, 12, 20), (256, 512, 768)])
+def test_colsum_finalize_vs_fp64(nblk, ncols, ld):
+    """ttsk_colsum_finalize: dst (+)= scale * sum_b partials[b * ld + c] for c < ncols (the 4-loads-in-flight loop and its remainder
+    at nblk around 16 / 64, a partials row stride ld > ncols), scale 1 and not 1, accumulate on and off, against fp64."""
+    from tts_king_amd import ops
+    part = rnd(nblk, ld, seed=nblk + ld, scale=10.0)
+    ref = part[:, :ncols].double().sum(0)
+    for scale in (1.0, 0.37):
+        for acc in (False, True):
+            dst0 = rnd(ncols, seed=8)
+            sentinel = torch.full((ncols + 8,), -5.0)
+            sentinel[:ncols] = dst0
+            dst = sentinel.to(DEV)
+            ops.colsum_finalize(part.to(DEV), nblk, ncols, ld, dst, accumulate=acc, scale=scale)
+            got = dst.cpu().double()
+            want = scale * ref + (dst0.double() if acc else 0.0)
+            tol = 1e-6 * (scale * part[:, :ncols].double().abs().sum(0) + dst0.double().abs()) + 1e-7
+            assert bool(((got[:ncols] - want).abs() <= tol).all()), (scale, acc, float((got[:ncols] - want).abs().max()))
+            assert bool((got[ncols:] == -5.0).all())                         # nothing past ncols is written
+
+
+def test_colsum_deferred_batch_equals_immediate_calls():
+    """The deferred path of the backward pass (colsum_into(defer=...) queues the column sum and its finalisation; flush_finalize
+    runs them as ttsk_colsum_batch + ttsk_colsum_finalize_batch, in chunks of 64 items) is bit-identical to the immediate calls —
+    with 70 queued column sums (> 64: two chunks each), mixed dtypes, widths, row counts, slices and accumulate flags."""
+    from tts_king_amd import ops
+    shapes = []
+    for i in range(70):
+        C, ld = [(4, 12), (80, 240), (256, 768), (1024, 1024), (512, 512)][i % 5]
+        rows = [1, 17, 423, 4081, 6768, 64, 2016][i % 7]
+        shapes.append((rows, C, ld, BF if i % 3 else torch.float32, bool(i % 2)))
+    xs, dsts0 = [], []
+    for i, (rows, C, ld, dt, acc) in enumerate(shapes):
+        big, off = _colsum_input(rows, C, ld, dt, seed=100 + i)
+        xs.append(big.to(DEV)[:, off:off + C])
+        dsts0.append(rnd(C, seed=200 + i).to(DEV))
+    immediate = [ops.colsum_into(x, d.clone(), accumulate=acc) for x, d, (_, _, _, _, acc) in zip(xs, dsts0, shapes)]
+    queue, deferred = [], []
+    for x, d, (_, _, _, _, acc) in zip(xs, dsts0, shapes):
+        deferred.append(ops.colsum_into(x, d.clone(), accumulate=acc, defer=queue))
+    # ... and finalisations queued on their own with scale != 1 (the path of the LayerNorm-family bias gradients)
+    parts = [rnd(nb, ld, seed=300 + i) for i, (nb, ld) in enumerate([(1, 80), (17, 256), (64, 768), (65, 1024), (256, 512)])]
+    fin_now, fin_later = [], []
+    for i, pt in enumerate(parts):
+        nb, ld = pt.shape
+        nc = ld if i % 2 else ld // 3
+        d0 = rnd(nc, seed=400 + i).to(DEV)
+        fin_now.append(ops.colsum_finalize(pt.to(DEV), nb, nc, ld, d0.clone(), accumulate=bool(i % 2), scale=0.37 + i))
+        fin_later.append(ops.colsum_finalize(pt.to(DEV), nb, nc, ld, d0.clone(), accumulate=bool(i % 2), scale=0.37 + i, defer=queue))
+    assert len(queue) == 140 + len(parts)
+    ops.flush_finalize(queue)
+    assert queue == []
+    torch.cuda.synchronize()
+    for i, (a, b) in enumerate(zip(immediate + fin_now, deferred + fin_later)):
+        assert torch.equal(a, b), (i, float((a - b).abs().max()))
+
+
+# ------------------------------------------------------------------------------------------------ eval helpers
+
+@pytest.mark.parametrize("d_control", [0.5, 1.0, 2.3])
+def test_duration_round_vs_fp64_rule(d_control):
+    """ttsk_duration_round against clamp(round_half_even(exp(x) - 1) * d_control, 0) (reference: modules.py:199-203) with the
+    rounding decided in fp64: negative log-durations (rounding to 0 and to -1, clamped), n = 1037 (not a multiple of 256).
+    Positions within 1e-5 of a rounding tie are left out (the device's expf may differ from fp64 by an ulp there)."""
+    from tts_king_amd import ops
+    x = torch.cat([torch.linspace(-4.0, 3.5, 1000), rnd(37, seed=41)]).float()
+    got = ops.duration_round(x.to(DEV), d_control).cpu()
+    v = torch.exp(x.double()) - 1.0
+    k = torch.round(v)                                                   # torch.round: half to even
+    want = torch.clamp(k.float() * torch.tensor(d_control, dtype=torch.float32), min=0.0)
+    tie = (v - torch.floor(v) - 0.5).abs() < 1e-5
+    assert int(tie.sum()) < 10 and bool((x < 0).sum() > 300) and bool((k == -1).any())
+    bad = (got != want) & ~tie
+    assert not bool(bad.any()), (x[bad][:5].tolist(), got[bad][:5].tolist(), want[bad][:5].tolist())
+
+
+@pytest.mark.parametrize("T", [77, 1031])
+def test_length_mask_exact(T):
+    """ttsk_length_mask: mask[b, t] = t >= lens[b] for lens in {0, 1, T-1, T, T+5}; B * T not a multiple of 256."""
+    from tts_king_amd import ops
+    lens = torch.tensor([0, 1, T - 1, T, T + 5], dtype=torch.int64)
+    assert (len(lens) * T) % 256 != 0
+    got = ops.length_mask(lens.to(DEV), T).cpu()
+    assert got.dtype == torch.bool and tuple(got.shape) == (5, T)
+    assert torch.equal(got, torch.arange(T)[None, :] >= lens[:, None])
