@@ -174,9 +174,10 @@ class HipStep:
         if dropout:
             self.masks = hip_dropout_masks(self.m, len(b[0]), self.Lp, self.Tp)
 
-    def run(self, b=None, upstream=None):
+    def run(self, b=None, upstream=None, on_ctx=None):
         """-> (losses or None, outputs (mel, post, pitch, energy, logd) on the CPU, flat gradient buffer clone).  `upstream`:
-        (g_mel, g_post, g_pitch, g_energy, g_logd) at the HIP shapes instead of the loss's gradients."""
+        (g_mel, g_post, g_pitch, g_energy, g_logd) at the HIP shapes instead of the loss's gradients.  `on_ctx(ctx, dmel_sum, dpost)`
+        is called between the forward and the backward (tests/test_block_grads_gpu.py keeps the step's saved activations there)."""
         from tts_king_amd import ops
         m = self.m
         if self.bucketed:
@@ -197,6 +198,8 @@ class HipStep:
             elif upstream is not None:
                 gm, gpo, gp, ge, gd = [t.to(DEV).float().contiguous() for t in upstream]
                 dmel_sum, dpost, dp, de, dd = gm + gpo, gpo, gp, ge, gd          # the convention of backward_native's docstring
+            if on_ctx is not None:
+                on_ctx(ctx, dmel_sum, dpost)
             m.flat_buffers()[1].fill_(SENTINEL)
             m.backward_native(ctx, dmel_sum, dpost, dp, de, dd, accumulate=False)
         torch.cuda.synchronize()
