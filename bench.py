@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — FS2 train-step throughput (BASELINE.json configs[1]) on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = one full `main_train_step` (forward, loss, backward, [RCCL gradient all-reduce], global-norm clip, Adam with the
@@ -9,6 +9,11 @@ reference LR schedule, zero_grad; grad_acc_step = 1) on one synthetic batch per 
 durations 1..11 frames -> T_max ~423 mel frames, 80-bin mel, 65 speakers, dropout ON, bf16 MFMA compute with fp32
 accumulation and fp32 master weights.  Inputs are resident in HBM before the timed region.  `value` counts VALID
 mel frames (sum of mel_lens) over all ranks per second.  Rank 0 prints ONE JSON line.
+
+A plain run times the step and, on one GPU, the HiFi-GAN batch (the metric's second half), and prints the line.  `--full` adds
+everything else: the step's per-family roofline, the HiFi-GAN stages, the CPU baselines, the eager / grad_acc_step=4 /
+trainer-loop / DP-schedule legs, end-to-end synthesis and mel extraction, and the long record beside the line; the `--no-*`
+options leave legs out of such a run.
 """
 import argparse
 import json
@@ -407,7 +412,8 @@ def compact_record(rec, full_path=None):
     """The ONE line bench.py prints: the contract's keys, `config`, `roofline` (dominant family only), `cpu_baseline` and a compact
     `hifi_gan` (the metric's second half), plus one scalar per auxiliary leg.  Everything else (`roofline.families` / `instances`, the
     HiFi-GAN stages' byte counts, the auxiliary legs' records) goes to the side file and to stderr.  Sections are dropped from the
-    end of `optional` until the line fits LINE_LIMIT; the headline halves are never dropped."""
+    end of `optional` until the line fits LINE_LIMIT; the headline halves are never dropped.  A plain run (no `--full`) has no
+    `roofline`, `cpu_baseline`, HiFi-GAN stages or auxiliary legs, and no side file."""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
             "data", "config", "mel_frames_per_s_per_gpu", "model_tflops", "step_mfma_roofline_frac", "final_losses", "unknown_switches")
     out = {k: rec[k] for k in keep if k in rec}
@@ -679,7 +685,7 @@ def dp1_leg(cfg, dev, B, L, steps=30):
             dist.destroy_process_group()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
@@ -695,8 +701,26 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the eager / grad_acc_step=4 / trainer-loop / DP-schedule legs")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed (losses and "
                     "forward outputs) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also run the roofline, HiFi-GAN stage, CPU-baseline, extra train-step, "
+                    "end-to-end synthesis and mel-extraction legs and write the long record (the --no-* options leave legs out)")
     ap.add_argument("--dp1-child", action="store_true", help=argparse.SUPPRESS)
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def plan_legs(args, world):
+    """What a run does beside the timed step, leg by leg.  A plain run: the HiFi-GAN batch alone (the metric's second half, one GPU).
+    `--full` adds the rest, each `--no-*` option leaving its leg out: the step's roofline (any world size), the HiFi-GAN stages, the
+    extra train-step legs (eager, grad_acc_step=4, trainer loop; the DP schedule in a child process), end-to-end synthesis, mel
+    extraction, the CPU baselines, and the long record beside the line."""
+    one, full = world == 1, args.full
+    hifi = one and not args.no_hifi
+    return {"hifi_gan": hifi, "hifi_stages": full and hifi, "roofline": full and not args.no_roofline,
+            "extra": full and one and not args.no_extra, "e2e": full and one and not args.no_e2e, "mel": full and one and not args.no_mel,
+            "cpu_baseline": full and one and not args.no_cpu_baseline, "full_record": full}
+
+
+def main():
+    args = parse_args()
     from tts_king_amd.hostcpu import fit_torch_threads
     fit_torch_threads()           # the host-side legs (eager launches, the trainer's loop) on the cores this process is granted
     if args.dp1_child:            # the DP-schedule leg in a process of its own (see dp1_leg_isolated)
@@ -713,7 +737,7 @@ def main():
         # it never makes one), relays rank 0's JSON line and exits non-zero if a rank failed or fewer than N devices are visible
         raise SystemExit(launch.spawn_ranks(args.gpus, [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]))
     dp1_rec = None
-    if args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_extra:
+    if args.gpus == 1 and plan_legs(args, int(os.environ.get("WORLD_SIZE", "1")))["extra"]:
         dp1_rec = dp1_leg_isolated(args)          # before this process touches the GPU
     # ONE JSON line on stdout, nothing else: RCCL prints a version banner to the C-level stdout when a communicator is created
     # (and flushes it at exit, i.e. AFTER the JSON line).  Everything the process or its libraries print goes to stderr; the
@@ -846,13 +870,14 @@ def main():
             rec["unknown_switches"] = switches.unknown_in_environment()      # TTSK_* variables nothing reads (tts_king_amd/switches.py)
         # the metric's second half right behind its first: both headline legs see the chip as the W warmup + K timed steps left it, neither
         # the state ~30 s of auxiliary legs (eager, grad_acc, trainer loop, roofline brackets) leave behind (HiFi-GAN measured 2 % slower there)
-        if world == 1 and not args.no_hifi:
+        legs = plan_legs(args, world)
+        if legs["hifi_gan"]:
             try:
                 from tts_king_amd.hifi_bench import hifi_rtf
-                rec["hifi_gan"] = hifi_rtf(cfg, dev)
+                rec["hifi_gan"] = hifi_rtf(cfg, dev, stages=legs["hifi_stages"])
             except ImportError:
                 rec["hifi_gan"] = None
-        if not args.no_roofline:
+        if legs["roofline"]:
             eager = make_enqueue(model, opt, cfg, loss_fn, reducer=None)
             rec["roofline"] = step_roofline(eager, batch)
             # the family with the most FLOPs behind one symbol's worth of launches (round 3's headline kernel), kept for continuity:
@@ -862,21 +887,23 @@ def main():
             if dwc:
                 rec["roofline"]["dwconv_grid"] = {"decoder_launch_workgroups": 192, "encoder_launch_workgroups": 128, "cus": 256,
                                                   "frac_of_peak": dwc[0]["frac_of_peak"]}
-        if world == 1 and not args.no_extra:
+        if legs["extra"]:
             rec.update(extra_train_legs(cfg, dev, B, L, steps=args.steps))
             rec["dp_schedule_1gpu"] = dp1_rec
-        if world == 1 and not args.no_e2e:
+        if legs["e2e"]:
             rec["e2e_synth"] = e2e_synth_leg(cfg, dev, with_cpu=not args.no_cpu_baseline)
-        if world == 1 and not args.no_mel:
+        if legs["mel"]:
             rec["mel_extraction"] = mel_extraction_leg(cfg, dev, with_cpu=not args.no_cpu_baseline)
-        if world == 1 and not args.no_cpu_baseline:
+        if legs["cpu_baseline"]:
             rec["cpu_baseline"] = cpu_baseline(cfg, B, L)
             if rec.get("hifi_gan"):
                 rec["hifi_gan"]["cpu_baseline"] = hifi_cpu_baseline(cfg)
-        sys.stdout.flush()
-        full = write_full_record(rec)
-        sys.stderr.write("bench.py full record (%s):\n%s\n" % (full, json.dumps(rec)))
-        sys.stderr.flush()
+        full = None
+        if legs["full_record"]:
+            sys.stdout.flush()
+            full = write_full_record(rec)
+            sys.stderr.write("bench.py full record (%s):\n%s\n" % (full, json.dumps(rec)))
+            sys.stderr.flush()
         os.write(real_stdout, (compact_record(rec, full) + "\n").encode())
     if world > 1:
         dist.barrier()

@@ -46,6 +46,42 @@ def test_line_fits_the_driver_tail_with_both_halves(path):
         assert abs(out["value"] - r["value"]) <= 1e-5 * r["value"] and abs(out["ms_per_step"] - r["ms_per_step"]) <= 1e-5 * r["ms_per_step"]
 
 
+def test_plain_run_does_only_the_headline_legs():
+    """bench.plan_legs: a plain run times the HiFi-GAN batch beside the step and nothing else; --full adds every other leg and the long
+    record, each --no-* option leaving its leg out; on more than one GPU a --full run adds the roofline alone."""
+    base = ["--gpus", "1", "--steps", "5", "--warmup", "2"]
+    assert bench.parse_args(base).full is False
+    on = lambda argv, world=1: sorted(k for k, v in bench.plan_legs(bench.parse_args(argv), world).items() if v)
+    everything = ["cpu_baseline", "e2e", "extra", "full_record", "hifi_gan", "hifi_stages", "mel", "roofline"]
+    assert on(base) == ["hifi_gan"]
+    assert on(base + ["--dump-outputs", "d"]) == ["hifi_gan"]
+    assert on(base + ["--no-hifi"]) == []
+    assert on(base + ["--full"]) == everything
+    assert on(base + ["--full", "--no-roofline", "--no-cpu-baseline", "--no-hifi"]) == ["e2e", "extra", "full_record", "mel"]
+    assert on(base + ["--full", "--no-extra", "--no-e2e", "--no-mel"]) == ["cpu_baseline", "full_record", "hifi_gan", "hifi_stages", "roofline"]
+    assert on(["--gpus", "2", "--full"], 2) == ["full_record", "roofline"]
+    assert on(["--gpus", "2"], 2) == []
+
+
+def test_plain_record_compacts_to_a_complete_line():
+    """compact_record on what a plain run records (no roofline, CPU baselines, HiFi-GAN stages or auxiliary legs, no side file): the
+    line still carries every contract key and both halves of the metric."""
+    rec = json.load(open(_full_records()[-1]))
+    plain = {k: rec[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                                 "vs_baseline", "dtype", "data", "config", "mel_frames_per_s_per_gpu", "model_tflops",
+                                 "step_mfma_roofline_frac", "final_losses", "hifi_gan")}
+    plain["hifi_gan"] = {k: v for k, v in plain["hifi_gan"].items() if k not in ("stages", "cpu_baseline")}
+    out = json.loads(bench.compact_record(plain))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "final_losses"):
+        assert k in out, k
+    for k in ("roofline", "cpu_baseline", "aux", "full_record"):
+        assert k not in out, k
+    assert out["hifi_gan"]["rtf"] > 0 and "stages" not in out["hifi_gan"]
+    assert out["metric"] == rec["metric"] and out["unit"] == rec["unit"] and out["dtype"] == rec["dtype"]
+    assert abs(out["value"] - rec["value"]) <= 1e-5 * rec["value"] and abs(out["ms_per_step"] - rec["ms_per_step"]) <= 1e-5 * rec["ms_per_step"]
+
+
 def test_line_refuses_to_grow_silently():
     rec = json.load(open(_full_records()[-1]))
     rec["config"]["workload"] = "x" * 7000

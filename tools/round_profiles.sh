@@ -3,7 +3,7 @@
 # the FS2 step and of the HiFi-GAN batch, the HBM-traffic PMC passes and the MFMA-utilisation PMC passes.
 # usage (GPU box): bash tools/round_profiles.sh <tag>   -> gpurun_out/round_<tag>/...
 R=${GRAFT_REPO_ROOT:-/root/repo}; TAG=${1:-r}; O=$R/gpurun_out/round_$TAG; mkdir -p $O; cd $R; export TMPDIR=/tmp
-timeout 1500 python bench.py > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 1500 python bench.py --full > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
 cp gpurun_out/bench_full.json $O/bench.json      # the long form (the line on stdout is the compact one the driver reads)
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/fs2_trace -o fs2 -- /usr/bin/python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-mel --no-e2e --no-hifi --no-extra > $O/fs2_trace.log 2>&1; echo "fs2 trace rc=$?"

@@ -94,11 +94,11 @@ def build_generator(cfg, dev, seed=1234):
     return g.eval()
 
 
-def hifi_rtf(cfg, dev, B=8, T=384, iters=20, warmup=3, use_graph=True, warm_replays=20):
+def hifi_rtf(cfg, dev, B=8, T=384, iters=20, warmup=3, use_graph=True, warm_replays=20, stages=True):
     """`warm_replays`: untimed replays of the captured graph before the timed ones — like the W warmup steps of bench.py's train-step leg, which
     are replays too.  (Round 5: the leg timed replays 2-21 of a freshly captured graph and read 2.44 ms where replays 6-55 of the same graph read
     2.34: the graph's buffers are new memory at capture, and the first replays pay for that — tools/debug/hifi_warm_curve.py: 2.587 ms over the
-    first ten, 2.39, then 2.38 steadily.)"""
+    first ten, 2.39, then 2.38 steadily.)  `stages`: also the per-stage rooflines (`stage_rooflines`: eager forwards of their own)."""
     gen = build_generator(cfg, dev)
     mel = make_mel(B, T, seed=1234).to(dev)
     for _ in range(warmup):
@@ -133,8 +133,11 @@ def hifi_rtf(cfg, dev, B=8, T=384, iters=20, warmup=3, use_graph=True, warm_repl
     i16 = ops.to_host(ops.to_int16(wav, float(cfg.hifi.MAX_WAV_VALUE)))
     d2h = time.perf_counter() - t1
     flops = HIFI_FLOP_PER_FRAME * B * T
-    return {"workload": "HiFi-GAN V1 generator, B=%d, T=%d mel frames -> %d samples @ %d Hz (BASELINE.json configs[2])" % (B, T, samples, int(sr)),
-            "rtf": wall / audio_s, "ms_per_batch": 1e3 * wall, "device_ms_per_batch": 1e3 * dev_s, "samples_per_s": samples / wall,
-            "audio_seconds_per_batch": audio_s, "tflops": flops / wall / 1e12, "mfma_roofline_frac": flops / wall / 2.5e15,
-            "int16_d2h_ms": 1e3 * d2h, "launch": "hipGraph replay" if use_graph else "eager", "dtype": "f16 (fp32 accumulate)",
-            "iters": iters, "warm_replays": max(1, warm_replays) if use_graph else 0, "stages": stage_rooflines(gen, mel, B, T)}
+    rec = {"workload": "HiFi-GAN V1 generator, B=%d, T=%d mel frames -> %d samples @ %d Hz (BASELINE.json configs[2])" % (B, T, samples, int(sr)),
+           "rtf": wall / audio_s, "ms_per_batch": 1e3 * wall, "device_ms_per_batch": 1e3 * dev_s, "samples_per_s": samples / wall,
+           "audio_seconds_per_batch": audio_s, "tflops": flops / wall / 1e12, "mfma_roofline_frac": flops / wall / 2.5e15,
+           "int16_d2h_ms": 1e3 * d2h, "launch": "hipGraph replay" if use_graph else "eager", "dtype": "f16 (fp32 accumulate)",
+           "iters": iters, "warm_replays": max(1, warm_replays) if use_graph else 0}
+    if stages:
+        rec["stages"] = stage_rooflines(gen, mel, B, T)
+    return rec
