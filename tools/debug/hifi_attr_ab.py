@@ -1,5 +1,5 @@
 """Generator attributes A/B'd on the replayed HiFi-GAN batch (B = 8, 384 mel frames), alternated on one box:
-python tools/debug/hifi_attr_ab.py name=value[,name=value] ...   e.g.  loop_upsample=False   window_conv_pre=False"""
+python tools/debug/hifi_attr_ab.py name=value[,name=value] ...   e.g.  loop_upsample=False   pair_ws=False"""
 import os, sys, time
 import torch
 sys.path.insert(0, os.getcwd())

@@ -139,7 +139,6 @@ class FastSpeech2(nn.Module):
         self._ctx = None
         self._deferred = None           # split-K slabs awaiting the batched reducer (backward only)
         self._deferred_fin = None       # gradient column-sum partials awaiting the batched finalize
-        self._side = None               # second HIP stream for parameter-gradient work (see _SideWork)
         # The FFT blocks' w_1 forward, q|k|v projection, fc and w_2 input gradients, and the PostNet's 512 -> 512 convs (forward and
         # input gradient) run on the window kernel (csrc/ffn_conv.hip).  It wants the weights in MFMA-fragment order (1 KiB contiguous
         # per fragment; from the tap-major shadow it is no faster than the implicit GEMM): `_w1_packed` holds such copies — for an input
@@ -148,21 +147,11 @@ class FastSpeech2(nn.Module):
         self.window_ffn = switches.get("TTSK_WINDOW_FFN") != "0"
         self._w1_packed = None
         self._adam_tables = None
-        self.adam_packs = True          # the optimizer's Adam launch writes the window kernels' weight packs itself (ttsk_optim_step_packed)
         self.flash_attention = True     # attention without the S x S tensors when d_k = 128 (csrc/flash_attn.hip); False / other head sizes: scores GEMM + softmax + P V GEMM
         self.fused_ln = True            # fc / w_2 + dropout + residual + LayerNorm + PAD zeroing in one kernel when d = 256
         self._postnet_ends_win = True       # the PostNet's 80 -> 512 / 512 -> 80 convs and their input gradients on the window kernel too (round 5; property below)
-        self.bn_stats_in_conv = True        # PostNet 512 -> 512 convs emit their BatchNorm statistics partials
-        self.bn_bwd_stats_in_conv = True    # ... and their input-gradient convs the backward's
-        self.fused_qkv_tail = True          # a block's last kernel also projects q|k|v for the next block
-        self.fused_qkv_dx = True            # ... and the q|k|v input gradient of the block behind in front of it
-        self.fused_ln_bwd = True            # LayerNorm backward + the k = 1 dX projection behind it in one kernel
         self.dwconv = switches.get("TTSK_DWCONV") != "0"   # w_1's weight gradient on the tap-sharing kernel (csrc/dwconv.hip), the other 256-multiple ones on dwgemm.hip
         self.group_predictors = True    # training with targets: the three VariancePredictors run as grouped launches
-        self.raw_slabs = True           # dX GEMMs that feed a LayerNorm backward leave their split-K tiles for it to sum
-        self.group_param_grads = True      # weight-gradient GEMMs of a backward pass share grouped launches (ops.DeferQueue)
-        self.overlap_param_grads = False   # measured on MI355X: the branches do overlap under graph replay, but the concurrent
-                                           # kernels slow each other by as much (6.39 vs 6.47 ms/step): off by default
         # The weight-gradient GEMMs of PostNet + decoder (88 % of the step's dW FLOPs) are complete once the decoder's backward is;
         # what follows on the dX path (length regulator, variance adaptor, encoder: ~0.5 ms of 32-128-workgroup kernels) fills a
         # fraction of the chip.  So that group is launched there on a second stream with its grid capped at `dw_side_wgs` workgroups
@@ -183,7 +172,6 @@ class FastSpeech2(nn.Module):
         # (Round 2's "early" schedule — a flush on the main stream whenever a bucket completes — measured 22 % more compute per step and
         # was deleted in round 4; without a second stream, dw_side_wgs = 0, buckets are still flushed one by one as they complete.)
         self.dp_schedule = switches.get("TTSK_DP_SCHEDULE")
-        self.side_small = False             # the 80-channel grouped problems behind dwgemm on the second stream (measured: they belong in the final phase)
         self._fin_side = None
         self._dp_keep = None
         self._fin_pending = False
@@ -274,7 +262,7 @@ class FastSpeech2(nn.Module):
         self._adam_tables = None
         self._shadow_version = -1
         self._rng_state = None
-        self._side = self._dw_side = self._fin_side = self._pred_stream = None
+        self._dw_side = self._fin_side = self._pred_stream = None
         self._rebind()
         if self.window_ffn and self._shadow.is_cuda:
             self._build_packs()
@@ -456,7 +444,7 @@ class FastSpeech2(nn.Module):
         # flat offset, storage shape and its plain / transposed packs.  A weight with more than one pack of a kind (w_1's transposed
         # pack exists once) or one that does not tile leaves `_adam_tables` None: the optimizer then calls refresh_packed as before.
         self._adam_tables = None
-        if self._pack_items and self.adam_packs:
+        if self._pack_items:
             by_key, ok = {}, True
             for key, fr, out, tr in self._pack_items:
                 W = self._pack_source(key, fr)
@@ -466,6 +454,10 @@ class FastSpeech2(nn.Module):
                 ent[3 if tr else 2] = out
             if ok:
                 self._adam_tables = ops.adam_pack_tables([tuple(v) for v in by_key.values()], self._n_flat, self._shadow.device)
+
+    def _pack(self, tag, key):
+        """The window kernel's pack `(tag, key)` of `_build_packs`, or None: no such pack, or no packs at all (TTSK_WINDOW_FFN=0)."""
+        return self._w1_packed.get((tag, key)) if (self.window_ffn and self._w1_packed) else None
 
     def _pack_source(self, key, fused_rows=None):
         """The tap-major bf16 shadow of `key` as a (Cs, k, Ds) tensor (a Linear weight is k = 1; `fused_rows`: the q|k|v rows as one)."""
@@ -525,7 +517,7 @@ class FastSpeech2(nn.Module):
         Sp = (S + 7) // 8 * 8
         dev = x.device
         # (1) q|k|v projections as one GEMM into a [rows][3d] buffer: SubLayers.py:41-43
-        pkq = self._w1_packed.get(("qkv", a + "w_qs.weight")) if (self.window_ffn and self._w1_packed) else None
+        pkq = self._pack("qkv", a + "w_qs.weight")
         if qkv is not None:
             pass                         # came out of the previous block's last kernel
         elif pkq is not None and x.dtype == bf16:
@@ -552,7 +544,7 @@ class FastSpeech2(nn.Module):
         qkv_next = None
         # (5) fc, dropout, +residual, LayerNorm, zero PAD rows: SubLayers.py:62-63, Layers.py:29 — one kernel when d = 256
         if fuse:
-            pkl = self._w1_packed.get(("fc", a + "fc.weight")) if (self.window_ffn and self._w1_packed) else None
+            pkl = self._pack("fc", a + "fc.weight")
             if pkl is not None:
                 x1, z1, mean1, rstd1 = ops.win_ln_fwd(o, pkl, self._m(a + "fc.bias"), x, self._m(a + "layer_norm.weight"),
                                                       self._m(a + "layer_norm.bias"), lens, S, p_pre=p, site_pre=site, rng=rng,
@@ -567,14 +559,14 @@ class FastSpeech2(nn.Module):
                                                         lens, S, p_pre=p, site_pre=site, rng=rng, save_z=ctx_list is not None)
         # (6) FFN: Conv1d(k=9)+ReLU, Conv1d(k=1), dropout, +residual, LayerNorm, zero PAD rows: SubLayers.py:96-99, Layers.py:32
         W1 = self._w(f + "w_1.weight")
-        pk = self._w1_packed.get(("w1", f + "w_1.weight")) if (self.window_ffn and self._w1_packed) else None
+        pk = self._pack("w1", f + "w_1.weight")
         if pk is not None and x1.dtype == bf16:
             h = ops.ffn_conv_fwd(x1.view(Bn, S, d), W1, self._m(f + "w_1.bias"), relu=True, packed=pk)      # window kernel (csrc/ffn_conv.hip)
         else:
             h = ops.conv1d(x1.view(Bn, S, d), W1, self._m(f + "w_1.bias"), flags=ops.RELU)
         if fuse and self.k2 == 1:
-            pkl = self._w1_packed.get(("w2", f + "w_2.weight")) if (self.window_ffn and self._w1_packed) else None
-            pkn = self._w1_packed.get(("qkv", next_pre + "slf_attn.w_qs.weight")) if (next_pre and pkl is not None and self.fused_qkv_tail) else None
+            pkl = self._pack("w2", f + "w_2.weight")
+            pkn = self._pack("qkv", next_pre + "slf_attn.w_qs.weight") if (next_pre and pkl is not None) else None
             if pkn is not None:
                 x2, z2, mean2, rstd2, qkv_next = ops.win_ln_fwd(h.view(rows, -1), pkl, self._m(f + "w_2.bias"), x1, self._m(f + "layer_norm.weight"),
                                                                 self._m(f + "layer_norm.bias"), lens, S, p_pre=p, site_pre=site + 1, rng=rng,
@@ -666,24 +658,22 @@ class FastSpeech2(nn.Module):
                                                     site_post=201, rng=rng, dhead=dstack.view(-1),
                                                     head_w=self._m(pre + "linear_layer.weight").view(-1))
         dh2 = dh2.view(3, rows, Fh)
-        with self._side_work(dh2, part, a1):
-            for g, n in enumerate(names):
-                cg = "variance_adaptor.%s_predictor.conv_layer." % n
-                self._finalize_ln(part[g], nblk, 4 * Fh + 1, cg + "conv1d_2.conv.bias")
-                ops.queue_dw(self._deferred, dh2[g].view(Bn, Lp, Fh), a1[g * rows:(g + 1) * rows].view(Bn, Lp, Fh), self._g(cg + "conv1d_2.conv.weight"),
-                             None, self._acc, k=self.k_var, use_dwgemm=self._use_dwconv)
+        for g, n in enumerate(names):
+            cg = "variance_adaptor.%s_predictor.conv_layer." % n
+            self._finalize_ln(part[g], nblk, 4 * Fh + 1, cg + "conv1d_2.conv.bias")
+            ops.queue_dw(self._deferred, dh2[g].view(Bn, Lp, Fh), a1[g * rows:(g + 1) * rows].view(Bn, Lp, Fh), self._g(cg + "conv1d_2.conv.weight"),
+                         None, self._acc, k=self.k_var, use_dwgemm=self._use_dwconv)
         da1 = torch.empty(3, rows, Fh, dtype=bf16, device=dev)
         ops.conv1d_dx(dh2[0].view(Bn, Lp, Fh), W2, out=da1[0].view(Bn, Lp, Fh), nz1=3, sA=(rows * Fh, 0), sB=(ps, 0), sC=(rows * Fh, 0))
         dh1, part, nblk = ops.layernorm_bwd_grouped(da1.view(3 * rows, Fh), h1.view(3 * rows, Fh), m1, r1, self._m(c + "layer_norm_1.weight"),
                                                     self._m(c + "layer_norm_1.bias"), 3, ps, 2, row_limit, Lp if row_limit is not None else 0,
                                                     relu_in=True, p_post=p, site_post=200, rng=rng)
         dh1 = dh1.view(3, rows, Fh)
-        with self._side_work(dh1, part, stack):
-            for g, n in enumerate(names):
-                cg = "variance_adaptor.%s_predictor.conv_layer." % n
-                self._finalize_ln(part[g], nblk, 3 * Fh, cg + "conv1d_1.conv.bias")
-                ops.queue_dw(self._deferred, dh1[g].view(Bn, Lp, Fh), stack[g].view(Bn, Lp, d), self._g(cg + "conv1d_1.conv.weight"), None,
-                             self._acc, k=self.k_var, use_dwgemm=self._use_dwconv)
+        for g, n in enumerate(names):
+            cg = "variance_adaptor.%s_predictor.conv_layer." % n
+            self._finalize_ln(part[g], nblk, 3 * Fh, cg + "conv1d_1.conv.bias")
+            ops.queue_dw(self._deferred, dh1[g].view(Bn, Lp, Fh), stack[g].view(Bn, Lp, d), self._g(cg + "conv1d_1.conv.weight"), None,
+                         self._acc, k=self.k_var, use_dwgemm=self._use_dwconv)
         dxin = torch.empty(3, rows, d, dtype=torch.float32, device=dev)
         ops.conv1d_dx(dh1[0].view(Bn, Lp, Fh), W1, out=dxin[0].view(Bn, Lp, d), nz1=3, sA=(rows * Fh, 0), sB=(ps, 0), sC=(rows * d, 0))
         return dxin
@@ -794,7 +784,7 @@ class FastSpeech2(nn.Module):
             y, qkv = y if nxt else (y, None)
         # ---- mel_linear (fp32 output + bf16 copy for the PostNet): fastspeech2.py:102
         rows = Bn * T
-        pkm = self._w1_packed.get(("lin", "mel_linear.weight")) if (self.window_ffn and self._w1_packed) else None
+        pkm = self._pack("lin", "mel_linear.weight")
         if pkm is not None and y.dtype == bf16:
             mel, mel16 = ops.win_conv_dual(y.view(Bn, T, d), pkm, self.n_mel, 1, bias=self._m("mel_linear.bias"))      # window kernel, k = 1
             mel, mel16 = mel.view(rows, self.n_mel), mel16.view(rows, self.n_mel)
@@ -810,11 +800,11 @@ class FastSpeech2(nn.Module):
         for i in range(5):
             pp = "postnet.convolutions.%d." % i
             # conv output stays fp32: BatchNorm divides by the batch std, which amplifies a bf16 rounding of it
-            pk = self._w1_packed.get(("pn", pp + "0.conv.weight")) if (self.window_ffn and self._w1_packed) else None
+            pk = self._pack("pn", pp + "0.conv.weight")
             stats = None
             if pk is not None and xin.dtype == bf16:
                 cw = self._table[pp + "0.conv.weight"].storage_shape
-                if train and xin.shape[2] in (512, 80) and ops.bn_slab_supported(cw[0]) and self.bn_stats_in_conv:
+                if train and xin.shape[2] in (512, 80) and ops.bn_slab_supported(cw[0]):
                     # window kernel; the BatchNorm statistics partials of its output come out of its epilogue
                     yc, stats = ops.win_conv_stats(xin, pk, cw[0], cw[1], bias=self._m(pp + "0.conv.bias"), frame_limit=fl)
                 else:
@@ -907,7 +897,7 @@ class FastSpeech2(nn.Module):
         xin = mel16.view(Bn, T, self.n_mel)
         for i in range(5):
             pp = "postnet.convolutions.%d." % i
-            pk = self._w1_packed.get(("pn", pp + "0.conv.weight")) if (self.window_ffn and self._w1_packed) else None
+            pk = self._pack("pn", pp + "0.conv.weight")
             if pk is not None and xin.dtype == bf16:
                 cw = self._table[pp + "0.conv.weight"].storage_shape
                 yc = ops.win_conv(xin, pk, cw[0], cw[1], bias=self._m(pp + "0.conv.bias"), out_dtype=torch.float32)   # window kernel
@@ -944,47 +934,10 @@ class FastSpeech2(nn.Module):
         off = self._table[first_key].offset
         ops.colsum_finalize(partials, nblk, ncol, ncol, self._flat_grad[off:off + ncol], accumulate=self._acc, defer=self._deferred_fin)
 
-    class _SideWork:
-        """Parameter-gradient work (dW GEMMs, bias / LayerNorm column sums) runs on a second HIP stream: nothing on the
-        dX critical path reads it, and most backward kernels fill a fraction of the 256 CUs, so the two chains overlap
-        (captured as parallel branches of the step's hipGraph).  Entering makes the side stream wait for everything the
-        main stream has enqueued (the producers of the tensors about to be read); leaving marks those tensors as in use
-        on the side stream so the caching allocator does not hand their memory to a later main-stream kernel."""
-
-        def __init__(self, model, tensors):
-            self.m, self.tensors = model, tensors
-
-        def __enter__(self):
-            m = self.m
-            if m._side is None:
-                return self
-            m._side.wait_stream(torch.cuda.current_stream())
-            self.ctx = torch.cuda.stream(m._side)
-            self.ctx.__enter__()
-            return self
-
-        def __exit__(self, *exc):
-            m = self.m
-            if m._side is None:
-                return False
-            for t in self.tensors:
-                if t is not None:
-                    t.record_stream(m._side)
-            self.ctx.__exit__(*exc)
-            return False
-
-    def _side_work(self, *tensors):
-        return FastSpeech2._SideWork(self, tensors)
-
-    def _join_side(self):
-        if self._side is not None:
-            torch.cuda.current_stream().wait_stream(self._side)
-
     def _raw_out_mode(self):
         """How a block hands its input gradient to the block in front of it (see _fft_bwd): "pre" = not at all — the consumer's first
         backward kernel (ttsk_layernorm_bwd_proj) computes it from dqkv; True = split-K slabs; the consumer must be that kernel."""
-        if (self.fused_qkv_dx and self.fused_ln_bwd and self.raw_slabs and self.window_ffn and self._w1_packed and self.d == 256 and
-                self.k2 == 1 and self.d_ff == 1024):
+        if self.window_ffn and self._w1_packed and self.d == 256 and self.k2 == 1 and self.d_ff == 1024:
             return "pre"
         return True
 
@@ -1001,13 +954,13 @@ class FastSpeech2(nn.Module):
         a, f = pre + "slf_attn.", pre + "pos_ffn."
         dev = z2.device
         # ---- FFN tail: LN backward (PAD rows carry no gradient), dropout mask regenerated
-        pk2 = self._w1_packed.get(("w2T", f + "w_2.weight")) if (self.window_ffn and self._w1_packed) else None
+        pk2 = self._pack("w2T", f + "w_2.weight")
         pre2 = None
         if isinstance(dx2, tuple) and len(dx2) == 3:          # (dqkv, packed transposed q|k|v weight, residual) of the block behind
             pre2, sl2, r2, dd2 = (dx2[0], dx2[1]), None, dx2[2], None
         else:
             sl2, r2, dd2 = (dx2[0], dx2[1], None) if isinstance(dx2, tuple) else (None, None, dx2)
-        fuse = self.fused_ln_bwd and d == 256 and self.k2 == 1
+        fuse = d == 256 and self.k2 == 1
         dh = None
         if fuse and pk2 is not None and h.shape[-1] == 1024:
             # (the q|k|v input gradient of the block behind +) LN backward + w_2's dX (ReLU gate on the way out) in one launch
@@ -1018,9 +971,8 @@ class FastSpeech2(nn.Module):
             dz2, dy2, part, nblk = ops.layernorm_bwd(dd2, z2, mean2, rstd2, self._m(f + "layer_norm.weight"), self._m(f + "layer_norm.bias"),
                                                      lens, S, p_pre=p, site_pre=site + 1, rng=rng, slabs=sl2, R=r2)
         # ---- w_2 (k=1): dW, dX gated by the ReLU
-        with self._side_work(dy2, part, h):
-            self._finalize_ln(part, nblk, 3 * d, f + "w_2.bias")
-            ops.queue_dw(self._deferred, dy2.view(Bn, S, d), h, self._g(f + "w_2.weight"), lens, self._acc, k=self.k2, use_dwgemm=self._use_dwconv)
+        self._finalize_ln(part, nblk, 3 * d, f + "w_2.bias")
+        ops.queue_dw(self._deferred, dy2.view(Bn, S, d), h, self._g(f + "w_2.weight"), lens, self._acc, k=self.k2, use_dwgemm=self._use_dwconv)
         if dh is not None:
             pass
         elif pk2 is not None and self.k2 == 1:
@@ -1028,41 +980,33 @@ class FastSpeech2(nn.Module):
         else:
             dh = ops.conv1d_dx(dy2.view(Bn, S, d), self._w(f + "w_2.weight"), G=h)
         # ---- w_1 (k=9): bias, dW, dX + residual gradient; the dX stays in split-K form for the attention LayerNorm's backward
-        with self._side_work(dh, x1):
-            ops.colsum_into(dh.view(rows, -1), self._g(f + "w_1.bias"), defer=self._deferred_fin, accumulate=self._acc)
-            if self._use_dwconv and self._deferred.group is not None and Bn <= 64 and dh.dtype == bf16 and ops.dwconv_supported(dh.shape[-1], d, self.k1):
-                # the taps share one fetch of dh and one window of x1 (csrc/dwconv.hip); dh is zero at PAD rows (the LayerNorm backward
-                # that produced dy2 gives them no gradient), so only the rows of each utterance's own length are walked
-                self._deferred.dwconv.append((dh, x1.view(Bn, S, d), self._g(f + "w_1.weight"), lens, self._acc))
-            else:
-                ops.conv1d_dw(dh, x1.view(Bn, S, d), self._g(f + "w_1.weight"), k=self.k1, defer=self._deferred, accumulate=self._acc)
+        ops.colsum_into(dh.view(rows, -1), self._g(f + "w_1.bias"), defer=self._deferred_fin, accumulate=self._acc)
+        if self._use_dwconv and Bn <= 64 and dh.dtype == bf16 and ops.dwconv_supported(dh.shape[-1], d, self.k1):
+            # the taps share one fetch of dh and one window of x1 (csrc/dwconv.hip); dh is zero at PAD rows (the LayerNorm backward
+            # that produced dy2 gives them no gradient), so only the rows of each utterance's own length are walked
+            self._deferred.dwconv.append((dh, x1.view(Bn, S, d), self._g(f + "w_1.weight"), lens, self._acc))
+        else:
+            ops.conv1d_dw(dh, x1.view(Bn, S, d), self._g(f + "w_1.weight"), k=self.k1, defer=self._deferred, accumulate=self._acc)
         # ---- attention tail
         do = delta = None
-        if self.raw_slabs:
-            pk1 = self._w1_packed.get(("w1T", f + "w_1.weight")) if (self.window_ffn and self._w1_packed) else None
-            if pk1 is not None:
-                sl = ops.win_conv_split(dh, pk1, d, self.k1)       # four 256-channel slices of the 1024-channel contraction, one launch
-            else:
-                sl = ops.conv1d_dx(dh, self._w(f + "w_1.weight"), raw=True)
-            pkf = self._w1_packed.get(("fcT", a + "fc.weight")) if (self.window_ffn and self._w1_packed) else None
-            if fuse and pkf is not None and lens is not None:
-                # LN backward + fc's dX (+ the attention backward's delta) in one launch
-                if flash and o32 is not None:
-                    delta = torch.empty(Bn * H, S, dtype=torch.float32, device=dev)
-                dz1, dy1, part, nblk, do = ops.layernorm_bwd_proj(None, z1, mean1, rstd1, self._m(a + "layer_norm.weight"), pkf, d, lens, S,
-                                                                  p_pre=p, site_pre=site, rng=rng, slabs=sl, R=dz2,
-                                                                  delta_o32=o32 if delta is not None else None, delta_out=delta)
-            else:
-                dz1, dy1, part, nblk = ops.layernorm_bwd(None, z1, mean1, rstd1, self._m(a + "layer_norm.weight"), self._m(a + "layer_norm.bias"),
-                                                         lens, S, p_pre=p, site_pre=site, rng=rng, slabs=sl, R=dz2)
+        pk1 = self._pack("w1T", f + "w_1.weight")
+        if pk1 is not None:
+            sl = ops.win_conv_split(dh, pk1, d, self.k1)       # four 256-channel slices of the 1024-channel contraction, one launch
         else:
-            dx1 = ops.conv1d_dx(dh, self._w(f + "w_1.weight"), R=dz2.view(Bn, S, d))
-            dz1, dy1, part, nblk = ops.layernorm_bwd(dx1.view(rows, d), z1, mean1, rstd1, self._m(a + "layer_norm.weight"),
-                                                     self._m(a + "layer_norm.bias"), lens, S, p_pre=p, site_pre=site, rng=rng)
-        with self._side_work(dy1, part, o):
-            self._finalize_ln(part, nblk, 3 * d, a + "fc.bias")
-            ops.queue_dw(self._deferred, dy1.view(Bn, S, d), o.view(Bn, S, d), self._g(a + "fc.weight"), lens, self._acc, use_dwgemm=self._use_dwconv)
-        pkf = self._w1_packed.get(("fcT", a + "fc.weight")) if (self.window_ffn and self._w1_packed) else None
+            sl = ops.conv1d_dx(dh, self._w(f + "w_1.weight"), raw=True)
+        pkf = self._pack("fcT", a + "fc.weight")
+        if fuse and pkf is not None and lens is not None:
+            # LN backward + fc's dX (+ the attention backward's delta) in one launch
+            if flash and o32 is not None:
+                delta = torch.empty(Bn * H, S, dtype=torch.float32, device=dev)
+            dz1, dy1, part, nblk, do = ops.layernorm_bwd_proj(None, z1, mean1, rstd1, self._m(a + "layer_norm.weight"), pkf, d, lens, S,
+                                                              p_pre=p, site_pre=site, rng=rng, slabs=sl, R=dz2,
+                                                              delta_o32=o32 if delta is not None else None, delta_out=delta)
+        else:
+            dz1, dy1, part, nblk = ops.layernorm_bwd(None, z1, mean1, rstd1, self._m(a + "layer_norm.weight"), self._m(a + "layer_norm.bias"),
+                                                     lens, S, p_pre=p, site_pre=site, rng=rng, slabs=sl, R=dz2)
+        self._finalize_ln(part, nblk, 3 * d, a + "fc.bias")
+        ops.queue_dw(self._deferred, dy1.view(Bn, S, d), o.view(Bn, S, d), self._g(a + "fc.weight"), lens, self._acc, use_dwgemm=self._use_dwconv)
         if do is not None:
             pass
         elif pkf is not None:
@@ -1090,18 +1034,16 @@ class FastSpeech2(nn.Module):
                      sA=(H * S * Sp, S * Sp), sB=(S * d, dk), sC=(S * 3 * d, dk), group=kv)
             kv.flush()
         # ---- q|k|v projections
-        with self._side_work(dqkv, x):
-            ops.colsum_into(dqkv, self._g(a + "w_qs.bias", 3 * d), defer=self._deferred_fin, accumulate=self._acc)
-            ops.queue_dw(self._deferred, dqkv.view(Bn, S, 3 * d), x.view(Bn, S, d), self._g(a + "w_qs.weight", 3 * d * d).view(3 * d, d), lens,
-                         self._acc, use_dwgemm=self._use_dwconv)
-        if raw_out and self.raw_slabs:
-            pkq = self._w1_packed.get(("qkvT", a + "w_qs.weight")) if (self.window_ffn and self._w1_packed) else None
+        ops.colsum_into(dqkv, self._g(a + "w_qs.bias", 3 * d), defer=self._deferred_fin, accumulate=self._acc)
+        ops.queue_dw(self._deferred, dqkv.view(Bn, S, 3 * d), x.view(Bn, S, d), self._g(a + "w_qs.weight", 3 * d * d).view(3 * d, d), lens,
+                     self._acc, use_dwgemm=self._use_dwconv)
+        pkq = self._pack("qkvT", a + "w_qs.weight")
+        if raw_out:
             if pkq is not None and raw_out == "pre" and d == 256:
                 return (dqkv, pkq, dz1)          # the consumer (the next block's first backward kernel) multiplies by the weight itself
             if pkq is not None:
                 return (ops.win_conv_split(dqkv.view(Bn, S, 3 * d), pkq, d, 1), dz1)
             return (ops.linear_dx(dqkv, self._w(a + "w_qs.weight", 3 * d), raw=True), dz1)
-        pkq = self._w1_packed.get(("qkvT", a + "w_qs.weight")) if (self.window_ffn and self._w1_packed and self.fused_qkv_dx) else None
         if pkq is not None and d == 256 and dqkv.shape[1] == 768:
             return ops.qkv_dx(dqkv, pkq, R=dz1)       # the first block of the stack: the same 32-row product as a kernel of its own
         return ops.linear_dx(dqkv, self._w(a + "w_qs.weight", 3 * d), R=dz1)
@@ -1115,16 +1057,14 @@ class FastSpeech2(nn.Module):
         dh2, _, part, nblk = ops.layernorm_bwd(None, h2.view(rows, Fh), m2, r2, self._m(c + "layer_norm_2.weight"),
                                                self._m(c + "layer_norm_2.bias"), lens, Lp, relu_in=True, p_post=p,
                                                site_post=site + 1, rng=rng, dhead=dout.contiguous().view(-1), head_w=hw)
-        with self._side_work(dh2, part, a1):
-            self._finalize_ln(part, nblk, 4 * Fh + 1, c + "conv1d_2.conv.bias")
-            ops.conv1d_dw(dh2.view(Bn, Lp, Fh), a1.view(Bn, Lp, Fh), self._g(c + "conv1d_2.conv.weight"), k=self.k_var, defer=self._deferred, accumulate=self._acc)
+        self._finalize_ln(part, nblk, 4 * Fh + 1, c + "conv1d_2.conv.bias")
+        ops.conv1d_dw(dh2.view(Bn, Lp, Fh), a1.view(Bn, Lp, Fh), self._g(c + "conv1d_2.conv.weight"), k=self.k_var, defer=self._deferred, accumulate=self._acc)
         da1 = ops.conv1d_dx(dh2.view(Bn, Lp, Fh), self._w(c + "conv1d_2.conv.weight"))
         dh1, _, part, nblk = ops.layernorm_bwd(da1.view(rows, Fh), h1.view(rows, Fh), m1, r1, self._m(c + "layer_norm_1.weight"),
                                                self._m(c + "layer_norm_1.bias"), None, 0, relu_in=True, p_post=p,
                                                site_post=site, rng=rng)
-        with self._side_work(dh1, part, x):
-            self._finalize_ln(part, nblk, 3 * Fh, c + "conv1d_1.conv.bias")
-            ops.conv1d_dw(dh1.view(Bn, Lp, Fh), x.view(Bn, Lp, d), self._g(c + "conv1d_1.conv.weight"), k=self.k_var, defer=self._deferred, accumulate=self._acc)
+        self._finalize_ln(part, nblk, 3 * Fh, c + "conv1d_1.conv.bias")
+        ops.conv1d_dw(dh1.view(Bn, Lp, Fh), x.view(Bn, Lp, d), self._g(c + "conv1d_1.conv.weight"), k=self.k_var, defer=self._deferred, accumulate=self._acc)
         return ops.conv1d_dx(dh1.view(Bn, Lp, Fh), self._w(c + "conv1d_1.conv.weight"), R=R)
 
     def _finalize_loss(self):
@@ -1159,7 +1099,7 @@ class FastSpeech2(nn.Module):
         with torch.cuda.stream(self._dw_side):
             ops.stamp("side.start")
             ops.flush_deferred_gemms(self._deferred, max_wgs=self.dw_side_wgs, frac=1.0 if everything else self.dw_side_frac,
-                                     small_too=True if everything else self.side_small)
+                                     small_too=everything)
             ops.stamp("side.end")
         self._dw_side_pending = True
 
@@ -1194,7 +1134,6 @@ class FastSpeech2(nn.Module):
 
     def _flush_param_grads(self):
         """Run the queued weight-gradient work (grouped dW GEMMs, split-K reducers, column sums, scatter-sums)."""
-        self._join_side()
         if self._dw_side_pending:
             # The main stream gets here ~0.1 ms before the capped dW group on the side stream ends.  The column sums / scatter-sums read
             # only activations and gradients the main chain produced: they run now, beside the side stream; the encoder-side dW group
@@ -1262,13 +1201,11 @@ class FastSpeech2(nn.Module):
         d, rows, nm = self.d, Bn * T, self.n_mel
         # split-K slabs of the weight-gradient GEMMs are summed by ONE batched reducer launch per parameter group when a
         # data-parallel reducer is waiting for finished buckets, otherwise once at the end (only Adam reads them)
-        self._deferred = ops.DeferQueue(group_gemms=self.group_param_grads)
+        self._deferred = ops.DeferQueue()
         self._deferred_fin = []
-        if self.overlap_param_grads and self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
         if self.dp_schedule not in ("side", "late"):
             raise ValueError("dp_schedule must be 'side' or 'late' (got %r)" % (self.dp_schedule,))
-        dp_side = on_bucket is not None and self.dw_side_wgs > 0 and self.group_param_grads and not self.overlap_param_grads
+        dp_side = on_bucket is not None and self.dw_side_wgs > 0
         self._dp_marks = []
         # w_1's weight gradients on the tap-sharing kernel: one launch for the six decoder blocks (192 workgroups) and one for the encoder's;
         # not when buckets are flushed one by one (no second stream): those flushes would launch them two at a time
@@ -1279,8 +1216,7 @@ class FastSpeech2(nn.Module):
         # ---- the predictors' backward up to their input gradients, on a stream of its own beside the PostNet's (see pred_side); not in
         # the schedules that flush the deferred queue before the decoder is done
         pred_dxin = None
-        if (self.pred_side in ("1", "b") and "grouped" in ctx.preds and (on_bucket is None or dp_side) and not self.overlap_param_grads
-                and self.group_param_grads):
+        if self.pred_side in ("1", "b") and "grouped" in ctx.preds and (on_bucket is None or dp_side):
             if self._pred_stream is None:
                 self._pred_stream = torch.cuda.Stream(device=self.device)
             if not self._var_on_pred:             # (the two-stream loss left dlogd / dpitch / denergy ON that stream: nothing of this one is needed)
@@ -1301,16 +1237,15 @@ class FastSpeech2(nn.Module):
                             p=self.p_post, site=300 + i, rng=rng, dgamma=self._g(pp + "1.weight"), dbeta=self._g(pp + "1.bias"),
                             frame_limit=ctx.frame_limit, keep=keep, accumulate=self._acc, partials=bn_partials)
             bn_partials = None
-            with self._side_work(dy, xin):
-                ops.colsum_into(dy, self._g(pp + "0.conv.bias"), defer=self._deferred_fin, accumulate=self._acc)
-                # (no `lens`: the PostNet's BatchNorm runs over the PAD rows too, Layers.py:133-143 — its gradients there are not zero)
-                ops.queue_dw(self._deferred, dy.view(Bn, T, C), xin, self._g(pp + "0.conv.weight"), None, self._acc, k=5,
-                             use_dwgemm=self._use_dwconv)
-            pkt = self._w1_packed.get(("pnT", pp + "0.conv.weight")) if (self.window_ffn and self._w1_packed) else None
+            ops.colsum_into(dy, self._g(pp + "0.conv.bias"), defer=self._deferred_fin, accumulate=self._acc)
+            # (no `lens`: the PostNet's BatchNorm runs over the PAD rows too, Layers.py:133-143 — its gradients there are not zero)
+            ops.queue_dw(self._deferred, dy.view(Bn, T, C), xin, self._g(pp + "0.conv.weight"), None, self._acc, k=5,
+                         use_dwgemm=self._use_dwconv)
+            pkt = self._pack("pnT", pp + "0.conv.weight")
             if i > 0 and pkt is not None:
                 cw = self._table[pp + "0.conv.weight"].storage_shape
                 pb, _, ycb, meanb, rstdb, keepb = ctx.pn[i - 1]
-                if (self.bn_bwd_stats_in_conv and C in (512, 80) and cw[2] == 512 and ycb.dtype == torch.float32 and ops.bn_slab_supported(cw[2])
+                if (C in (512, 80) and cw[2] == 512 and ycb.dtype == torch.float32 and ops.bn_slab_supported(cw[2])
                         and (keepb is not None or self.p_post == 0.0)):
                     # ... which also sums the BatchNorm-backward statistics of the layer below over its output tile
                     dout, bn_partials = ops.win_conv_bnb(dy.view(Bn, T, C), pkt, cw[2], cw[1], ycb.view(rows, cw[2]), meanb, rstdb,
@@ -1332,10 +1267,9 @@ class FastSpeech2(nn.Module):
         notify("postnet")
         ops.stamp("bwd.postnet_done")
         # ---- mel_linear
-        with self._side_work(dmel_tot, ctx.dec_out):
-            ops.colsum_into(dmel_tot, self._g("mel_linear.bias"), defer=self._deferred_fin, accumulate=self._acc)
-            ops.linear_dw(dmel_tot, ctx.dec_out, self._g("mel_linear.weight"), defer=self._deferred, accumulate=self._acc)
-        pkm = self._w1_packed.get(("linT", "mel_linear.weight")) if (self.window_ffn and self._w1_packed) else None
+        ops.colsum_into(dmel_tot, self._g("mel_linear.bias"), defer=self._deferred_fin, accumulate=self._acc)
+        ops.linear_dw(dmel_tot, ctx.dec_out, self._g("mel_linear.weight"), defer=self._deferred, accumulate=self._acc)
+        pkm = self._pack("linT", "mel_linear.weight")
         if pkm is not None and dmel_tot.dtype == bf16:
             dx = ops.win_conv(dmel_tot.view(Bn, T, nm), pkm, d, 1).view(rows, d)      # mel_linear's input gradient: a k = 1 conv on the transposed pack
         else:
@@ -1350,27 +1284,23 @@ class FastSpeech2(nn.Module):
             torch.cuda.current_stream().wait_stream(self._pred_stream)    # long done; its queued dW work joins the second stream's
         if dp_side and self.dp_schedule == "side":
             self._launch_dw_side_buckets(on_bucket, notifier.ready)
-        elif self.dw_side_wgs > 0 and (on_bucket is None or dp_side) and self.group_param_grads and not self.overlap_param_grads:
+        elif self.dw_side_wgs > 0:
             self._launch_dw_side()
         # ---- length regulator: segment sums (the position table has no parameters)
         dx3 = ops.length_regulator_bwd(dx.view(Bn, T, d), ctx.cs, Lp).view(Bn * Lp, d)
         # ---- variance adaptor, reverse order of modules.py:158-193
         va = "variance_adaptor."
-        with self._side_work(dx3):
-            ops.scatter_sum(dx3, ctx.eidx.view(-1), self._g(va + "energy_embedding.weight"), defer=self._deferred_fin, accumulate=self._acc)
+        ops.scatter_sum(dx3, ctx.eidx.view(-1), self._g(va + "energy_embedding.weight"), defer=self._deferred_fin, accumulate=self._acc)
         if "grouped" in ctx.preds:
             dx2, dx1, dxe = self._predictors_bwd_grouped(ctx.preds["grouped"], None if pred_dxin is not None else
                                                          self._stack3(dlogd, dpitch, denergy), rng, dx3, dxin=pred_dxin)
-            with self._side_work(dx2, dx1):
-                ops.scatter_sum(dx2, ctx.pidx.view(-1), self._g(va + "pitch_embedding.weight"), defer=self._deferred_fin, accumulate=self._acc)
-                ops.scatter_sum(dx1, ctx.speakers, self._g("speaker_emb.weight"), idx_div=Lp, defer=self._deferred_fin, accumulate=self._acc)
+            ops.scatter_sum(dx2, ctx.pidx.view(-1), self._g(va + "pitch_embedding.weight"), defer=self._deferred_fin, accumulate=self._acc)
+            ops.scatter_sum(dx1, ctx.speakers, self._g("speaker_emb.weight"), idx_div=Lp, defer=self._deferred_fin, accumulate=self._acc)
         else:
             dx2 = self._predictor_bwd(va + "energy_predictor.", ctx.preds[va + "energy_predictor."], denergy, rng, dx3.view(Bn, Lp, d))
-            with self._side_work(dx2):
-                ops.scatter_sum(dx2.view(Bn * Lp, d), ctx.pidx.view(-1), self._g(va + "pitch_embedding.weight"), defer=self._deferred_fin, accumulate=self._acc)
+            ops.scatter_sum(dx2.view(Bn * Lp, d), ctx.pidx.view(-1), self._g(va + "pitch_embedding.weight"), defer=self._deferred_fin, accumulate=self._acc)
             dx1 = self._predictor_bwd(va + "pitch_predictor.", ctx.preds[va + "pitch_predictor."], dpitch, rng, dx2)
-            with self._side_work(dx1):
-                ops.scatter_sum(dx1.view(Bn * Lp, d), ctx.speakers, self._g("speaker_emb.weight"), idx_div=Lp, defer=self._deferred_fin, accumulate=self._acc)
+            ops.scatter_sum(dx1.view(Bn * Lp, d), ctx.speakers, self._g("speaker_emb.weight"), idx_div=Lp, defer=self._deferred_fin, accumulate=self._acc)
             dxe = self._predictor_bwd(va + "duration_predictor.", ctx.preds[va + "duration_predictor."], dlogd, rng, dx1)
         notify("variance_adaptor")
         # ---- encoder
@@ -1378,8 +1308,7 @@ class FastSpeech2(nn.Module):
         for i in range(self.n_enc - 1, -1, -1):
             dx = self._fft_bwd(ctx.blocks[i], dx, rng, raw_out=self._raw_out_mode() if i > 0 else False)
             notify("encoder.%d" % i)
-        with self._side_work(dx):
-            ops.scatter_sum(dx, ctx.texts.view(-1), self._g("encoder.src_word_emb.weight"), skip_row=0, defer=self._deferred_fin, accumulate=self._acc)   # padding_idx=0
+        ops.scatter_sum(dx, ctx.texts.view(-1), self._g("encoder.src_word_emb.weight"), skip_row=0, defer=self._deferred_fin, accumulate=self._acc)   # padding_idx=0
         notify("embedding")
         ops.stamp("bwd.chain_done")
         self._flush_param_grads()

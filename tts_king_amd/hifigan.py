@@ -105,9 +105,7 @@ class Generator(nn.Module):
         self.fused = True            # fused ResBlock1 kernel where an instance exists (C in {32,64}); False = conv-by-conv
         self.stream_upsample = True  # stride-2 upsamplers (128->64, 64->32) on the streaming kernel; False = polyphase implicit GEMMs
         self.window_upsample = switches.get("TTSK_HIFI_UPS8") != "0"   # stride-8 upsamplers and 128 -> 64 on the window-conv kernel (fp16); 0 = polyphase GEMMs / streaming kernel
-        self.window_conv_pre = True       # conv_pre on the window-conv kernel (False: the implicit GEMM)
         self.loop_upsample = True         # the 256 -> 128 upsampler on ups_loop_kernel (False: win_conv_kernel, one channel group per workgroup)
-        self.group_resblocks = True  # conv m of the three MRF ResBlocks as one grouped launch where they run conv by conv (C = 256)
         self.mrf_fused = True        # the last stage (C = 32: three ResBlock1s + average + LeakyReLU + conv_post + tanh) as ONE launch (csrc/mrf32.hip)
 
     # ------------------------------------------------------------------ reference surface
@@ -151,7 +149,7 @@ class Generator(nn.Module):
         pk = {}
         pk["pre"] = (ops.pack_conv_weight(self.conv_pre.folded_weight(), dtype=dt), self.conv_pre.bias.data)
         cpre, kpre = pk["pre"][0].shape[0], pk["pre"][0].shape[1]
-        pk["pre_win"] = (ops.hifi_conv_pre_win_pack(pk["pre"][0]) if (self.window_upsample and self.window_conv_pre and dt == torch.float16 and
+        pk["pre_win"] = (ops.hifi_conv_pre_win_pack(pk["pre"][0]) if (self.window_upsample and dt == torch.float16 and
                                                                       ops.hifi_conv_pre_win_supported(int(pk["pre"][0].shape[2]), cpre, kpre)) else None)
         pk["ups"] = [(ops.pack_conv_weight(u.folded_weight(), transposed=True, dtype=dt), u.bias.data) for u in self.ups]
         # the stride-8 upsamplers and the 128 -> 64 stride-2 one on the window-conv kernel (fp16 rows): a two-tap conv over the input frames
@@ -351,8 +349,7 @@ class Generator(nn.Module):
                 axl = torch.empty(al.shape[0], al.shape[1] * u, wu.shape[1], dtype=al.dtype, device=al.device)
                 a = ops.conv_transpose1d(al, wu, bu, u, k, C2=axl, flags=ops.C2_LRELU, out_slope=LRELU_SLOPE)   # x and lrelu(x)
                 self._mark("ups%d" % i)
-                if self.group_resblocks and all(rb.kind == "1" for rb in rbs) and len({len(rb.dilation) for rb in rbs}) == 1 and \
-                        not windowed:
+                if all(rb.kind == "1" for rb in rbs) and len({len(rb.dilation) for rb in rbs}) == 1 and not windowed:
                     outs = self._resblocks_lockstep(rbs, [pk["rb"][i * nk + j] for j in range(nk)], a, axl)
                 else:
                     outs = [self._resblock(rb, pk["rb"][i * nk + j], a, axl, pk["rbw"][i * nk + j]) for j, rb in enumerate(rbs)]
