@@ -488,6 +488,15 @@ int ttsk_hifi_conv_pair_ws_supported(int C, int K, int dil);
 int ttsk_hifi_conv_pair_ws(const void* x16, const void* w1_pack, const float* bias1, const void* w2_pack, const float* bias2, void* out16,
                            int f16, int B, int len, int C, int K, int dil, float slope, int mode, float scale, float final_slope,
                            int max_wgs, void* stream);
+/* ResBlock2 (hifi/models.py:104-143, the block of the V3 generator) as ONE launch, csrc/resblock2.hip: x16 is the raw block input
+ * (B, len, C), x1 = x + b0 + conv_{K,d0}(lrelu(x)), y = x1 + b1 + conv_{K,d1}(lrelu(x1)); x1 (rounded to the 16-bit type) and
+ * lrelu(x1) stay in LDS, each conv sees zeros outside [0, len).  w*_pack: ttsk_pack_resblock_weight packs; out must not alias x.
+ * mode as ttsk_hifi_conv_pair (0: out = y   1: out += y   2: out = lrelu((out + y) * scale, final_slope)): a stage of three blocks is
+ * three launches.  C in {32, 64, 128}, K in {3, 5, 7}, (K-1)/2 * d0 <= 16, (K-1)/2 * d1 <= 40 (C = 128) / 48 (C = 64) / 64 (C = 32). */
+int ttsk_hifi_resblock2_supported(int C, int K, int d0, int d1);
+int ttsk_hifi_resblock2(const void* x16, const void* w0_pack, const float* bias0, const void* w1_pack, const float* bias1, void* out16,
+                        int f16, int B, int len, int C, int K, int d0, int d1, float slope, int mode, float scale, float final_slope,
+                        void* stream);
 /* conv_post + tanh (hifi/models.py:198-199): x (B, len, C) 16-bit (already activated), w (1, k, C) tap-major 16-bit,
  * out (B, 1, len) fp32.  A streaming kernel: one output sample per thread. */
 int ttsk_hifi_conv_post(const void* x16, const void* w16, const float* bias, float* out, int f16, int B, int len, int C, int K,

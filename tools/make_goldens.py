@@ -220,6 +220,38 @@ def g8_shapes():
     print("G8 fs2 keys", len(sd), "hifi", len(sdw), len(sdf))
 
 
+# the published HiFi-GAN V3 generator (config_v3): ResBlock2, three upsamplers; every other `hifi:` key as in config.yaml
+HIFI_V3 = dict(resblock="2", upsample_rates=[8, 8, 4], upsample_kernel_sizes=[16, 16, 8], upsample_initial_channel=256,
+               resblock_kernel_sizes=[3, 5, 7], resblock_dilation_sizes=[[1, 2], [2, 6], [3, 12]])
+
+
+def g12_hifigan_v3():
+    """g7_hifigan and the HiFi-GAN half of g8_shapes for the V3 generator (ResBlock2, hifi/models.py:104-143): waveform, int16
+    samples, fold probes and both key / shape lists in one file."""
+    h = AD(dict(cfg.hifi, **HIFI_V3))
+    torch.manual_seed(0)
+    gen = Generator(h)
+    sd_wn = gen.state_dict()
+    seeded_fill(sd_wn, WEIGHT_SEED)
+    wn_keys, wn_shapes = list(sd_wn.keys()), [";".join(map(str, v.shape)) for v in sd_wn.values()]
+    gen.remove_weight_norm()
+    gen.eval()
+    folded = gen.state_dict()
+    mel = make_mel(2, 32, seed=21)
+    with torch.no_grad():
+        wav = gen(mel)
+        i16 = (wav * h.MAX_WAV_VALUE).cpu().numpy().astype("int16")
+    probe = ["ups.0.weight", "ups.2.weight", "conv_pre.weight", "resblocks.8.convs.1.weight", "conv_post.weight"]
+    np.savez_compressed(os.path.join(OUT, "hifi_v3_b2_t32.npz"), B=2, T=32, seed=21, weight_seed=WEIGHT_SEED,
+                        wav=npy(wav), int16=i16, n_wn_keys=len(wn_keys), n_folded_keys=len(folded),
+                        wn_keys=np.array(wn_keys), wn_shapes=np.array(wn_shapes), keys=np.array(list(folded.keys())),
+                        shapes=np.array([";".join(map(str, v.shape)) for v in folded.values()]),
+                        **{("fold/" + k): npy(folded[k]).ravel()[:64] for k in probe},
+                        **{("foldnorm/" + k): float(folded[k].norm()) for k in probe})
+    print("G12 V3 wav", tuple(wav.shape), "absmax", float(wav.abs().max()), "rms", float(wav.pow(2).mean().sqrt()),
+          "keys", len(wn_keys), len(folded))
+
+
 def g9_text():
     """Symbol inventory (data asset pretrained/symbols.json: the id of a symbol is its position + the model's vocabulary
     is len + 1, Models.py:40) and known-answer vectors of `text_to_sequence` (examples.ipynb cell 2 plus a few more)."""
@@ -320,6 +352,9 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "collate":
         g10_collate()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "hifi_v3":
+        g12_hifigan_v3()
+        sys.exit(0)
     g1_eval_teacher_forced()
     g2_eval_free_running()
     g3_train_no_dropout()
@@ -330,3 +365,4 @@ if __name__ == "__main__":
     g9_text()
     g10_collate()
     g11_mel()
+    g12_hifigan_v3()

@@ -1,4 +1,4 @@
-"""HiFi-GAN V1 generator inference on MI355X: the reference's `Generator(h)` surface (constructor, weight-normed
+"""HiFi-GAN generator inference on MI355X (V1 and V3 configurations): the reference's `Generator(h)` surface (constructor, weight-normed
 `state_dict` keys, `remove_weight_norm()`, `forward((B,80,T)) -> (B,1,T*prod(upsample_rates))`) over hand-written
 gfx950 kernels.
 
@@ -107,6 +107,7 @@ class Generator(nn.Module):
         self.window_upsample = switches.get("TTSK_HIFI_UPS8") != "0"   # stride-8 upsamplers and 128 -> 64 on the window-conv kernel (fp16); 0 = polyphase GEMMs / streaming kernel
         self.loop_upsample = True         # the 256 -> 128 upsampler on ups_loop_kernel (False: win_conv_kernel, one channel group per workgroup)
         self.mrf_fused = True        # the last stage (C = 32: three ResBlock1s + average + LeakyReLU + conv_post + tanh) as ONE launch (csrc/mrf32.hip)
+        self.resblock2_fused = True  # each ResBlock2 (V3) as ONE launch with the MRF average folded in (csrc/resblock2.hip); False = conv by conv
 
     # ------------------------------------------------------------------ reference surface
     def remove_weight_norm(self):
@@ -157,10 +158,14 @@ class Generator(nn.Module):
         pk["ups8"] = [ops.hifi_upsample_win_pack(w, b, uu) if (self.window_upsample and dt == torch.float16 and
                                                                ops.hifi_upsample_win_supported(w.shape[2], w.shape[1], uu, kk)) else None
                       for (w, b), uu, kk in zip(pk["ups"], self.h.upsample_rates, self.h.upsample_kernel_sizes)]
-        pk["rb"], pk["rbf"], pk["rbw"] = [], [], []
+        pk["rb"], pk["rbf"], pk["rbw"], pk["rb2"] = [], [], [], []
         for rb in self.resblocks:
             convs = rb.all_convs()
             ch = convs[0].bias.shape[0]
+            if rb.kind == "2" and len(rb.dilation) == 2 and ops.hifi_resblock2_supported(ch, rb.k, *rb.dilation):
+                pk["rb2"].append(([ops.pack_resblock_weight(c.folded_weight(), dtype=dt) for c in convs], [c.bias.data for c in convs]))
+            else:
+                pk["rb2"].append(None)
             if rb.kind == "1" and ops.hifi_resblock1_supported(ch, rb.k):
                 n = len(rb.dilation)
                 order = [convs[m // 2 + (n if m % 2 else 0)] for m in range(2 * n)]          # c1_0, c2_0, c1_1, c2_1, ...
@@ -265,6 +270,19 @@ class Generator(nn.Module):
             xls = nxt
         return xs
 
+    def _upsample_raw(self, al, pk, i):
+        """ConvTranspose1d i (hifi/models.py:189) without an activated copy: the window / looped kernels where `pk["ups8"]` has a pack
+        (fp16: stride 8 from 256 / 512 channels, 128 -> 64 at stride 2), the streaming stride-2 kernel, else the polyphase implicit GEMMs."""
+        wu, bu = pk["ups"][i]
+        u, k, C_out = self.h.upsample_rates[i], self.h.upsample_kernel_sizes[i], wu.shape[1]
+        if pk["ups8"][i] is not None and al.is_contiguous():
+            if self.loop_upsample and ops.hifi_upsample_loop_supported(al.shape[2], C_out, u, k):
+                return ops.hifi_upsample_loop(al, pk["ups8"][i][0], pk["ups8"][i][1], C_out, u)      # 256 -> 128: channel groups looped per frame tile
+            return ops.hifi_upsample_win(al, pk["ups8"][i][0], pk["ups8"][i][1], C_out, u)
+        if self.stream_upsample and ops.hifi_upsample2_supported(wu.shape[2], wu.shape[1], u, k) and al.is_contiguous():
+            return ops.hifi_upsample2(al, wu, bu)
+        return ops.conv_transpose1d(al, wu, bu, u, k)
+
     _stage_marks = None     # bench.py's per-stage timing: a list to which forward appends (name, HIP event) at stage boundaries
 
     def _mark(self, name):
@@ -298,19 +316,24 @@ class Generator(nn.Module):
                 nxt_slope = LRELU_SLOPE if i + 1 < self.num_upsamples else 0.01
                 rbs = [self.resblocks[i * nk + j] for j in range(nk)]
                 C_out = wu.shape[1]
+                if self.resblock2_fused and nk >= 2 and all(pk["rb2"][i * nk + j] is not None for j in range(nk)):
+                    # V3 (ResBlock2): one launch per block on the raw upsampler output, the MRF average and the consumer's LeakyReLU
+                    # folded into the last block's epilogue (modes 0 / 1 / 2): no lrelu copy from the upsampler, no avg3 pass
+                    a = self._upsample_raw(al, pk, i)
+                    self._mark("ups%d" % i)
+                    out = torch.empty_like(a)
+                    for j, rb in enumerate(rbs):
+                        (w0, w1), (b0, b1) = pk["rb2"][i * nk + j]
+                        lastb = j == nk - 1
+                        ops.hifi_resblock2(a, w0, b0, w1, b1, rb.k, rb.dilation, slope=LRELU_SLOPE, out=out, mode=0 if j == 0 else (2 if lastb else 1),
+                                           scale=1.0 / nk, final_slope=nxt_slope if lastb else 1.0)
+                    al = out
+                    continue
                 # C = 32: the fused kernel is as fast or faster for every kernel size (86 / 143 / 181 us against 102 / 139 / 178)
                 want_pair = (self.conv_pair and self.window_conv) if C_out >= 128 else (self.conv_pair_small and self.fused and C_out == 64)
                 ppacks = self._pair_packs(pk, i, nk, rbs, C_out) if want_pair else None
                 if ppacks is not None:
-                    if pk["ups8"][i] is not None and al.is_contiguous():
-                        if self.loop_upsample and ops.hifi_upsample_loop_supported(al.shape[2], C_out, u, k):
-                            a = ops.hifi_upsample_loop(al, pk["ups8"][i][0], pk["ups8"][i][1], C_out, u)      # 256 -> 128: channel groups looped per frame tile
-                        else:
-                            a = ops.hifi_upsample_win(al, pk["ups8"][i][0], pk["ups8"][i][1], C_out, u)
-                    elif self.stream_upsample and ops.hifi_upsample2_supported(wu.shape[2], wu.shape[1], u, k) and al.is_contiguous():
-                        a = ops.hifi_upsample2(al, wu, bu)
-                    else:
-                        a = ops.conv_transpose1d(al, wu, bu, u, k)                         # raw x: the pair kernels activate it themselves
+                    a = self._upsample_raw(al, pk, i)                                        # raw x: the pair kernels activate it themselves
                     # measured per block at the bench shape (tools/debug/convpair_micro.py): three pair launches beat the six-conv
                     # fused kernel at C = 64 for k = 7, 11 (228 vs 242 us, 290 vs 370 us) and lose at k = 3 (158 vs 141 us: the block is
                     # then bound by its HBM passes, and the fused kernel makes one instead of three)

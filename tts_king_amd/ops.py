@@ -1731,6 +1731,31 @@ def hifi_conv_pair(x, w1_pack, bias1, w2_pack, bias2, K, dilation, slope=0.1, ou
     return out
 
 
+def hifi_resblock2_supported(Cn, K, d0, d1):
+    return bool(L.load().ttsk_hifi_resblock2_supported(Cn, K, d0, d1))
+
+
+def hifi_resblock2(x, w0_pack, bias0, w1_pack, bias1, K, dilations, slope=0.1, out=None, mode=0, scale=1.0, final_slope=1.0):
+    """One ResBlock2 (hifi/models.py:134-140) in one launch: x1 = x + b0 + conv_{K,d0}(lrelu(x)), y = x1 + b1 + conv_{K,d1}(lrelu(x1)).
+    x (B, len, C) 16-bit raw block input; packs from pack_resblock_weight.  mode 0: out = y; 1: out += y;
+    2: out = lrelu((out + y) * scale, final_slope) (the MRF average, :190-197; hifi_conv_pair's modes)."""
+    _dev(x, w0_pack, bias0, w1_pack, bias1, out)
+    x = x.contiguous()
+    Bn, ln, Cn = x.shape
+    d0, d1 = (int(d) for d in dilations)
+    if out is None:
+        if mode >= 1:
+            raise L.TtskError("hifi_resblock2: mode %d accumulates into `out`" % mode)
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous():
+        raise L.TtskError("hifi_resblock2: `out` must be a contiguous %s tensor of shape %s" % (x.dtype, tuple(x.shape)))
+    if w0_pack.numel() < Cn * Cn * K or w1_pack.numel() < Cn * Cn * K or bias0.numel() < Cn or bias1.numel() < Cn:
+        raise L.TtskError("hifi_resblock2: weight packs / biases too small for C=%d K=%d" % (Cn, K))
+    check(L.load().ttsk_hifi_resblock2(_ptr(x), _ptr(w0_pack), _ptr(bias0), _ptr(w1_pack), _ptr(bias1), _ptr(out), int(x.dtype == f16), Bn,
+                                       ln, Cn, K, d0, d1, slope, mode, scale, final_slope, _stream()), "ttsk_hifi_resblock2")
+    return out
+
+
 def hifi_conv_window(x, w_pack, bias, K, dilation=1, R=None, out2=None, lrelu_out=False, slope=0.1):
     """out = [lrelu](conv_{K,dil}(x) + bias [+ R]) on the window kernel (C = 128); out2 (optional tensor) = lrelu(out)."""
     _dev(x, w_pack, bias, R, out2)
