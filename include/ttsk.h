@@ -702,6 +702,54 @@ int ttsk_optim_step_packed(float* params, float* grads, float* exp_avg, float* e
                            const ttsk_adam_item* dev_items, int n_items, int n_tiles, const int64_t* dev_gaps, int n_gaps,
                            int64_t gap_floats, void* stream);
 
+/* ------------------------------------------------------------------------------------------- CWT pitch branch
+ * model_config.use_cwt: True.  reference: fs_two/model/modules.py:18-141 (get_pitch_embedding_cwt), :358-385 (CNNflat / CNNscalar),
+ * fs_two/cwt/cwt_utils.py:41-66 (inverse_batch_cwt), fs_two/model/loss.py:65-124.  fp32 arithmetic in a fixed summation order
+ * (no atomics): equal inputs give equal bits in every process.  Nothing here synchronises with the host.
+ *
+ * ttsk_layernorm_head_fwd / _bwd: the pitch predictor's tail with its 11 outputs — ttsk_layernorm_fwd's head mode
+ *   (LayerNorm -> dropout_{p_post, site_post} -> Linear -> PAD mask, same dropout bits at the same (rng, site)) for
+ *   Linear(256 -> 11): head_w [11][256], head_b [11], head_out [rows][11]; D = 256 and n_out = 11 only.  y is the LayerNorm input
+ *   (no residual, no pre-dropout); the backward takes it again as z, gates dz with the ReLU that produced it (z > 0) and writes
+ *   partials [ttsk_layernorm_head_bwd_nblocks(rows)][14 * 256 + 11] = dbias | dgamma | dbeta | dhead_w | dhead_b, the order of the
+ *   flat gradient buffer (ttsk_colsum_finalize sums the blocks).
+ * ttsk_cnnscalar_fwd / _bwd: BOTH CNNscalar heads (pitch_mean, pitch_std) in one launch, one workgroup per utterance:
+ *   two 1x1 convs over the time axis (x [B][L][256] bf16 and cwt [B][L][11] fp32), AdaptiveAvgPool1d(30) over the padded length L
+ *   (bins [floor(i L / 30), ceil((i + 1) L / 30))), LayerNorm(30), ReLU, sum, Linear(30, 1), ReLU -> out [2][B] (mean row, std row).
+ *   params: the two heads' parameter blocks back to back, TTSK_CNNSCALAR_FLOATS floats each, every tensor at a multiple of 8 floats in
+ *   state_dict order: flat_one.net.0.weight [256] @0, .bias @256, net.2.weight [30] @264, net.2.bias @296, flat_two.net.0.weight [11]
+ *   @328, .bias @344, net.2.weight @352, net.2.bias @384, linear.weight [30] @416, linear.bias @448.
+ *   Saved for the backward: pooled [B][4][30] (row = head * 2 + flat), stats [B][4][2] (mean, rstd), pre [B][2]; rowdot [B][4][L] is
+ *   workspace for both directions.  The backward turns dout [2][B] into partials [B][2 * TTSK_CNNSCALAR_FLOATS] (same layout, gaps
+ *   zero), one row per utterance — ttsk_colsum_finalize sums them over B in order.  No input gradients: the reference detaches both
+ *   inputs.
+ * ttsk_cwt_pitch: s[b][l] = sum_{i<10} cwt[b][l][i] * (i + 3.5)^-2.5; per column l over ALL B rows: z = (s - mean) / (std + 1e-12)
+ *   (population std, two passes, B = 1 and all-PAD columns give exactly 0); pitch = z * heads[1][b] + heads[0][b], computed in fp64
+ *   and rounded to fp32 once (1 / std amplifies fp32 rounding of s and of the mean); idx = #{bins < pitch * p_control}
+ *   (ttsk_bucketize's rule).
+ * ttsk_fs2_loss_cwt: runs BEHIND ttsk_fs2_loss on the same stream (which must have been given a pitch term of zero): masked
+ *   11-channel MSE (mean over 11 * sum(src_lens)) and the two [B] MSEs; losses[0] += their sum, losses[2] / [5] / [6] = pitch / mean /
+ *   std terms; dcwt [B][L][11] and dheads [2][B] are gradients of grad_scale * total.
+ */
+#define TTSK_CWT_CHANNELS 11
+#define TTSK_CNNSCALAR_BINS 30
+#define TTSK_CNNSCALAR_FLOATS 456
+int ttsk_layernorm_head_bwd_nblocks(int rows);
+int ttsk_layernorm_head_fwd(const void* y_bf16, const float* gamma, const float* beta, const int64_t* lens, int seg_len, int rows, int D,
+                            int n_out, float eps, float p_post, uint32_t site_post, const uint64_t* rng, const float* head_w,
+                            const float* head_b, float* mean, float* rstd, float* head_out, void* stream);
+int ttsk_layernorm_head_bwd(const float* dhead, const float* head_w, const void* z_bf16, const float* mean, const float* rstd,
+                            const float* gamma, const float* beta, const int64_t* lens, int seg_len, int rows, int D, int n_out,
+                            float p_post, uint32_t site_post, const uint64_t* rng, void* dz_bf16, float* partials, void* stream);
+int ttsk_cnnscalar_fwd(const void* x_bf16, const float* cwt, const float* params, int B, int L, int D, float* rowdot, float* pooled,
+                       float* stats, float* pre, float* out, void* stream);
+int ttsk_cnnscalar_bwd(const float* dout, const void* x_bf16, const float* cwt, const float* params, const float* pooled,
+                       const float* stats, const float* pre, int B, int L, int D, float* rowdot, float* partials, void* stream);
+int ttsk_cwt_pitch(const float* cwt, const float* heads, const float* bins, int n_bins, float p_control, int B, int L, float* pitch,
+                   int32_t* idx, void* stream);
+int ttsk_fs2_loss_cwt(const float* cwt, const float* cwt_target, const float* heads, const float* mean_target, const float* std_target,
+                      const int64_t* src_lens, int B, int L, float grad_scale, float* dcwt, float* dheads, float* losses, void* stream);
+
 /* ------------------------------------------------------------------------------------------- mel extraction
  * SURVEY.md §8 row f-3.  reference: hifi/meldataset.py:49-74 (mel_spectrogram), fs_two/audio/stft.py:57-90
  * (STFT.transform: strided conv with a windowed Fourier basis), :174-193 (TacotronSTFT.mel_spectrogram).

@@ -120,7 +120,14 @@ def main(cfg, max_steps=None):
     engine = TrainEngine(model, optimizer, cfg, Loss, reducer=reducer)
     bucket = None
     if bool(mi.get("bucket_shapes", True)):
-        bucket = (int(mi.get("l_bucket", 8)), int(mi.get("t_bucket", 32)), int(cfg.model_config["max_seq_len"]))
+        # use_cwt: the CNNscalar heads pool over the padded text length and the batch-axis pitch statistics count the PAD rows, both as
+        # the reference's batch has them — texts keep their own longest length there, only the frames are bucketed
+        l_bucket = int(mi.get("l_bucket", 8))
+        if cfg.model_config["use_cwt"] and l_bucket != 1:
+            if rank == 0:
+                print("use_cwt: mi355x.l_bucket %d -> 1 (texts keep their own longest length; one captured graph per (L, frame bucket))" % l_bucket)
+            l_bucket = 1
+        bucket = (l_bucket, int(mi.get("t_bucket", 32)), int(cfg.model_config["max_seq_len"]))
     if rank == 0:
         print("Number of FastSpeech2 Parameters:", get_param_num(model))
         for p in cfg.train_config["path"].values():

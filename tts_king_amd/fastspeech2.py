@@ -49,15 +49,17 @@ class _Bridge(torch.autograd.Function):
     backward, which accumulates into the flat gradient buffer (the `.grad` views of the parameters)."""
 
     @staticmethod
-    def forward(ctx, anchor, model, mel, post, pitch, energy, logd):
+    def forward(ctx, anchor, model, mel, post, pitch, energy, logd, *heads):
+        # `heads` (CWT branch only): the (B, 1) pitch_mean / pitch_std predictions
         ctx.model = model
         ctx.step_ctx = model._ctx
-        return mel.view_as(mel), post.view_as(post), pitch.view_as(pitch), energy.view_as(energy), logd.view_as(logd)
+        return (mel.view_as(mel), post.view_as(post), pitch.view_as(pitch), energy.view_as(energy), logd.view_as(logd)) + \
+            tuple(h.view_as(h) for h in heads)
 
     @staticmethod
-    def backward(ctx, dmel, dpost, dpitch, denergy, dlogd):
-        ctx.model._backward_from_autograd(ctx.step_ctx, dmel, dpost, dpitch, denergy, dlogd)
-        return None, None, None, None, None, None, None
+    def backward(ctx, dmel, dpost, dpitch, denergy, dlogd, *dheads):
+        ctx.model._backward_from_autograd(ctx.step_ctx, dmel, dpost, dpitch, denergy, dlogd, *dheads)
+        return (None,) * (7 + len(dheads))
 
 
 class _Ctx:
@@ -105,8 +107,11 @@ class FastSpeech2(nn.Module):
         if not model_config["multi_speaker"]:
             # reference: fastspeech2.py:72-88 raises NameError on this path; only multi-speaker works there too
             raise NotImplementedError("multi_speaker: False is not a working path in the reference either")
-        if model_config["use_cwt"]:
-            raise NotImplementedError("use_cwt: True (CWT pitch) is out of scope; shipped config sets False")
+        # CWT pitch (modules.py:26-36,104-130): the pitch predictor has 11 outputs and a dropout of its own (0.1 by its constructor call,
+        # whatever variance_predictor.dropout says), the pitch_mean / pitch_std heads compute, the embedding row comes from the
+        # PREDICTED coefficients in training too
+        self.use_cwt = bool(model_config["use_cwt"])
+        self.p_pitch = 0.1
         if n_speakers is None:
             n_speakers = get_speakers_number(preprocess_config)
         if device is None or device == "gpu":
@@ -151,7 +156,8 @@ class FastSpeech2(nn.Module):
         self.fused_ln = True            # fc / w_2 + dropout + residual + LayerNorm + PAD zeroing in one kernel when d = 256
         self._postnet_ends_win = True       # the PostNet's 80 -> 512 / 512 -> 80 convs and their input gradients on the window kernel too (round 5; property below)
         self.dwconv = switches.get("TTSK_DWCONV") != "0"   # w_1's weight gradient on the tap-sharing kernel (csrc/dwconv.hip), the other 256-multiple ones on dwgemm.hip
-        self.group_predictors = True    # training with targets: the three VariancePredictors run as grouped launches
+        self.group_predictors = not self.use_cwt    # training with targets: the three VariancePredictors run as grouped launches (the CWT
+                                                    # branch picks its pitch embedding from the prediction: sequential by construction)
         # The weight-gradient GEMMs of PostNet + decoder (88 % of the step's dW FLOPs) are complete once the decoder's backward is;
         # what follows on the dX path (length regulator, variance adaptor, encoder: ~0.5 ms of 32-128-workgroup kernels) fills a
         # fraction of the chip.  So that group is launched there on a second stream with its grid capped at `dw_side_wgs` workgroups
@@ -200,7 +206,16 @@ class FastSpeech2(nn.Module):
         va = "variance_adaptor."
         o = [self._table[va + n + "_predictor.conv_layer.conv1d_1.conv.weight"].offset for n in ("duration", "pitch", "energy")]
         self._pred_stride = o[1] - o[0]
-        assert o[2] - o[1] == self._pred_stride and self._pred_stride % 8 == 0
+        if self.use_cwt:
+            self._pred_stride = None        # the 11-output pitch predictor is longer than its neighbours: no grouped launches
+            hm = [self._table[va + "pitch_mean." + k].offset for k in
+                  ("flat_one.net.0.weight", "flat_one.net.0.bias", "flat_one.net.2.weight", "flat_one.net.2.bias", "flat_two.net.0.weight",
+                   "flat_two.net.0.bias", "flat_two.net.2.weight", "flat_two.net.2.bias", "linear.weight", "linear.bias")]
+            assert tuple(h - hm[0] for h in hm) == ops.CNNSCALAR_OFFSETS, "CNNscalar block layout (include/ttsk.h)"
+            assert self._table[va + "pitch_std.flat_one.net.0.weight"].offset - hm[0] == ops.CNNSCALAR_FLOATS
+            assert self.d == 256 and model_config["variance_predictor"]["filter_size"] == 256, "the CWT kernels handle 256 channels"
+        else:
+            assert o[2] - o[1] == self._pred_stride and self._pred_stride % 8 == 0
         if self.window_ffn and self._shadow.is_cuda:
             self._build_packs()
 
@@ -501,11 +516,17 @@ class FastSpeech2(nn.Module):
         with torch.no_grad():
             out, ctx = self._forward(train, speakers, texts, src_lens, int(max_src_len), mel_lens, max_mel_len, e_targets,
                                      d_targets, pitches_raw, float(p_control), float(e_control), float(d_control))
-        mel, pitch, energy, logd, d_rounded, src_masks, mel_masks, mel_lens_out, post = out
+        mel, pitch, energy, logd, d_rounded, src_masks, mel_masks, mel_lens_out, post = out[:9]
         self._ctx = ctx
+        pm = ps = None
+        if self.use_cwt:                 # slots 10, 11: the (B, 1) head predictions (fastspeech2.py:117-118)
+            pm, ps = out[9][0].view(-1, 1), out[9][1].view(-1, 1)
         if train and torch.is_grad_enabled():
-            mel, post, pitch, energy, logd = _Bridge.apply(self._anchor, self, mel, post, pitch, energy, logd)
-        return (mel, pitch, energy, logd, d_rounded, src_masks, mel_masks, src_lens, mel_lens_out, post, None, None)
+            if self.use_cwt:
+                mel, post, pitch, energy, logd, pm, ps = _Bridge.apply(self._anchor, self, mel, post, pitch, energy, logd, pm, ps)
+            else:
+                mel, post, pitch, energy, logd = _Bridge.apply(self._anchor, self, mel, post, pitch, energy, logd)
+        return (mel, pitch, energy, logd, d_rounded, src_masks, mel_masks, src_lens, mel_lens_out, post, pm, ps)
 
     def _fft_fwd(self, pre, x, Bn, S, lens, H, p, site, rng, ctx_list, out=None, qkv=None, next_pre=None):
         """One FFTBlock.  reference: Layers.py:25-34, SubLayers.py:31-65 (MHA), :93-101 (FFN), Modules.py:14-24.
@@ -599,12 +620,17 @@ class FastSpeech2(nn.Module):
         a1, _, m1, r1, _ = ops.layernorm_fwd(h1.view(rows, -1), None, self._m(c + "layer_norm_1.weight"), self._m(c + "layer_norm_1.bias"),
                                              None, 0, p_post=p, site_post=site, rng=rng, save_z=False)
         h2 = ops.conv1d(a1.view(Bn, Lp, -1), self._w(c + "conv1d_2.conv.weight"), self._m(c + "conv1d_2.conv.bias"), flags=ops.RELU)
-        _, _, m2, r2, out = ops.layernorm_fwd(h2.view(rows, -1), None, self._m(c + "layer_norm_2.weight"), self._m(c + "layer_norm_2.bias"),
-                                              lens, Lp, p_post=p, site_post=site + 1, rng=rng, save_z=False, want_out=False,
-                                              head=(self._m(pre + "linear_layer.weight").view(-1), self._m(pre + "linear_layer.bias")))
+        hw, hb = self._m(pre + "linear_layer.weight"), self._m(pre + "linear_layer.bias")
+        if hb.numel() > 1:              # the CWT pitch predictor's Linear(256 -> 11): csrc/cwt.hip
+            m2, r2, out = ops.layernorm_head_fwd(h2.view(rows, -1), self._m(c + "layer_norm_2.weight"), self._m(c + "layer_norm_2.bias"),
+                                                 lens, Lp, hw, hb, p_post=p, site_post=site + 1, rng=rng)
+        else:
+            _, _, m2, r2, out = ops.layernorm_fwd(h2.view(rows, -1), None, self._m(c + "layer_norm_2.weight"), self._m(c + "layer_norm_2.bias"),
+                                                  lens, Lp, p_post=p, site_post=site + 1, rng=rng, save_z=False, want_out=False,
+                                                  head=(hw.view(-1), hb))
         if ctx is not None:
             ctx[pre] = (x, h1, m1, r1, a1, h2, m2, r2, Bn, Lp, lens, p, site)
-        return out.view(Bn, Lp)
+        return out.view(Bn, Lp, -1) if hb.numel() > 1 else out.view(Bn, Lp)
 
     def _predictors_fwd_grouped(self, stack, Bn, Lp, lens, p, rng, ctx, row_limit=None):
         """The duration / pitch / energy VariancePredictors (model/modules.py:255-309) as ONE chain of grouped launches: with
@@ -687,12 +713,18 @@ class FastSpeech2(nn.Module):
         batch has there.  `frame_limit` (device int32[1], training only): the batch was padded to a shape bucket (tts_king_amd/engine.py);
         frames t >= frame_limit[0] of every utterance do not exist in the reference's batch — the PostNet's BatchNorm statistics,
         its zero padding and (in the loss) the mel denominators are taken as if the batch ended there."""
+        if self.use_cwt and phoneme_limit is not None:
+            # the CNNscalar heads pool over the padded length as the reference's batch has it (modules.py:360-364): a text axis padded
+            # further would change their result, so the CWT branch takes texts at their own longest length (train.py: l_bucket 1)
+            raise ops.L.TtskError("use_cwt: texts padded to a phoneme bucket are not supported (mi355x.l_bucket must be 1)")
         self.sync_shadow()
         dev, d = self.device, self.d
         Bn = texts.shape[0]
         ctx = _Ctx() if train else None
         rng = ops.rng_of(self._state()) if train else None
         p_enc, p_dec, p_var, p_post = (self.p_enc, self.p_dec, self.p_var, self.p_post) if train else (0.0, 0.0, 0.0, 0.0)
+        p_pitch = (self.p_pitch if train else 0.0) if self.use_cwt else p_var
+        heads = heads_saved = None
         blocks = [] if train else None
         preds = {} if train else None
 
@@ -741,8 +773,10 @@ class FastSpeech2(nn.Module):
         else:
             logd = self._predictor_fwd(va + "duration_predictor.", x, Bn, Lp, src_lens, p_var, 200, rng, preds)
             x1 = ops.gather_add(x, self._m("speaker_emb.weight"), speakers, idx_div=Lp)          # fastspeech2.py:72-75
-            pitch = self._predictor_fwd(va + "pitch_predictor.", x1, Bn, Lp, src_lens, p_var, 202, rng, preds)
-            if pitches_raw is not None:
+            pitch = self._predictor_fwd(va + "pitch_predictor.", x1, Bn, Lp, src_lens, p_pitch, 202, rng, preds)
+            if self.use_cwt:
+                pidx, heads, heads_saved = self._cwt_pitch_rows(x1, pitch, Bn, Lp, p_control)
+            elif pitches_raw is not None:
                 pidx = ops.bucketize(pitches_raw.to(dev).float(), self.get(va + "pitch_bins"))
             else:
                 pidx, pitch = ops.bucketize(pitch, self.get(va + "pitch_bins"), p_control, want_scaled=True)
@@ -843,9 +877,23 @@ class FastSpeech2(nn.Module):
             ctx.dec_out = y
             ctx.frame_limit = fl
             ctx.used = False
+            ctx.heads_saved = heads_saved
         out = (mel.view(Bn, T, self.n_mel), pitch, energy, logd, d_rounded, src_masks, mel_masks, mel_lens_out,
                post.view(Bn, T, self.n_mel))
+        if self.use_cwt:
+            out = out + (heads,)            # (2, B) fp32: pitch_mean row, pitch_std row
         return out, ctx
+
+    def _cwt_pitch_rows(self, x1, pitch_cwt, Bn, Lp, p_control):
+        """get_pitch_embedding_cwt behind the predictor (modules.py:118-129): both CNNscalar heads on (x + speaker, prediction) in one
+        launch, then the coefficients -> pitch -> embedding row.  Returns (rows (B, L) int32, heads (2, B), what the heads' backward
+        needs).  `self._cwt_pitch`: the fp32 pitch of the last call, `self._cwt_head_inputs`: what the heads read in it (the facade and
+        the tests read them)."""
+        va = "variance_adaptor."
+        heads, saved = ops.cnnscalar_fwd(x1, pitch_cwt, self._m(va + "pitch_mean.flat_one.net.0.weight", 2 * ops.CNNSCALAR_FLOATS), Bn, Lp)
+        self._cwt_head_inputs = (x1, pitch_cwt)
+        self._cwt_pitch, pidx = ops.cwt_pitch(pitch_cwt, heads, self.get(va + "pitch_bins"), p_control)
+        return pidx, heads, saved
 
     # ------------------------------------------------------------------ inference in two capturable halves
     def eval_front(self, speakers, texts, src_lens, Lp, p_control=1.0, e_control=1.0, d_control=1.0):
@@ -867,13 +915,19 @@ class FastSpeech2(nn.Module):
         logd = self._predictor_fwd(va + "duration_predictor.", x, Bn, Lp, src_lens, 0.0, 0, None, None)
         x1 = ops.gather_add(x, self._m("speaker_emb.weight"), speakers, idx_div=Lp)
         pitch = self._predictor_fwd(va + "pitch_predictor.", x1, Bn, Lp, src_lens, 0.0, 0, None, None)
-        pidx, pitch = ops.bucketize(pitch, self.get(va + "pitch_bins"), p_control, want_scaled=True)
+        heads = None
+        if self.use_cwt:
+            pidx, heads, _ = self._cwt_pitch_rows(x1, pitch, Bn, Lp, p_control)
+        else:
+            pidx, pitch = ops.bucketize(pitch, self.get(va + "pitch_bins"), p_control, want_scaled=True)
         x2 = ops.gather_add(x1, self._m(va + "pitch_embedding.weight"), pidx.view(-1))
         energy = self._predictor_fwd(va + "energy_predictor.", x2, Bn, Lp, src_lens, 0.0, 0, None, None)
         eidx, energy = ops.bucketize(energy, self.get(va + "energy_bins"), e_control, want_scaled=True)
         x3 = ops.gather_add(x2, self._m(va + "energy_embedding.weight"), eidx.view(-1))
         dur = ops.duration_round(logd, d_control)
         _, _, _, total = ops.length_regulator_fwd(x3.view(Bn, Lp, d), dur, 1, want_idx=False)
+        if self.use_cwt:
+            return x3, dur, total, (pitch, energy, logd, src_masks, heads)     # pitch: the (B, L, 11) prediction; heads (2, B)
         return x3, dur, total, (pitch, energy, logd, src_masks)
 
     def eval_back(self, x3, dur, Lp, T):
@@ -911,7 +965,7 @@ class FastSpeech2(nn.Module):
         return mel.view(Bn, T, self.n_mel), xin.view(Bn, T, self.n_mel), mel_lens, mel_masks
 
     # ------------------------------------------------------------------ backward
-    def _backward_from_autograd(self, ctx, dmel, dpost, dpitch, denergy, dlogd):
+    def _backward_from_autograd(self, ctx, dmel, dpost, dpitch, denergy, dlogd, dpm=None, dps=None):
         dev = self.device
         Bn, Lp, T = ctx.dims
 
@@ -922,7 +976,11 @@ class FastSpeech2(nn.Module):
         dmel, dpost = f32(dmel, (Bn, T, self.n_mel)), f32(dpost, (Bn, T, self.n_mel))
         with torch.no_grad():
             dmel_sum = ops.add_f32(dmel, dpost)
-            self.backward_native(ctx, dmel_sum, dpost, f32(dpitch, (Bn, Lp)), f32(denergy, (Bn, Lp)), f32(dlogd, (Bn, Lp)))
+            dheads = None
+            if self.use_cwt:
+                dheads = torch.stack([f32(dpm, (Bn, 1)).view(-1), f32(dps, (Bn, 1)).view(-1)])      # device copies, no arithmetic
+            self.backward_native(ctx, dmel_sum, dpost, f32(dpitch, (Bn, Lp, ops.CWT_CHANNELS) if self.use_cwt else (Bn, Lp)),
+                                 f32(denergy, (Bn, Lp)), f32(dlogd, (Bn, Lp)), dheads=dheads)
             # one dropout-counter tick per micro-step, as main_train_step / graph.make_enqueue do: Philox masks are a
             # function of (seed, step, site, element), so without it every `loss.backward()` step would reuse one mask
             ops.rng_advance(self._state())
@@ -1053,11 +1111,17 @@ class FastSpeech2(nn.Module):
         d, rows = self.d, Bn * Lp
         c = pre + "conv_layer."
         Fh = h1.shape[-1]
-        hw = self._m(pre + "linear_layer.weight").view(-1)
-        dh2, _, part, nblk = ops.layernorm_bwd(None, h2.view(rows, Fh), m2, r2, self._m(c + "layer_norm_2.weight"),
-                                               self._m(c + "layer_norm_2.bias"), lens, Lp, relu_in=True, p_post=p,
-                                               site_post=site + 1, rng=rng, dhead=dout.contiguous().view(-1), head_w=hw)
-        self._finalize_ln(part, nblk, 4 * Fh + 1, c + "conv1d_2.conv.bias")
+        hw = self._m(pre + "linear_layer.weight")
+        n_out = hw.shape[0]
+        if n_out > 1:                   # the CWT pitch predictor: dout (B, L, 11)
+            dh2, part, nblk = ops.layernorm_head_bwd(dout.contiguous().view(rows, n_out), hw, h2.view(rows, Fh), m2, r2,
+                                                     self._m(c + "layer_norm_2.weight"), self._m(c + "layer_norm_2.bias"), lens, Lp,
+                                                     p_post=p, site_post=site + 1, rng=rng)
+        else:
+            dh2, _, part, nblk = ops.layernorm_bwd(None, h2.view(rows, Fh), m2, r2, self._m(c + "layer_norm_2.weight"),
+                                                   self._m(c + "layer_norm_2.bias"), lens, Lp, relu_in=True, p_post=p,
+                                                   site_post=site + 1, rng=rng, dhead=dout.contiguous().view(-1), head_w=hw.view(-1))
+        self._finalize_ln(part, nblk, (3 + n_out) * Fh + n_out, c + "conv1d_2.conv.bias")
         ops.conv1d_dw(dh2.view(Bn, Lp, Fh), a1.view(Bn, Lp, Fh), self._g(c + "conv1d_2.conv.weight"), k=self.k_var, defer=self._deferred, accumulate=self._acc)
         da1 = ops.conv1d_dx(dh2.view(Bn, Lp, Fh), self._w(c + "conv1d_2.conv.weight"))
         dh1, _, part, nblk = ops.layernorm_bwd(da1.view(rows, Fh), h1.view(rows, Fh), m1, r1, self._m(c + "layer_norm_1.weight"),
@@ -1183,9 +1247,10 @@ class FastSpeech2(nn.Module):
             out[i].copy_(t)               # a device-to-device copy, no arithmetic
         return out
 
-    def backward_native(self, ctx, dmel_sum, dpost, dpitch, denergy, dlogd, on_bucket=None, accumulate=None):
+    def backward_native(self, ctx, dmel_sum, dpost, dpitch, denergy, dlogd, on_bucket=None, accumulate=None, dheads=None):
         """d(loss)/d(params) into the flat gradient buffer.
         dmel_sum = dL/dmel (direct terms) + dL/dpost, dpost = dL/dpost — fp32 (B,T,n_mel); dpitch/denergy/dlogd fp32 (B,L).
+        CWT branch: dpitch is (B,L,11) and `dheads` (2,B) fp32 holds the gradients of the pitch_mean / pitch_std predictions.
         `on_bucket(name)` is called when the gradients of a top-level group are complete (data-parallel overlap).
         `accumulate`: True adds to what the buffer holds (the reference's `.grad +=`, train.py:43-44, micro-steps 2.. of a
         `grad_acc_step` cycle); False OVERWRITES every gradient element (the first micro-step after an update: the buffer need not be
@@ -1300,6 +1365,14 @@ class FastSpeech2(nn.Module):
             dx2 = self._predictor_bwd(va + "energy_predictor.", ctx.preds[va + "energy_predictor."], denergy, rng, dx3.view(Bn, Lp, d))
             ops.scatter_sum(dx2.view(Bn * Lp, d), ctx.pidx.view(-1), self._g(va + "pitch_embedding.weight"), defer=self._deferred_fin, accumulate=self._acc)
             dx1 = self._predictor_bwd(va + "pitch_predictor.", ctx.preds[va + "pitch_predictor."], dpitch, rng, dx2)
+            if self.use_cwt:
+                # the heads read detached inputs (modules.py:118-119): parameter gradients only, from their own loss terms; the twenty
+                # tensors are one stretch of the flat buffer, summed over the utterances in order by the deferred finalize
+                if dheads is None:
+                    raise RuntimeError("use_cwt: backward_native needs dheads (the gradients of the pitch_mean / pitch_std predictions)")
+                hk = va + "pitch_mean.flat_one.net.0.weight"
+                hpart = ops.cnnscalar_bwd(dheads, ctx.heads_saved, self._m(hk, 2 * ops.CNNSCALAR_FLOATS))
+                self._finalize_ln(hpart, Bn, 2 * ops.CNNSCALAR_FLOATS, hk)
             ops.scatter_sum(dx1.view(Bn * Lp, d), ctx.speakers, self._g("speaker_emb.weight"), idx_div=Lp, defer=self._deferred_fin, accumulate=self._acc)
             dxe = self._predictor_bwd(va + "duration_predictor.", ctx.preds[va + "duration_predictor."], dlogd, rng, dx1)
         notify("variance_adaptor")

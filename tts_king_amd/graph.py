@@ -84,7 +84,15 @@ def make_enqueue(model, optimizer, cfg, Loss, step_is_update=True, reducer=None,
             mel, pitch, energy, logd = out[0], out[1], out[2], out[3]
             post = out[8]
             lim = None if frame_limit is None else (frame_limit, 0)
-            if model._pred_fwd_pending:
+            dh = None
+            if getattr(model, "use_cwt", False):
+                # the CWT branch (its predictors run in sequence on this stream): the plain loss with a pitch term of zero, then the
+                # three CWT terms behind it (ops.fs2_loss_cwt); batch[12:15] = pitches_cwt, pitches_mean, pitches_std (fp32, NaN-free:
+                # train_step.to_device)
+                losses, dmel_sum, dpost, dp, de, dd, dh = ops.fs2_loss_cwt(mel, post, batch[6], batch[7], pitch, out[9], energy, logd, batch[12],
+                                                                           batch[13], batch[14], batch[9], batch[10], batch[4], grad_scale=gs,
+                                                                           frame_limit=lim)
+            elif model._pred_fwd_pending:
                 # The predictors ran on a stream of their own and nobody has waited for it yet.  The frame-level half of the loss — all the
                 # PostNet's backward needs — goes out on this stream without that wait; the phoneme-level half and the predictors' backward
                 # follow the predictors on THEIR stream at once (backward_native joins it where the variance adaptor's gradients meet);
@@ -100,10 +108,10 @@ def make_enqueue(model, optimizer, cfg, Loss, step_is_update=True, reducer=None,
                 losses, dmel_sum, dpost, dp, de, dd = ops.fs2_loss(mel, post, batch[6], batch[7], pitch, energy, logd, batch[11],
                                                                    batch[9], batch[10], batch[4], grad_scale=gs, frame_limit=lim)
             if reducer is not None and step_is_update:
-                model.backward_native(ctx, dmel_sum, dpost, dp, de, dd, on_bucket=reducer.on_group_done, accumulate=accumulate)
+                model.backward_native(ctx, dmel_sum, dpost, dp, de, dd, on_bucket=reducer.on_group_done, accumulate=accumulate, dheads=dh)
                 reducer.finish()
             else:
-                model.backward_native(ctx, dmel_sum, dpost, dp, de, dd, accumulate=accumulate)
+                model.backward_native(ctx, dmel_sum, dpost, dp, de, dd, accumulate=accumulate, dheads=dh)
             if step_is_update:
                 # the end-of-step dropout-counter tick rides along; the gradients stay (the next backward overwrites them)
                 optimizer.step_and_update_lr(advance_rng=True, keep_grads=True)

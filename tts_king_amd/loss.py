@@ -31,13 +31,42 @@ class _LossFn(torch.autograd.Function):
         return dmel, dpost, dp, de, dd, None
 
 
+class _LossFnCwt(torch.autograd.Function):
+    """The same for the CWT branch (loss.py:65-124 with use_cwt): the (B, L, 11) prediction and the two (B, 1) heads."""
+
+    @staticmethod
+    def forward(ctx, mel, post, pitch, energy, logd, pm, ps, targets, cwt_targets):
+        heads = torch.stack([pm.detach().reshape(-1), ps.detach().reshape(-1)]).float().contiguous()
+        losses, *_ = ops.fs2_loss_cwt(mel.detach(), post.detach(), *targets[:2], pitch.detach().contiguous(), heads, energy.detach(),
+                                      logd.detach(), *cwt_targets, *targets[3:], grad_scale=1.0)
+        ctx.save_for_backward(mel, post, pitch, energy, logd, pm, ps)
+        ctx.targets, ctx.cwt_targets = targets, cwt_targets
+        return losses
+
+    @staticmethod
+    def backward(ctx, dlosses):
+        mel, post, pitch, energy, logd, pm, ps = ctx.saved_tensors
+        scale = float(dlosses[0])           # host read: compatibility path only
+        heads = torch.stack([pm.detach().reshape(-1), ps.detach().reshape(-1)]).float().contiguous()
+        _, dmel_sum, dpost, dc, de, dd, dh = ops.fs2_loss_cwt(mel.detach(), post.detach(), *ctx.targets[:2], pitch.detach().contiguous(), heads,
+                                                              energy.detach(), logd.detach(), *ctx.cwt_targets, *ctx.targets[3:],
+                                                              grad_scale=scale)
+        dmel = ops.add_f32(dmel_sum, dpost, scale_b=-1.0)
+        return dmel, dpost, dc, de, dd, dh[0].view_as(pm), dh[1].view_as(ps), None, None
+
+
 class FastSpeech2Loss(nn.Module):
     def __init__(self, preprocess_config, model_config):
         super().__init__()
         self.pitch_feature_level = preprocess_config["preprocessing"]["pitch"]["feature"]
         self.energy_feature_level = preprocess_config["preprocessing"]["energy"]["feature"]
-        if model_config["use_cwt"]:
-            raise NotImplementedError("use_cwt: True is out of scope (shipped config: False)")
+        self.use_cwt = bool(model_config["use_cwt"])
+
+    @staticmethod
+    def cwt_targets_of(inputs, device):
+        """(pitches_cwt (B, L, 11), pitches_mean (B,), pitches_std (B,)) of the 15-tuple batch, fp32 on `device` (NaN -> 0 as in to_device)."""
+        f = lambda t: torch.nan_to_num(torch.as_tensor(t).to(device).float(), nan=0.0).contiguous()
+        return (f(inputs[12]), f(inputs[13]), f(inputs[14]))
 
     @staticmethod
     def targets_of(inputs, device):
@@ -52,6 +81,10 @@ class FastSpeech2Loss(nn.Module):
         mel, pitch, energy, logd = predictions[0], predictions[1], predictions[2], predictions[3]
         post = predictions[9]
         targets = self.targets_of(inputs, mel.device)
+        if self.use_cwt:
+            losses = _LossFnCwt.apply(mel, post, pitch, energy, logd, predictions[10], predictions[11], targets,
+                                      self.cwt_targets_of(inputs, mel.device))
+            return (losses[0:1], losses[1], losses[2], losses[3], losses[4], losses[5], losses[6])
         losses = _LossFn.apply(mel, post, pitch, energy, logd, targets)
         zero = torch.zeros(1, dtype=torch.int64, device=mel.device)
         return (losses[0:1], losses[1], losses[2], losses[3], losses[4], zero, zero)

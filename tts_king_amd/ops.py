@@ -1413,6 +1413,98 @@ def fs2_loss_finalize(losses, pending, src_lens):
           "ttsk_fs2_loss_finalize")
 
 
+# ---------------------------------------------------------------------------------------------- CWT pitch branch (csrc/cwt.hip)
+CWT_CHANNELS = 11
+CNNSCALAR_FLOATS = 456      # one CNNscalar's parameter block (include/ttsk.h: TTSK_CNNSCALAR_FLOATS)
+CNNSCALAR_OFFSETS = (0, 256, 264, 296, 328, 344, 352, 384, 416, 448)     # its ten tensors, in state_dict order
+_ZEROS = {}                 # (device, B, L) -> a (B, L) fp32 tensor of zeros nobody writes (fs2_loss_cwt), kept so that a step allocates none
+
+
+def layernorm_head_fwd(y, gamma, beta, lens, seg_len, head_w, head_b, p_post=0.0, site_post=0, rng=None, eps=1e-5):
+    """LayerNorm -> dropout -> Linear(256 -> 11) -> PAD mask (the CWT pitch predictor's tail).  y (rows, 256) bf16, head_w (11, 256),
+    head_b (11,).  Returns (mean, rstd, head_out (rows, 11) fp32)."""
+    _dev(y, gamma, beta, lens, head_w, head_b, rng)
+    rows, D = y.shape
+    n_out = head_b.numel()
+    mean, rstd, ho = _f32(rows, device=y.device), _f32(rows, device=y.device), _f32(rows, n_out, device=y.device)
+    check(L.load().ttsk_layernorm_head_fwd(_ptr(y), _ptr(gamma), _ptr(beta), _ptr(lens), seg_len, rows, D, n_out, eps, p_post, site_post,
+                                           _ptr(rng), _ptr(head_w), _ptr(head_b), _ptr(mean), _ptr(rstd), _ptr(ho), _stream()),
+          "ttsk_layernorm_head_fwd")
+    return mean, rstd, ho
+
+
+def layernorm_head_bwd(dhead, head_w, z, mean, rstd, gamma, beta, lens, seg_len, p_post=0.0, site_post=0, rng=None):
+    """Backward of layernorm_head_fwd.  dhead (rows, 11) fp32.  Returns (dz (rows, 256) bf16 — through the ReLU that produced z —,
+    partials (nblk, 14 * 256 + 11) = dbias | dgamma | dbeta | dhead_w | dhead_b, nblk)."""
+    _dev(dhead, head_w, z, mean, rstd, gamma, beta, lens, rng)
+    rows, D = z.shape
+    n_out = dhead.shape[-1]
+    lib = L.load()
+    nblk = lib.ttsk_layernorm_head_bwd_nblocks(rows)
+    partials = _f32(nblk, (3 + n_out) * D + n_out, device=z.device)
+    dz = torch.empty(rows, D, dtype=bf16, device=z.device)
+    check(lib.ttsk_layernorm_head_bwd(_ptr(dhead), _ptr(head_w), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(lens), seg_len,
+                                      rows, D, n_out, p_post, site_post, _ptr(rng), _ptr(dz), _ptr(partials), _stream()),
+          "ttsk_layernorm_head_bwd")
+    return dz, partials, nblk
+
+
+def cnnscalar_fwd(x, cwt, params, B, Lp):
+    """Both CNNscalar heads in one launch.  x (B * Lp, 256) bf16, cwt (B, Lp, 11) fp32, params: the two heads' parameter blocks
+    (2 * CNNSCALAR_FLOATS fp32).  Returns (heads (2, B) fp32 = pitch_mean row, pitch_std row; saved = what cnnscalar_bwd needs)."""
+    _dev(x, cwt, params)
+    dev = x.device
+    rowdot, pooled = _f32(B, 4, Lp, device=dev), _f32(B, 4, 30, device=dev)
+    stats, pre, out = _f32(B, 4, 2, device=dev), _f32(B, 2, device=dev), _f32(2, B, device=dev)
+    check(L.load().ttsk_cnnscalar_fwd(_ptr(x), _ptr(cwt), _ptr(params), B, Lp, x.shape[-1], _ptr(rowdot), _ptr(pooled), _ptr(stats), _ptr(pre),
+                                      _ptr(out), _stream()), "ttsk_cnnscalar_fwd")
+    return out, (x, cwt, pooled, stats, pre, rowdot, B, Lp)
+
+
+def cnnscalar_bwd(dheads, saved, params):
+    """dheads (2, B) fp32 -> per-utterance partials (B, 2 * CNNSCALAR_FLOATS) of the 20 parameter gradients (sum them over B with
+    colsum_finalize).  No input gradients: the reference detaches both inputs (model/modules.py:118-119)."""
+    x, cwt, pooled, stats, pre, rowdot, B, Lp = saved
+    _dev(dheads)
+    partials = _f32(B, 2 * CNNSCALAR_FLOATS, device=x.device)
+    check(L.load().ttsk_cnnscalar_bwd(_ptr(dheads), _ptr(x), _ptr(cwt), _ptr(params), _ptr(pooled), _ptr(stats), _ptr(pre), B, Lp, x.shape[-1],
+                                      _ptr(rowdot), _ptr(partials), _stream()), "ttsk_cnnscalar_bwd")
+    return partials
+
+
+def cwt_pitch(cwt, heads, bins, p_control=1.0):
+    """inverse_batch_cwt + `* std + mean` + bucketize(pitch * p_control).  cwt (B, L, 11) fp32, heads (2, B).  Returns (pitch (B, L) fp32,
+    idx (B, L) int32)."""
+    _dev(cwt, heads, bins)
+    B, Lp, _ = cwt.shape
+    pitch = _f32(B, Lp, device=cwt.device)
+    idx = torch.empty(B, Lp, dtype=torch.int32, device=cwt.device)
+    check(L.load().ttsk_cwt_pitch(_ptr(cwt), _ptr(heads), _ptr(bins), bins.numel(), p_control, B, Lp, _ptr(pitch), _ptr(idx), _stream()),
+          "ttsk_cwt_pitch")
+    return pitch, idx
+
+
+def fs2_loss_cwt(mel, post, mel_t, mel_lens, cwt, heads, energy, logd, cwt_t, mean_t, std_t, energy_t, dur_t, src_lens, grad_scale=1.0,
+                 frame_limit=None):
+    """The loss of the CWT branch (loss.py:24-134 with use_cwt): ttsk_fs2_loss with a pitch term of exactly zero, then ttsk_fs2_loss_cwt
+    behind it on the same stream.  Returns (losses[8] = {total, mel, pitch, energy, duration, mean_pitch, std_pitch, n_valid}, dmel_sum,
+    dpost, dcwt (B, L, 11), denergy, dlogd, dheads (2, B))."""
+    _dev(cwt, heads, cwt_t, mean_t, std_t)
+    B, Lp, _ = cwt.shape
+    # the (B, L) pitch slot of the plain loss takes zeros as prediction and as target: its term and its gradient are exactly 0
+    zero = _ZEROS.get((cwt.device, B, Lp))
+    if zero is None:
+        zero = torch.zeros(B, Lp, dtype=torch.float32, device=cwt.device)
+        if not torch.cuda.is_current_stream_capturing():       # (memory made inside a capture belongs to that graph: not kept)
+            _ZEROS[(cwt.device, B, Lp)] = zero
+    losses, dmel, dpost, _, de, dd = fs2_loss(mel, post, mel_t, mel_lens, zero, energy, logd, zero, energy_t, dur_t, src_lens,
+                                              grad_scale=grad_scale, frame_limit=frame_limit)
+    dcwt, dheads = torch.empty_like(cwt), _f32(2, B, device=cwt.device)
+    check(L.load().ttsk_fs2_loss_cwt(_ptr(cwt), _ptr(cwt_t), _ptr(heads), _ptr(mean_t), _ptr(std_t), _ptr(src_lens), B, Lp, grad_scale,
+                                     _ptr(dcwt), _ptr(dheads), _ptr(losses), _stream()), "ttsk_fs2_loss_cwt")
+    return losses, dmel, dpost, dcwt, de, dd, dheads
+
+
 def optim_state(device, seed=1234, sched_step=0):
     """Device state block (see include/ttsk.h): int64[8] view; fields set here, advanced by kernels."""
     n = L.load().ttsk_optim_state_bytes() // 8

@@ -51,24 +51,30 @@ def _fft_block(pre, d, d_ff, k1, k2):
     ]
 
 
-def _predictor(pre, d, filt, k):
+def _predictor(pre, d, filt, k, n_out=1):
     c = pre + "conv_layer."
     return [
         Entry(c + "conv1d_1.conv.weight", (filt, d, k), TRAIN, conv=True), Entry(c + "conv1d_1.conv.bias", (filt,), TRAIN),
         Entry(c + "layer_norm_1.weight", (filt,), TRAIN), Entry(c + "layer_norm_1.bias", (filt,), TRAIN),
         Entry(c + "conv1d_2.conv.weight", (filt, filt, k), TRAIN, conv=True), Entry(c + "conv1d_2.conv.bias", (filt,), TRAIN),
         Entry(c + "layer_norm_2.weight", (filt,), TRAIN), Entry(c + "layer_norm_2.bias", (filt,), TRAIN),
-        Entry(pre + "linear_layer.weight", (1, filt), TRAIN), Entry(pre + "linear_layer.bias", (1,), TRAIN),
+        Entry(pre + "linear_layer.weight", (n_out, filt), TRAIN), Entry(pre + "linear_layer.bias", (n_out,), TRAIN),
     ]
 
 
-def _cnn_scalar(pre, size_one, size_two, reduce=30):
-    """CWT pitch mean/std heads (reference: model/modules.py:358-385): parameters exist, compute is off."""
+CWT_CHANNELS = 11      # outputs of the CWT pitch predictor (reference: model/modules.py:27-29)
+
+
+def _cnn_scalar(pre, size_one, size_two, reduce=30, kind=UNUSED):
+    """CWT pitch mean/std heads (reference: model/modules.py:358-385).  `kind`: UNUSED (use_cwt False: the parameters exist, compute
+    is off) or TRAIN (use_cwt True): then the ten tensors of a head sit back to back in the flat buffer, in this order, each at a
+    multiple of 8 floats — the parameter block csrc/cwt.hip reads (include/ttsk.h: ttsk_cnnscalar_fwd).  The 1x1 conv weight
+    (1, size, 1) is stored as it is: with one output channel and one tap the tap-major layout is the same memory."""
     out = []
     for name, size in (("flat_one", size_one), ("flat_two", size_two)):
-        out += [Entry(pre + name + ".net.0.weight", (1, size, 1), UNUSED), Entry(pre + name + ".net.0.bias", (1,), UNUSED),
-                Entry(pre + name + ".net.2.weight", (reduce,), UNUSED), Entry(pre + name + ".net.2.bias", (reduce,), UNUSED)]
-    out += [Entry(pre + "linear.weight", (1, reduce), UNUSED), Entry(pre + "linear.bias", (1,), UNUSED)]
+        out += [Entry(pre + name + ".net.0.weight", (1, size, 1), kind), Entry(pre + name + ".net.0.bias", (1,), kind),
+                Entry(pre + name + ".net.2.weight", (reduce,), kind), Entry(pre + name + ".net.2.bias", (reduce,), kind)]
+    out += [Entry(pre + "linear.weight", (1, reduce), kind), Entry(pre + "linear.bias", (1,), kind)]
     return out
 
 
@@ -88,9 +94,11 @@ def build_entries(model_config, n_mel, n_speakers, n_vocab):
         e += _fft_block("encoder.layer_stack.%d." % i, d, d_ff, k1, k2)
     e.append(Entry("speaker_emb.weight", (n_speakers, d), TRAIN))
     va = "variance_adaptor."
+    cwt = bool(model_config["use_cwt"])
     for name in ("duration_predictor", "pitch_predictor", "energy_predictor"):
-        e += _predictor(va + name + ".", d, vp["filter_size"], vp["kernel_size"])
-    e += _cnn_scalar(va + "pitch_mean.", d, 11) + _cnn_scalar(va + "pitch_std.", d, 11)
+        e += _predictor(va + name + ".", d, vp["filter_size"], vp["kernel_size"], CWT_CHANNELS if (cwt and name == "pitch_predictor") else 1)
+    hk = TRAIN if cwt else UNUSED
+    e += _cnn_scalar(va + "pitch_mean.", d, CWT_CHANNELS, kind=hk) + _cnn_scalar(va + "pitch_std.", d, CWT_CHANNELS, kind=hk)
     e += [Entry(va + "pitch_bins", (n_bins - 1,), FROZEN), Entry(va + "energy_bins", (n_bins - 1,), FROZEN),
           Entry(va + "pitch_embedding.weight", (n_bins, d), TRAIN), Entry(va + "energy_embedding.weight", (n_bins, d), TRAIN),
           Entry("decoder.position_enc", (1, n_pos, d), FROZEN)]

@@ -83,21 +83,30 @@ def main_train_step(model, batch, step, optimizer, cfg, Loss, reducer=None):
         out, ctx = model._forward(True, batch[2].to(dev).long().contiguous(), batch[3].to(dev).long().contiguous(),
                                   batch[4].to(dev).long().contiguous(), int(batch[5]), batch[7], batch[8], batch[9], batch[10],
                                   batch[11], 1.0, 1.0, 1.0)
-        mel, pitch, energy, logd, d_rounded, src_masks, mel_masks, mel_lens_out, post = out
+        mel, pitch, energy, logd, d_rounded, src_masks, mel_masks, mel_lens_out, post = out[:9]
         targets = Loss.targets_of(batch, dev)
-        losses, dmel_sum, dpost, dp, de, dd = ops.fs2_loss(mel, post, targets[0], targets[1], pitch, energy, logd, targets[2],
-                                                           targets[3], targets[4], targets[5], grad_scale=1.0 / grad_acc_step)
+        dh = heads = None
+        if model.use_cwt:
+            heads = out[9]
+            cwt_t, mean_t, std_t = Loss.cwt_targets_of(batch, dev)
+            losses, dmel_sum, dpost, dp, de, dd, dh = ops.fs2_loss_cwt(mel, post, targets[0], targets[1], pitch, heads, energy, logd, cwt_t,
+                                                                       mean_t, std_t, targets[3], targets[4], targets[5],
+                                                                       grad_scale=1.0 / grad_acc_step)
+        else:
+            losses, dmel_sum, dpost, dp, de, dd = ops.fs2_loss(mel, post, targets[0], targets[1], pitch, energy, logd, targets[2],
+                                                               targets[3], targets[4], targets[5], grad_scale=1.0 / grad_acc_step)
         do_step = step % grad_acc_step == 0
         if reducer is not None and do_step:
-            model.backward_native(ctx, dmel_sum, dpost, dp, de, dd, on_bucket=reducer.on_group_done)
+            model.backward_native(ctx, dmel_sum, dpost, dp, de, dd, on_bucket=reducer.on_group_done, dheads=dh)
             reducer.finish()
         else:
-            model.backward_native(ctx, dmel_sum, dpost, dp, de, dd)
+            model.backward_native(ctx, dmel_sum, dpost, dp, de, dd, dheads=dh)
         if do_step:
             optimizer.step_and_update_lr(advance_rng=True)          # the end-of-step dropout-counter tick rides along
             optimizer.zero_grad()
         else:
             ops.rng_advance(model._state())
-    output = (mel, pitch, energy, logd, d_rounded, src_masks, mel_masks, batch[4], mel_lens_out, post, None, None)
+    pm, ps = (heads[0].view(-1, 1), heads[1].view(-1, 1)) if heads is not None else (None, None)
+    output = (mel, pitch, energy, logd, d_rounded, src_masks, mel_masks, batch[4], mel_lens_out, post, pm, ps)
     vals = losses.cpu().tolist()                       # the step's only host read (reference: 6x .item(), train.py:45)
     return [v / grad_acc_step for v in vals[1:7]], output
