@@ -69,3 +69,24 @@ class HIFIapi:
             audio = ops.to_int16(audio, float(self.cfg.hifi.MAX_WAV_VALUE))     # scale + truncate toward zero on device
             audio = ops.to_host(audio).numpy()                                     # D2H through a pinned staging buffer
         return audio
+
+    def generate_ragged(self, mels, frames_first=False):
+        """mels: a list of (80, T_i) or (1, 80, T_i) mels of any lengths (`frames_first`: FastSpeech2's (T_i, 80) / (1, T_i, 80) rows) ->
+        a list of int16 ndarrays (1, 1, 256 T_i) on the host, each the truncation of what the generator gives for that mel alone.
+        Utterances of at least `tts_king_amd.windows.W` frames run together as fixed-size windows (`Generator.forward_ragged`; with
+        `hip_graph` one replayed graph per window count) and come back in ONE device-to-host copy; shorter ones go through the
+        generator one by one."""
+        from tts_king_amd import windows
+        self.model.eval()
+        scale = float(self.cfg.hifi.MAX_WAV_VALUE)
+        mels = list(mels)
+        with torch.no_grad():
+            if self._synth is not None:
+                flat, plan, spf = self._synth.wav_ragged_flat(mels, frames_first, scale)
+                short = self.model.forward_short(mels, plan, frames_first, scale, forward=self._synth.wav)
+            else:
+                flat, plan, spf = self.model.forward_ragged_flat(mels, frames_first, scale)
+                short = self.model.forward_short(mels, plan, frames_first, scale)
+            host = None if flat is None else ops.to_host(flat).numpy()              # one D2H copy; its shape repeats with N
+            short = {i: ops.to_host(y).numpy() for i, y in short.items()}
+        return windows.split(host, plan, spf, short)

@@ -447,6 +447,25 @@ int ttsk_nct_to_ntc(const float* src, void* dst16, int f16, int B, int C, int T,
 /* (x * scale) truncated toward zero to int16 — reference: hifiapi.py:50-51 */
 int ttsk_to_int16(const float* src, int16_t* dst, int64_t n, float scale, void* stream);
 
+/* ------------------------------------------------------------------------------------ windowed vocoding
+ * Utterances of any length as N fixed-size windows of W mel frames (tts_king_amd/windows.py plans them on the host).  Both
+ * kernels are driven by the device-resident plan table, TTSK_WIN_ROW int32 per window:
+ *   [0] utterance   [1] start frame of the window in its utterance   [2],[3] kept frames [lo, hi) of the utterance
+ *   [4] frame of the flat output where frame lo goes   [5] frame of the mel staging buffer where the window starts,
+ *   -1 = padding window (reads zeros, keeps nothing)   [6],[7] zero
+ * so lengths are data and a captured graph holds for every call with the same N.
+ * mel_windows: mel staging (fp32; frame f, channel c at src[f * stride_t + c * stride_c]: (C, frames) rows with stride_t = 1, or
+ *              FastSpeech2's (frames, C) rows with stride_c = 1) -> (N, W, C) bf16 / fp16 channels-last, what ttsk_nct_to_ntc
+ *              writes for a (N, C, W) batch.  W a multiple of 32, C a multiple of 8, n_src_frames = frames the staging holds.
+ * wav_stitch:  (N, spf * W) fp32 window waveforms (spf samples per frame, a multiple of 8) -> the kept samples of every window at
+ *              dst[plan[4] * spf ...]; to_i16 = 0: fp32, 1: int16 = (x * scale) truncated toward zero (ttsk_to_int16's arithmetic).
+ *              n_dst_frames = frames the destination holds. */
+#define TTSK_WIN_ROW 8
+int ttsk_mel_windows(const float* src, int64_t stride_t, int64_t stride_c, int64_t n_src_frames, const int32_t* plan, void* dst16,
+                     int f16, int N, int W, int C, void* stream);
+int ttsk_wav_stitch(const float* src, const int32_t* plan, void* dst, int64_t n_dst_frames, int to_i16, float scale, int N, int W,
+                    int spf, void* stream);
+
 /* ------------------------------------------------------------------------------------ HiFi-GAN generator
  * reference: hifi/models.py:146-210 (Generator), :12-95 (ResBlock1), hifi/vocoder/utils.py:24-37.
  * 16-bit tensors of this family are bf16 (f16 = 0) or IEEE fp16 (f16 = 1; what hifigan.py uses: the generator is

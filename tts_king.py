@@ -28,7 +28,11 @@ class TTSKing:
         return self.tts.generate(phonemes, duration_control, pitch_control, energy_control, speaker_name=speaker)
 
     def mel_to_wav(self, mel_spec):
-        """(1, T, 80) mel -> int16 ndarray (1, 1, 256 T).  reference: tts_king.py:47-49."""
+        """(1, T, 80) mel -> int16 ndarray (1, 1, 256 T).  reference: tts_king.py:47-49.
+        A list of (1, T_i, 80) mels of any lengths -> a list of such arrays, vocoded together as fixed-size windows
+        (`HIFIapi.generate_ragged`); a one-element list is how a single long utterance gets onto the bounded graph set."""
+        if isinstance(mel_spec, (list, tuple)):
+            return self.vocoder.generate_ragged(mel_spec, frames_first=True)
         return self.vocoder.generate(mel_spec.transpose(1, 2))
 
     def speak(self, text, duration_control=1.0, pitch_control=1.0, energy_control=1.0, speaker=0):

@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from . import ops
 from . import switches
+from . import windows
 from .ops import bf16, f16
 
 LRELU_SLOPE = 0.1          # reference: hifi/models.py:9
@@ -299,11 +300,18 @@ class Generator(nn.Module):
         if not x.is_cuda:
             raise ops.L.TtskError("HiFi-GAN Generator.forward needs a HIP device tensor (gpu: 'cuda:0'); there is no CPU path")
         pk = self._prepare()
-        h = self.h
-        nk = self.num_kernels
         with torch.no_grad():
             self._mark("start")
             a0 = ops.nct_to_ntc(x.float(), self.act_dtype)                                 # (B, T, 80) 16-bit
+            return self.forward_ntc(a0, pk)
+
+    def forward_ntc(self, a0, pk=None):
+        """`forward` from the channels-last 16-bit mel on: a0 (B, T, 80) in `act_dtype`, what `ops.nct_to_ntc` and `ops.mel_windows` write."""
+        if pk is None:
+            pk = self._prepare()
+        h = self.h
+        nk = self.num_kernels
+        with torch.no_grad():
             if pk["pre_win"] is not None:
                 al = ops.hifi_conv_pre_win(a0, pk["pre_win"], pk["pre"][1], pk["pre"][0].shape[0], pk["pre"][0].shape[1], LRELU_SLOPE)   # window kernel
             else:
@@ -390,3 +398,82 @@ class Generator(nn.Module):
             y = torch.empty(Bn * Tout, 1, dtype=torch.float32, device=al.device)
             ops.conv1d(al, wp, bp, out=y.view(Bn, Tout, 1), flags=ops.TANH)
         return y.view(Bn, 1, Tout)
+
+    # ------------------------------------------------------------------ ragged batches, any length
+    def halo(self):
+        return windows.receptive_halo(self.h)
+
+    def samples_per_frame(self):
+        n = 1
+        for u in self.h.upsample_rates:
+            n *= int(u)
+        return n
+
+    def stage_mels(self, mels, plan, frames_first, stage=None):
+        """The planned utterances back to back in the fp32 staging buffer the gather reads (N * W frames): (80, frames) rows, or,
+        `frames_first`, (frames, 80) rows.  One copy per utterance (host or device source); frames past the call's own stay as they are,
+        no window reads them."""
+        frames = plan.N * plan.W
+        dev = self.conv_pre.bias.device
+        if stage is None:
+            stage = torch.empty(frames * 80, dtype=torch.float32, device=dev)
+        v = stage.view(frames, 80) if frames_first else stage.view(80, frames)
+        for i in plan.planned:
+            o, T = plan.offsets[i], plan.lens[i]
+            (v[o:o + T] if frames_first else v[:, o:o + T]).copy_(mels[i], non_blocking=True)
+        return stage
+
+    def forward_windows(self, stage, table, frames_first=False, int16_scale=None):
+        """Gather -> generator -> stitch on device-resident inputs (capturable: nothing here depends on a length): the staging buffer
+        and the plan table (N, 8) int32 -> one flat buffer of N * W * 256 samples, the kept samples of every utterance back to back."""
+        with torch.no_grad():
+            a0 = ops.mel_windows(stage, table, windows.W, self.act_dtype, frames_first)
+            y = self.forward_ntc(a0)
+            return ops.wav_stitch(y, table, windows.W, int16_scale=int16_scale)
+
+    @staticmethod
+    def ragged_mels(mels, frames_first=False):
+        """The call's mels as 2-D tensors ((80, T_i), or (T_i, 80) when `frames_first`; a leading batch dimension of 1 is dropped) and their lengths."""
+        out = []
+        for m in mels:
+            if m.dim() == 3 and m.shape[0] == 1:
+                m = m[0]
+            if m.dim() != 2 or m.shape[1 if frames_first else 0] != 80:
+                raise ops.L.TtskError("ragged vocoding takes mels of shape %s, got %s" % ("(T, 80)" if frames_first else "(80, T)", tuple(m.shape)))
+            out.append(m)
+        return out, [int(m.shape[0 if frames_first else 1]) for m in out]
+
+    def forward_ragged_flat(self, mels, frames_first=False, int16_scale=None):
+        """The windowed part of `forward_ragged`: (flat buffer of the planned utterances' samples, back to back, or None when no
+        utterance fills a window; the plan; samples per frame).  `int16_scale`: the buffer is int16, truncation of waveform * scale."""
+        mels, lens = self.ragged_mels(mels, frames_first)
+        dev = self.conv_pre.bias.device
+        if dev.type != "cuda":
+            raise ops.L.TtskError("HiFi-GAN ragged vocoding needs the generator's weights on a HIP device; there is no CPU path")
+        plan = windows.plan_windows(lens, windows.W, self.halo())
+        if not plan.planned:
+            return None, plan, self.samples_per_frame()
+        stage = self.stage_mels(mels, plan, frames_first)
+        table = torch.from_numpy(plan.table).to(dev)
+        return self.forward_windows(stage, table, frames_first, int16_scale), plan, self.samples_per_frame()
+
+    def forward_short(self, mels, plan, frames_first=False, int16_scale=None, forward=None):
+        """The utterances too short for a window, each through `forward` (or the caller's `forward`) on its own: {index: waveform}."""
+        mels, _ = self.ragged_mels(mels, frames_first)
+        out = {}
+        for i in plan.short:
+            m = mels[i].to(self.conv_pre.bias.device).float()
+            y = (forward or self.forward)((m.t() if frames_first else m).unsqueeze(0))
+            out[i] = y if int16_scale is None else ops.to_int16(y, float(int16_scale))
+        return out
+
+    def forward_ragged(self, mels, frames_first=False):
+        """mels: a list of (80, T_i) or (1, 80, T_i) tensors of any lengths (`frames_first`: (T_i, 80) / (1, T_i, 80), FastSpeech2's
+        layout) -> a list of (1, 1, 256 T_i) fp32 waveforms, each what `forward` gives for that mel alone (tts_king_amd/windows.py).
+
+        Utterances of at least `windows.W` frames run together as fixed-size windows: one gather launch, the generator on
+        (N, W, 80), one stitch launch.  An utterance shorter than a window cannot be windowed (a padded mel is not a solo run) and
+        goes through `forward` on its own, one utterance per call."""
+        mels = list(mels)
+        flat, plan, spf = self.forward_ragged_flat(mels, frames_first)
+        return windows.split(flat, plan, spf, self.forward_short(mels, plan, frames_first))

@@ -1221,6 +1221,37 @@ def to_int16(x, scale):
     return out
 
 
+def mel_windows(stage, plan, W, dtype=f16, frames_first=False, C=80):
+    """The windows of a call, gathered from the mel staging buffer by the device-resident plan (tts_king_amd/windows.py): `stage` fp32,
+    contiguous, holding the utterances back to back as (C, frames) rows (the reference's mel layout) or, `frames_first`, as FastSpeech2's
+    (frames, C) rows -> (N, W, C) 16-bit channels-last, bit for bit `nct_to_ntc` of the sliced windows.  Padding windows read zeros."""
+    _dev(stage, plan)
+    if stage.dtype != torch.float32 or not stage.is_contiguous() or plan.dtype != torch.int32 or not plan.is_contiguous():
+        raise L.TtskError("mel_windows: needs a contiguous fp32 staging buffer and a contiguous int32 plan")
+    N, frames = plan.shape[0], stage.numel() // C
+    out = torch.empty(N, W, C, dtype=dtype, device=stage.device)
+    st, sc = (C, 1) if frames_first else (1, frames)
+    check(L.load().ttsk_mel_windows(_ptr(stage), st, sc, frames, _ptr(plan), _ptr(out), int(dtype == f16), N, W, C, _stream()), "ttsk_mel_windows")
+    return out
+
+
+def wav_stitch(y, plan, W, out=None, int16_scale=None):
+    """y (N, 1, spf * W) fp32 window waveforms -> the kept samples of every window, utterances back to back, in one flat buffer of
+    N * W * spf samples (what the plan can fill at most; the tail past the call's frames is not written): fp32, or int16 with
+    `to_int16`'s arithmetic when `int16_scale` is given."""
+    _dev(y, plan)
+    N = plan.shape[0]
+    spf = y.shape[-1] // W
+    if y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != N * W * spf or plan.dtype != torch.int32 or not plan.is_contiguous():
+        raise L.TtskError("wav_stitch: needs contiguous fp32 (N, 1, spf * W) window waveforms and a contiguous int32 plan of N rows")
+    i16 = int16_scale is not None
+    if out is None:
+        out = torch.empty(N * W * spf, dtype=torch.int16 if i16 else torch.float32, device=y.device)
+    check(L.load().ttsk_wav_stitch(_ptr(y), _ptr(plan), _ptr(out), out.numel() // spf, int(i16), float(int16_scale or 0.0), N, W, spf, _stream()),
+          "ttsk_wav_stitch")
+    return out
+
+
 _PINNED = {}
 _PINNED_LOCK = threading.Lock()
 
