@@ -39,19 +39,15 @@ class FSTWOapi:
         self.restore_step = 0
         mi = config.get("mi355x", {}) if hasattr(config, "get") else {}
         self._synth = None
+        self._buckets = dict(l_bucket=int(mi.get("l_bucket", 8)), t_bucket=int(mi.get("t_bucket", 32))) if mi else {}
+        self._batch_synth = None         # `generate_batch` without hip_graph: the same kernels, launched plainly (built on first use)
         if mi and mi.get("hip_graph", False) and str(device).startswith("cuda"):
             from tts_king_amd.synth import GraphedSynthesizer
-            self._synth = GraphedSynthesizer(self.model)
+            self._synth = GraphedSynthesizer(self.model, **self._buckets)
 
     def generate(self, phonemes, duration_control=1.0, pitch_control=1.0, energy_control=1.0, speaker_name=None):
         """phonemes: int ndarray (1, L) -> postnet mel (1, T, 80) fp32 on the device.  reference: fsapi.py:38-82."""
-        if speaker_name is not None:
-            if speaker_name not in self.speakers_dict:
-                raise Exception(f"Speaker {speaker_name} was not found in speakers.json")
-            speaker_id = self.speakers_dict[speaker_name]
-        else:
-            speaker_id = 0          # the reference leaves `speaker` unbound here (NameError); default to the first speaker
-        speaker = torch.tensor(speaker_id).long().unsqueeze(0).to(self.device)
+        speaker = torch.tensor(self._speaker_id(speaker_name)).long().unsqueeze(0).to(self.device)
         self.model.eval()
         phonemes = np.asarray(phonemes)
         if self._synth is not None:      # hipGraph-replayed path (tts_king_amd/synth.py): same kernels, no launch overhead
@@ -63,6 +59,33 @@ class FSTWOapi:
                             max(src_len), d_control=duration_control, p_control=pitch_control, e_control=energy_control)
         postnet_output = result[9]
         return postnet_output
+
+    def _speaker_id(self, speaker_name):
+        if speaker_name is None:
+            return 0          # the reference leaves `speaker` unbound here (NameError); default to the first speaker
+        if speaker_name not in self.speakers_dict:
+            raise Exception(f"Speaker {speaker_name} was not found in speakers.json")
+        return self.speakers_dict[speaker_name]
+
+    def generate_batch(self, phonemes_list, duration_control=1.0, pitch_control=1.0, energy_control=1.0, speaker_names=None, aux=False):
+        """phonemes_list: a list of int arrays (L_i,) or (1, L_i) of any lengths -> a list of postnet mels (1, T_i, 80) fp32 on the
+        device, each what `generate` gives for that text alone (NOT what the reference's padded batch gives: there an utterance's last
+        phoneme and length depend on what it is batched with).  Each control is a scalar or one value per
+        utterance, `speaker_names` a name or a list of names.  With `hip_graph` the call replays two graphs keyed by shape buckets;
+        without it the same kernels are launched plainly.  `aux`: also the per-utterance predictions (`GraphedSynthesizer.mel_ragged`)."""
+        from tts_king_amd import batching
+        texts = batching.as_id_rows(phonemes_list)
+        names = batching.per_utterance_names(speaker_names, len(texts), "speaker_names")
+        speakers = [self._speaker_id(n) for n in names]
+        synth = self._synth
+        if synth is None:
+            if self._batch_synth is None:
+                from tts_king_amd.synth import GraphedSynthesizer
+                self._batch_synth = GraphedSynthesizer(self.model, graphs=False, **self._buckets)
+            synth = self._batch_synth
+        out = synth.mel_ragged(speakers, texts, pitch_control, energy_control, duration_control, aux=aux)
+        mels = [mel.unsqueeze(0) for mel in out[0]]
+        return (mels, out[2]) if aux else mels
 
 
 def load_speakers_json(dir_path):

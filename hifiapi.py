@@ -70,6 +70,15 @@ class HIFIapi:
             audio = ops.to_host(audio).numpy()                                     # D2H through a pinned staging buffer
         return audio
 
+    def call_ragged(self, mels, frames_first=False):
+        """The ragged counterpart of `__call__`: a list of mels of any lengths (layouts as in `generate_ragged`) -> a list of float
+        waveforms (1, 1, 256 T_i) on the device, through the same windowed route; device mels are not taken to the host."""
+        self.model.eval()
+        with torch.no_grad():
+            if self._synth is not None:
+                return self._synth.wav_ragged(mels, frames_first)
+            return self.model.forward_ragged(mels, frames_first)
+
     def generate_ragged(self, mels, frames_first=False):
         """mels: a list of (80, T_i) or (1, 80, T_i) mels of any lengths (`frames_first`: FastSpeech2's (T_i, 80) / (1, T_i, 80) rows) ->
         a list of int16 ndarrays (1, 1, 256 T_i) on the host, each the truncation of what the generator gives for that mel alone.

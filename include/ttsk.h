@@ -432,6 +432,21 @@ int ttsk_gather_add(const void* in_bf16, const float* table, const void* idx, in
                     int pe_mod, void* out_bf16, int rows, int D, void* stream);
 int ttsk_scatter_sum(const void* dx_bf16, const void* idx, int idx_is_i64, int idx_div, int n_idx, float* dtable,
                      int n_table_rows, int D, int skip_row, int accumulate, void* stream);
+/* ---- batched synthesis: per-utterance limits and controls (tts_king_amd/synth.py `mel_ragged`)
+ * Rows are (utterance, position) pairs, row = u*seg_len + l.  Positions l >= lens[u] (int64 [rows / seg_len], clamped to
+ * [0, seg_len] in the kernel) exist only because the call padded its texts to a shape bucket: they are written as zero rows, the
+ * zero padding the predictors' convolutions (model/modules.py:255-309) meet when utterance u runs alone.
+ * gather_add_lens: out[row] = in[row] + table[idx[row / seg_len]] (the speaker add, fastspeech2.py:72-75), idx int64.
+ * embed_step: the free-running embedding step (modules.py:92-101,131-140 without targets) in one launch --
+ *   scaled[row] = pred[row] * control[row / seg_len]; idx[row] = #{bins < scaled[row]}; x_out[row] = x[row] + table[idx[row]].
+ *   Search, NaN rule and sums are ttsk_bucketize's and ttsk_gather_add's: a control array filled with one value gives their bits.
+ * duration_round_dev: ttsk_duration_round with d_control[i / L] read from a device fp32 array. */
+int ttsk_gather_add_lens(const void* in_bf16, const float* table, const int64_t* idx, const int64_t* lens, int seg_len,
+                         void* out_bf16, int rows, int D, void* stream);
+int ttsk_embed_step(const float* pred, const float* control, const float* bins, int n_bins, const float* table,
+                    const void* x_bf16, const int64_t* lens, int seg_len, void* x_out_bf16, float* scaled_out,
+                    int32_t* idx_out, int rows, int D, void* stream);
+int ttsk_duration_round_dev(const float* logd, const float* d_control, int L, float* out, int n, void* stream);
 /* the same for up to 8 independent tables per launch (all embedding-table gradients of a backward pass) */
 typedef struct ttsk_scatter_item {
   const void* dx;      /* (n_idx * idx_div, D) bf16 */
@@ -556,6 +571,9 @@ int ttsk_hifi_mrf32_post(const void* x16, float* out, void* stage_out16, int f16
  * frames / mel gradients past the batch's own longest utterance under shape-bucketed training (see BatchNorm below). */
 int ttsk_zero_frames_from(void* x, int elem_bytes, int rows, int C, int seg_len, const int32_t* frame_limit, void* stream);
 
+/* the per-utterance form (batched synthesis): rows (u, t) with t >= lens[u] (int64, clamped to [0, seg_len]) are set to zero. */
+int ttsk_zero_frames_lens(void* x, int elem_bytes, int rows, int C, int seg_len, const int64_t* lens, void* stream);
+
 /* ------------------------------------------------------------------------------------- PostNet BatchNorm1d
  * reference: fs_two/transformer/Layers.py:133-143 — training statistics over ALL rows (PAD rows included),
  * eps 1e-5, momentum 0.1, running_var updated with the unbiased variance; tanh (all but the last layer) and
@@ -602,6 +620,12 @@ int ttsk_bn_bwd_apply_slab(const void* dout, int dout_is_f32, const void* x, int
 int ttsk_bn_apply(const void* x, int x_is_f32, const float* mean, const float* rstd, const float* gamma, const float* beta, int rows,
                   int C, int use_tanh, float p, uint32_t site, const uint64_t* rng, const float* resid_f32, void* out_bf16,
                   float* out_f32, const int32_t* frame_limit, int seg_len, void* stream);
+/* inference BatchNorm-apply of the batched synthesis: ttsk_bn_apply's arithmetic without dropout; frames t >= lens[u] (int64
+ * [rows / seg_len], clamped to [0, seg_len]) come out as zero rows, so the next PostNet convolution meets the zero padding a
+ * solo run of utterance u has past its last frame (Layers.py:133-143). */
+int ttsk_bn_apply_lens(const void* x, int x_is_f32, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                       int rows, int C, int use_tanh, const float* resid_f32, void* out_bf16, float* out_f32, const int64_t* lens,
+                       int seg_len, void* stream);
 int ttsk_bn_bwd_stats(const void* dout, int dout_is_f32, const void* x, int x_is_f32, const float* mean, const float* rstd,
                       const float* gamma, const float* beta, int rows, int C, int use_tanh, float p, uint32_t site,
                       const uint64_t* rng, float* partials /* [nblocks][2C]: sum dy | sum dy*xhat */, const int32_t* frame_limit,

@@ -22,6 +22,14 @@ class TTSKing:
         self.speakers = self.tts.speaker_names
 
     def generate_mel(self, text, duration_control=1.0, pitch_control=1.0, energy_control=1.0, speaker=0):
+        """One text -> (1, T, 80) mel (reference: tts_king.py:25-45).  A list of texts -> a list of such mels, run together
+        (`FSTWOapi.generate_batch`): each is what its text gives alone; `speaker` and the controls may then be lists, one per text."""
+        if isinstance(text, (list, tuple)):
+            from tts_king_amd import batching
+            phonemes = [t if isinstance(t, np.ndarray) else self.text_preprocess(t) for t in text]
+            names = [self.speakers[s] if isinstance(s, (int, np.integer)) else s
+                     for s in batching.per_utterance_names(speaker, len(phonemes), "speaker")]
+            return self.tts.generate_batch(phonemes, duration_control, pitch_control, energy_control, speaker_names=names)
         phonemes = text if isinstance(text, np.ndarray) else self.text_preprocess(text)
         if isinstance(speaker, int):
             speaker = self.speakers[speaker]
@@ -36,7 +44,11 @@ class TTSKing:
         return self.vocoder.generate(mel_spec.transpose(1, 2))
 
     def speak(self, text, duration_control=1.0, pitch_control=1.0, energy_control=1.0, speaker=0):
-        """reference: tts_king.py:51-57 calls a missing `generate_mel_batch`; here: mel -> float waveform."""
+        """reference: tts_king.py:51-57 calls a missing `generate_mel_batch`; here: mel -> float waveform.  A list of texts -> a list
+        of float waveforms (1, 1, 256 T_i) on the device: the batched mels go straight into the vocoder's ragged route."""
+        if isinstance(text, (list, tuple)):
+            mels = self.generate_mel(text, duration_control, pitch_control, energy_control, speaker)
+            return self.vocoder.call_ragged(mels, frames_first=True)
         mel = self.generate_mel(text, duration_control, pitch_control, energy_control, speaker)
         return self.vocoder(mel.transpose(1, 2))
 

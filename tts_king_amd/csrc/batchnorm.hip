@@ -28,6 +28,9 @@ struct BnCommon {
   // forward writes them and the slab backward kernels read them: Philox costs 40 quarter-rate integer multiplies per quad, and
   // regenerating the mask twice in the backward made those kernels VALU-bound.
   uint8_t* keep;
+  // Per-utterance frame limit of the batched synthesis (bn_apply only): frames t >= lens[u], clamped to [0, seg_len], are written
+  // as zero rows -- the next convolution's zero padding in a solo run of utterance u.  null = none.
+  const long long* lens;
 };
 // tanh = 1 - 2 / (exp(2x) + 1) on the hardware exp and reciprocal: absolute error ~1e-7 (the result is stored as bf16, or multiplies
 // a bf16 gradient); libm's tanhf is ~4x the instructions, and these kernels are VALU-bound
@@ -141,6 +144,7 @@ __global__ __launch_bounds__(256) void rsqrt_eps_kernel(const float* __restrict_
 }
 
 // ---- pass 2: y = tanh?(gamma * xhat + beta) -> dropout -> (+ residual) -> out
+template <bool LENS>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const BnCommon a, const float* __restrict__ resid, bf16_t* __restrict__ out16,
                                                        float* __restrict__ out32) {
   const int tpr = a.C >> 2;
@@ -149,7 +153,13 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const BnCommon a, const f
   const float scale = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
   for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const int r = (int)(i / tpr), c4 = (int)(i - (int64_t)r * tpr) * 4;
-    if (!bn_live(a.frame_limit, a.seg_len, r)) {     // a frame past the batch's own length: a zero row (the next conv's padding)
+    bool live = bn_live(a.frame_limit, a.seg_len, r);
+    if (LENS) {
+      const int u = r / a.seg_len;
+      const long long len = a.lens[u];
+      live = live && (r - u * a.seg_len) < (len < 0 ? 0 : (len > a.seg_len ? (long long)a.seg_len : len));
+    }
+    if (!live) {     // a frame past the batch's own (or the utterance's own) length: a zero row (the next conv's padding)
       if (out16) *(uint2*)(out16 + (int64_t)r * a.C + c4) = make_uint2(0u, 0u);
       if (out32) *(f32x4*)(out32 + (int64_t)r * a.C + c4) = f32x4{0.f, 0.f, 0.f, 0.f};
       continue;
@@ -602,7 +612,22 @@ extern "C" int ttsk_bn_apply(const void* x, int x_is_f32, const float* mean, con
   int64_t n = (int64_t)rows * (C >> 2);
   int blocks = (int)((n + 255) / 256);
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, resid_f32, (bf16_t*)out_bf16, out_f32);
+  hipLaunchKernelGGL(bn_apply_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, resid_f32, (bf16_t*)out_bf16, out_f32);
+  TTSK_CHECK_LAUNCH();
+  return TTSK_OK;
+}
+
+extern "C" int ttsk_bn_apply_lens(const void* x, int x_is_f32, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                                  int rows, int C, int use_tanh, const float* resid_f32, void* out_bf16, float* out_f32,
+                                  const int64_t* lens, int seg_len, void* stream) {
+  TTSK_REQUIRE(x && mean && rstd && gamma && beta && lens && (out_bf16 || out_f32), "bn_apply_lens: null pointer");
+  TTSK_REQUIRE(seg_len > 0 && rows % seg_len == 0, "bn_apply_lens: rows %% seg_len != 0");
+  if (int rc = bn_check(rows, C)) return rc;
+  BnCommon a{x, mean, rstd, gamma, beta, nullptr, rows, C, use_tanh, 0.f, 0u, x_is_f32, nullptr, seg_len, nullptr, (const long long*)lens};
+  int64_t n = (int64_t)rows * (C >> 2);
+  int blocks = (int)((n + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, resid_f32, (bf16_t*)out_bf16, out_f32);
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
 }

@@ -276,6 +276,81 @@ __global__ __launch_bounds__(256) void va_combine_kernel(const bf16_t* __restric
   }
 }
 
+// ---------------------------------------------------------------------------------------------- per-utterance limits (batched synthesis)
+// Rows are (utterance, position) pairs, row = u*seg_len + l; positions l >= lens[u] exist only because the batch was padded to a
+// shape bucket.  A solo run of utterance u has zero padding there, so these kernels write them as zero rows.  lens[u] is clamped
+// to [0, seg_len] here: a caller's bad length cannot move a row's limit outside its own segment.
+__device__ __forceinline__ int clamp_len(const long long* __restrict__ lens, int u, int seg_len) {
+  const long long v = lens[u];
+  return v < 0 ? 0 : (v > seg_len ? seg_len : (int)v);
+}
+
+// gather_add with the limit: out[row] = in[row] + table[idx[row / seg_len]] for l < lens[u], else 0 (the speaker add)
+__global__ __launch_bounds__(256) void gather_add_lens_kernel(const bf16_t* __restrict__ in, const float* __restrict__ table,
+                                                              const long long* __restrict__ idx, const long long* __restrict__ lens,
+                                                              int seg_len, bf16_t* __restrict__ out, int rows, int D) {
+  const int cpr = D >> 2;
+  const int64_t n = (int64_t)rows * cpr;
+  for (int64_t c = blockIdx.x * 256 + threadIdx.x; c < n; c += (int64_t)gridDim.x * 256) {
+    const int row = (int)(c / cpr), ch = (int)(c - (int64_t)row * cpr) * 4;
+    const int u = row / seg_len;
+    if (row - u * seg_len >= clamp_len(lens, u, seg_len)) {
+      *(uint2*)(out + (int64_t)row * D + ch) = make_uint2(0u, 0u);
+      continue;
+    }
+    f32x4 v = *(const f32x4*)(table + idx[u] * D + ch);
+    const uint2 w = *(const uint2*)(in + (int64_t)row * D + ch);
+    v[0] += __uint_as_float(w.x << 16); v[1] += __uint_as_float(w.x & 0xFFFF0000u);
+    v[2] += __uint_as_float(w.y << 16); v[3] += __uint_as_float(w.y & 0xFFFF0000u);
+    *(uint2*)(out + (int64_t)row * D + ch) = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
+  }
+}
+
+// The free-running embedding step (reference: model/modules.py:92-101,131-140 without targets) in one pass: scaled = pred *
+// control[u]; idx = #{bins < scaled} (bucketize_kernel's search and NaN rule); x_out = x + table[idx] (gather_add_kernel's
+// sum), zero rows past lens[u].  Every thread of a row repeats the 8-step search rather than wait for one of them.
+__global__ __launch_bounds__(256) void embed_step_kernel(const float* __restrict__ pred, const float* __restrict__ control,
+                                                         const float* __restrict__ bins, int nb, const float* __restrict__ table,
+                                                         const bf16_t* __restrict__ x, const long long* __restrict__ lens, int seg_len,
+                                                         bf16_t* __restrict__ out, float* __restrict__ scaled, int* __restrict__ idx,
+                                                         int rows, int D) {
+  const int cpr = D >> 2;
+  const int64_t n = (int64_t)rows * cpr;
+  for (int64_t c = blockIdx.x * 256 + threadIdx.x; c < n; c += (int64_t)gridDim.x * 256) {
+    const int row = (int)(c / cpr), ch = (int)(c - (int64_t)row * cpr) * 4;
+    const int u = row / seg_len;
+    const float s = pred[row] * control[u];
+    const int bi = bucket_of(bins, nb, s);
+    if (ch == 0) { scaled[row] = s; idx[row] = bi; }
+    if (row - u * seg_len >= clamp_len(lens, u, seg_len)) {
+      *(uint2*)(out + (int64_t)row * D + ch) = make_uint2(0u, 0u);
+      continue;
+    }
+    f32x4 v = *(const f32x4*)(table + (int64_t)bi * D + ch);
+    const uint2 w = *(const uint2*)(x + (int64_t)row * D + ch);
+    v[0] += __uint_as_float(w.x << 16); v[1] += __uint_as_float(w.x & 0xFFFF0000u);
+    v[2] += __uint_as_float(w.y << 16); v[3] += __uint_as_float(w.y & 0xFFFF0000u);
+    *(uint2*)(out + (int64_t)row * D + ch) = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
+  }
+}
+
+// duration_round_kernel with the control of the row's utterance read from device memory
+__global__ __launch_bounds__(256) void duration_round_dev_kernel(const float* __restrict__ logd, const float* __restrict__ d_control, int L,
+                                                                 float* __restrict__ out, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = fmaxf(rintf(expf(logd[i]) - 1.f) * d_control[i / L], 0.f);
+}
+
+// rows (u, t) with t >= lens[u] := 0 (16-byte pieces), the per-utterance form of zero_frames_kernel
+__global__ __launch_bounds__(256) void zero_frames_lens_kernel(uint4* __restrict__ x, int rows, int q_per_row, int seg_len,
+                                                               const long long* __restrict__ lens) {
+  const int64_t n = (int64_t)rows * q_per_row;
+  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int r = (int)(i / q_per_row), u = r / seg_len;
+    if (r - u * seg_len >= clamp_len(lens, u, seg_len)) x[i] = make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- conversions
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, int64_t n) {
   const int64_t n4 = n >> 2;
@@ -497,6 +572,45 @@ extern "C" int ttsk_zero_frames_from(void* x, int elem_bytes, int rows, int C, i
   const int q = C * elem_bytes / 16;
   hipLaunchKernelGGL(zero_frames_kernel, dim3(grid_for((int64_t)rows * q)), dim3(256), 0, (hipStream_t)stream, (uint4*)x, rows, q, seg_len,
                      frame_limit);
+  TTSK_CHECK_LAUNCH();
+  return TTSK_OK;
+}
+
+extern "C" int ttsk_gather_add_lens(const void* in_bf16, const float* table, const int64_t* idx, const int64_t* lens, int seg_len,
+                                    void* out_bf16, int rows, int D, void* stream) {
+  TTSK_REQUIRE(in_bf16 && table && idx && lens && out_bf16, "gather_add_lens: null pointer");
+  TTSK_REQUIRE(rows > 0 && seg_len > 0 && rows % seg_len == 0 && D > 0 && (D & 3) == 0, "gather_add_lens: bad sizes");
+  hipLaunchKernelGGL(gather_add_lens_kernel, dim3(grid_for((int64_t)rows * (D >> 2))), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)in_bf16, table, (const long long*)idx, (const long long*)lens, seg_len, (bf16_t*)out_bf16, rows, D);
+  TTSK_CHECK_LAUNCH();
+  return TTSK_OK;
+}
+
+extern "C" int ttsk_embed_step(const float* pred, const float* control, const float* bins, int n_bins, const float* table,
+                               const void* x_bf16, const int64_t* lens, int seg_len, void* x_out_bf16, float* scaled_out,
+                               int32_t* idx_out, int rows, int D, void* stream) {
+  TTSK_REQUIRE(pred && control && bins && table && x_bf16 && lens && x_out_bf16 && scaled_out && idx_out, "embed_step: null pointer");
+  TTSK_REQUIRE(rows > 0 && seg_len > 0 && rows % seg_len == 0 && D > 0 && (D & 3) == 0 && n_bins > 0, "embed_step: bad sizes");
+  hipLaunchKernelGGL(embed_step_kernel, dim3(grid_for((int64_t)rows * (D >> 2))), dim3(256), 0, (hipStream_t)stream, pred, control, bins,
+                     n_bins, table, (const bf16_t*)x_bf16, (const long long*)lens, seg_len, (bf16_t*)x_out_bf16, scaled_out, idx_out, rows, D);
+  TTSK_CHECK_LAUNCH();
+  return TTSK_OK;
+}
+
+extern "C" int ttsk_duration_round_dev(const float* logd, const float* d_control, int L, float* out, int n, void* stream) {
+  TTSK_REQUIRE(logd && d_control && out && n > 0 && L > 0 && n % L == 0, "duration_round_dev: bad arguments");
+  hipLaunchKernelGGL(duration_round_dev_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, logd, d_control, L, out, n);
+  TTSK_CHECK_LAUNCH();
+  return TTSK_OK;
+}
+
+extern "C" int ttsk_zero_frames_lens(void* x, int elem_bytes, int rows, int C, int seg_len, const int64_t* lens, void* stream) {
+  TTSK_REQUIRE(x && lens && rows > 0 && C > 0 && seg_len > 0 && rows % seg_len == 0, "zero_frames_lens: bad arguments");
+  TTSK_REQUIRE((elem_bytes == 2 || elem_bytes == 4) && ((int64_t)C * elem_bytes) % 16 == 0 && (((uintptr_t)x) & 15) == 0,
+               "zero_frames_lens: rows must be whole 16-byte pieces");
+  const int q = C * elem_bytes / 16;
+  hipLaunchKernelGGL(zero_frames_lens_kernel, dim3(grid_for((int64_t)rows * q)), dim3(256), 0, (hipStream_t)stream, (uint4*)x, rows, q, seg_len,
+                     (const long long*)lens);
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
 }

@@ -612,13 +612,14 @@ class FastSpeech2(nn.Module):
             return x2, qkv_next
         return x2
 
-    def _predictor_fwd(self, pre, x, Bn, Lp, lens, p, site, rng, ctx):
-        """VariancePredictor.  reference: model/modules.py:255-309."""
+    def _predictor_fwd(self, pre, x, Bn, Lp, lens, p, site, rng, ctx, hidden_lens=None):
+        """VariancePredictor.  reference: model/modules.py:255-309.  `hidden_lens` (batched synthesis): the hidden rows between the two
+        convs are zero past each utterance's own length, as the second conv's zero padding is when the utterance runs alone."""
         d, rows = self.d, Bn * Lp
         c = pre + "conv_layer."
         h1 = ops.conv1d(x.view(Bn, Lp, d), self._w(c + "conv1d_1.conv.weight"), self._m(c + "conv1d_1.conv.bias"), flags=ops.RELU)
         a1, _, m1, r1, _ = ops.layernorm_fwd(h1.view(rows, -1), None, self._m(c + "layer_norm_1.weight"), self._m(c + "layer_norm_1.bias"),
-                                             None, 0, p_post=p, site_post=site, rng=rng, save_z=False)
+                                             hidden_lens, Lp if hidden_lens is not None else 0, p_post=p, site_post=site, rng=rng, save_z=False)
         h2 = ops.conv1d(a1.view(Bn, Lp, -1), self._w(c + "conv1d_2.conv.weight"), self._m(c + "conv1d_2.conv.bias"), flags=ops.RELU)
         hw, hb = self._m(pre + "linear_layer.weight"), self._m(pre + "linear_layer.bias")
         if hb.numel() > 1:              # the CWT pitch predictor's Linear(256 -> 11): csrc/cwt.hip
@@ -900,11 +901,47 @@ class FastSpeech2(nn.Module):
         """Encoder + variance adaptor of the free-running inference path (reference: fastspeech2.py:62-99 with no
         targets, modules.py:142-205) up to the per-utterance frame totals.  Only enqueues kernels (hipGraph-capturable);
         the caller reads `total.max()` on the host — the one data-dependent shape of the path — and calls `eval_back`."""
+        return self._eval_front(speakers, texts, src_lens, Lp, p_control, e_control, d_control, ragged=False)
+
+    def eval_back(self, x3, dur, Lp, T):
+        """LengthRegulator + decoder + mel_linear + PostNet for a known frame count T (reference: modules.py:199-205,
+        Models.py:157-189, fastspeech2.py:101-104).  Capturable; returns (mel, postnet mel, mel_lens, mel_masks)."""
+        return self._eval_back(x3, dur, Lp, T, ragged=False)
+
+    # ---- batched inference: every utterance as if run alone
+    def eval_front_ragged(self, speakers, texts, src_lens, Lp, p_control, e_control, d_control):
+        """`eval_front` for texts of different lengths padded to Lp phonemes, each utterance computed as the model computes it
+        alone.  The reference's padded batch is not that: its predictors' second conv reads non-zero padded
+        rows.  Here every tensor a predictor conv reads as a neighbour is zero past src_lens[u]: the encoder output (its last
+        LayerNorm zeroes PAD rows), + speaker (`gather_add_lens`), + pitch embedding (`embed_step`), and the hidden rows
+        (`layernorm_fwd` given the lengths).  speakers / src_lens (B,) int64, the controls (B,) fp32 device tensors: values, not
+        shapes, so one captured graph serves every setting.  Returns (x3, dur, total, (pitch, energy, logd)): no masks."""
+        if self.use_cwt:
+            # inverse_batch_cwt standardises over the batch axis (cwt_utils.py:40-66, x.mean(0)) and the CNNscalar heads pool over the
+            # padded length (modules.py:360-364): the reference defines no batch-independent result for this branch
+            raise ops.L.TtskError("use_cwt: batched synthesis of different-length texts is not defined -- the reference's CWT pitch "
+                                  "standardises over the batch axis and its scalar heads pool over the padded length; synthesize one text per call")
+        if Lp > self.max_seq_len:
+            raise ops.L.TtskError("eval_front_ragged: %d phonemes exceed max_seq_len %d; longer texts take the single-utterance path" % (Lp, self.max_seq_len))
+        return self._eval_front(speakers, texts, src_lens, Lp, p_control, e_control, d_control, ragged=True)
+
+    def eval_back_ragged(self, x3, dur, Lp, T):
+        """`eval_back` for a frame count T that is a bucket (>= every utterance's own count): frames t >= mel_lens[u] of the PostNet's
+        input and of its layers' outputs are zero rows, the zero padding each k = 5 conv meets when utterance u runs alone (in the
+        reference's batch mel_linear's bias sits there, Layers.py:133-143).  Returns (mel, postnet mel, mel_lens); only frames
+        t < mel_lens[u] of the two mels mean anything."""
+        if T > self.max_seq_len:
+            raise ops.L.TtskError("eval_back_ragged: %d frames exceed max_seq_len %d" % (T, self.max_seq_len))
+        return self._eval_back(x3, dur, Lp, T, ragged=True)[:3]
+
+    def _eval_front(self, speakers, texts, src_lens, Lp, p_control, e_control, d_control, ragged):
+        """The body of `eval_front` (`ragged` False: scalar controls, the reference's padded-batch semantics) and of
+        `eval_front_ragged` (True: control tensors, per-utterance limits on everything a predictor conv reads)."""
         self.sync_shadow()
         d = self.d
         Bn = texts.shape[0]
         va = "variance_adaptor."
-        src_masks = ops.length_mask(src_lens, Lp)
+        src_masks = None if ragged else ops.length_mask(src_lens, Lp)       # nothing on the device reads the masks
         pe_enc = sinusoid_table(Lp, d).to(self.device) if Lp > self.max_seq_len else self.get("encoder.position_enc")[0]
         x = ops.gather_add(None, self._m("encoder.src_word_emb.weight"), texts, pe=pe_enc, pe_mod=Lp, rows=Bn * Lp)
         qkv = None
@@ -912,33 +949,45 @@ class FastSpeech2(nn.Module):
             nxt = "encoder.layer_stack.%d." % (i + 1) if i + 1 < self.n_enc else None
             x = self._fft_fwd("encoder.layer_stack.%d." % i, x, Bn, Lp, src_lens, self.n_head_enc, 0.0, 0, None, None, qkv=qkv, next_pre=nxt)
             x, qkv = x if nxt else (x, None)
-        logd = self._predictor_fwd(va + "duration_predictor.", x, Bn, Lp, src_lens, 0.0, 0, None, None)
-        x1 = ops.gather_add(x, self._m("speaker_emb.weight"), speakers, idx_div=Lp)
-        pitch = self._predictor_fwd(va + "pitch_predictor.", x1, Bn, Lp, src_lens, 0.0, 0, None, None)
-        heads = None
-        if self.use_cwt:
-            pidx, heads, _ = self._cwt_pitch_rows(x1, pitch, Bn, Lp, p_control)
+        hl = src_lens if ragged else None
+        logd = self._predictor_fwd(va + "duration_predictor.", x, Bn, Lp, src_lens, 0.0, 0, None, None, hidden_lens=hl)
+        if ragged:
+            x1 = ops.gather_add_lens(x, self._m("speaker_emb.weight"), speakers, src_lens, Lp)
         else:
-            pidx, pitch = ops.bucketize(pitch, self.get(va + "pitch_bins"), p_control, want_scaled=True)
-        x2 = ops.gather_add(x1, self._m(va + "pitch_embedding.weight"), pidx.view(-1))
-        energy = self._predictor_fwd(va + "energy_predictor.", x2, Bn, Lp, src_lens, 0.0, 0, None, None)
-        eidx, energy = ops.bucketize(energy, self.get(va + "energy_bins"), e_control, want_scaled=True)
-        x3 = ops.gather_add(x2, self._m(va + "energy_embedding.weight"), eidx.view(-1))
-        dur = ops.duration_round(logd, d_control)
+            x1 = ops.gather_add(x, self._m("speaker_emb.weight"), speakers, idx_div=Lp)
+        pitch = self._predictor_fwd(va + "pitch_predictor.", x1, Bn, Lp, src_lens, 0.0, 0, None, None, hidden_lens=hl)
+        heads = None
+        if ragged:
+            x2, pitch, _ = ops.embed_step(pitch, p_control, self.get(va + "pitch_bins"), self._m(va + "pitch_embedding.weight"), x1, src_lens, Lp)
+        else:
+            if self.use_cwt:
+                pidx, heads, _ = self._cwt_pitch_rows(x1, pitch, Bn, Lp, p_control)
+            else:
+                pidx, pitch = ops.bucketize(pitch, self.get(va + "pitch_bins"), p_control, want_scaled=True)
+            x2 = ops.gather_add(x1, self._m(va + "pitch_embedding.weight"), pidx.view(-1))
+        energy = self._predictor_fwd(va + "energy_predictor.", x2, Bn, Lp, src_lens, 0.0, 0, None, None, hidden_lens=hl)
+        if ragged:
+            x3, energy, _ = ops.embed_step(energy, e_control, self.get(va + "energy_bins"), self._m(va + "energy_embedding.weight"), x2, src_lens, Lp)
+            dur = ops.duration_round_dev(logd, d_control)
+        else:
+            eidx, energy = ops.bucketize(energy, self.get(va + "energy_bins"), e_control, want_scaled=True)
+            x3 = ops.gather_add(x2, self._m(va + "energy_embedding.weight"), eidx.view(-1))
+            dur = ops.duration_round(logd, d_control)
         _, _, _, total = ops.length_regulator_fwd(x3.view(Bn, Lp, d), dur, 1, want_idx=False)
+        if ragged:
+            return x3, dur, total, (pitch, energy, logd)
         if self.use_cwt:
             return x3, dur, total, (pitch, energy, logd, src_masks, heads)     # pitch: the (B, L, 11) prediction; heads (2, B)
         return x3, dur, total, (pitch, energy, logd, src_masks)
 
-    def eval_back(self, x3, dur, Lp, T):
-        """LengthRegulator + decoder + mel_linear + PostNet for a known frame count T (reference: modules.py:199-205,
-        Models.py:157-189, fastspeech2.py:101-104).  Capturable; returns (mel, postnet mel, mel_lens, mel_masks)."""
+    def _eval_back(self, x3, dur, Lp, T, ragged):
+        """The body of `eval_back` and (`ragged`: per-utterance frame limits in the PostNet, no mask) of `eval_back_ragged`."""
         d = self.d
         Bn = x3.shape[0] // Lp
         dev = self.device
         pe_dec = sinusoid_table(T, d).to(dev) if T > self.max_seq_len else self.get("decoder.position_enc")[0]
         dec_in, _, _, mel_lens = ops.length_regulator_fwd(x3.view(Bn, Lp, d), dur, T, pe=pe_dec, want_idx=False)
-        mel_masks = ops.length_mask(mel_lens, T)
+        mel_masks = None if ragged else ops.length_mask(mel_lens, T)
         y = dec_in.view(Bn * T, d)
         qkv = None
         for i in range(self.n_dec):
@@ -948,6 +997,8 @@ class FastSpeech2(nn.Module):
         rows = Bn * T
         mel16 = torch.empty(rows, self.n_mel, dtype=bf16, device=dev)
         mel = ops.linear(y, self._w("mel_linear.weight"), self._m("mel_linear.bias"), out_dtype=torch.float32, C2=mel16)
+        if ragged:
+            ops.zero_frames_lens(mel16, mel_lens, T)     # the path's one zero-fill pass: the GEMM's bf16 copy carries the bias in padded frames
         xin = mel16.view(Bn, T, self.n_mel)
         for i in range(5):
             pp = "postnet.convolutions.%d." % i
@@ -959,8 +1010,11 @@ class FastSpeech2(nn.Module):
                 yc = ops.conv1d(xin, self._w(pp + "0.conv.weight"), self._m(pp + "0.conv.bias"), out_dtype=torch.float32)
             C = yc.shape[2]
             last = i == 4
-            nxt = ops.bn_apply(yc.view(rows, C), self.get(pp + "1.running_mean"), ops.rsqrt_eps(self.get(pp + "1.running_var")),
-                               self._m(pp + "1.weight"), self._m(pp + "1.bias"), not last, resid=mel if last else None, out_f32=last)
+            bn = (self.get(pp + "1.running_mean"), ops.rsqrt_eps(self.get(pp + "1.running_var")), self._m(pp + "1.weight"), self._m(pp + "1.bias"), not last)
+            if ragged:
+                nxt = ops.bn_apply_lens(yc.view(rows, C), *bn, mel_lens, T, resid=mel if last else None, out_f32=last)
+            else:
+                nxt = ops.bn_apply(yc.view(rows, C), *bn, resid=mel if last else None, out_f32=last)
             xin = nxt.view(Bn, T, C) if not last else nxt
         return mel.view(Bn, T, self.n_mel), xin.view(Bn, T, self.n_mel), mel_lens, mel_masks
 

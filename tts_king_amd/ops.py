@@ -1149,6 +1149,18 @@ def duration_round(logd, d_control=1.0):
     return out
 
 
+def duration_round_dev(logd, d_control):
+    """`duration_round` with one control per utterance: logd (B, L) fp32, d_control (B,) fp32 on the device."""
+    _dev(logd, d_control)
+    if logd.dtype != torch.float32 or d_control.dtype != torch.float32 or logd.dim() != 2 or not logd.is_contiguous() \
+            or not d_control.is_contiguous() or d_control.numel() != logd.shape[0]:
+        raise L.TtskError("duration_round_dev: needs contiguous fp32 logd (B, L) and d_control (B,), got %s and %s" % (tuple(logd.shape), tuple(d_control.shape)))
+    out = torch.empty_like(logd)
+    check(L.load().ttsk_duration_round_dev(_ptr(logd), _ptr(d_control), logd.shape[-1], _ptr(out), logd.numel(), _stream()),
+          "ttsk_duration_round_dev")
+    return out
+
+
 def length_mask(lens, T):
     """(B,) int64 -> (B,T) bool, True = PAD.  reference: fs_two/utils/tools.py:121-131."""
     _dev(lens)
@@ -1178,6 +1190,44 @@ def gather_add(x, table, idx, idx_div=1, pe=None, pe_mod=1, rows=None, out=None)
     check(L.load().ttsk_gather_add(_ptr(x), _ptr(table), _ptr(idx), int(idx.dtype == torch.int64), idx_div, _ptr(pe), pe_mod,
                                    _ptr(out), rows, D, _stream()), "ttsk_gather_add")
     return out
+
+
+def gather_add_lens(x, table, idx, lens, seg_len, out=None):
+    """out[u*seg_len + l] = x[..] + table[idx[u]] for l < lens[u], a zero row past it; x bf16 (rows, D), idx / lens (B,) int64."""
+    _dev(x, table, idx, lens)
+    if idx.dtype != torch.int64 or lens.dtype != torch.int64:
+        raise L.TtskError("gather_add_lens: idx and lens must be int64")
+    rows, D = x.shape
+    Bn = rows // max(int(seg_len), 1)
+    if seg_len <= 0 or Bn * seg_len != rows or idx.numel() != Bn or lens.numel() != Bn or not (x.is_contiguous() and idx.is_contiguous() and lens.is_contiguous()):
+        raise L.TtskError("gather_add_lens: %d rows of seg_len %d need contiguous idx and lens of %d entries, got %d and %d"
+                          % (rows, seg_len, Bn, idx.numel(), lens.numel()))
+    if out is None:
+        out = torch.empty(rows, D, dtype=bf16, device=x.device)
+    check(L.load().ttsk_gather_add_lens(_ptr(x), _ptr(table), _ptr(idx), _ptr(lens), seg_len, _ptr(out), rows, D, _stream()),
+          "ttsk_gather_add_lens")
+    return out
+
+
+def embed_step(pred, control, bins, table, x, lens, seg_len):
+    """The free-running embedding step in one launch: scaled = pred * control[u], idx = bucketize(scaled, bins), x_out = x + table[idx]
+    with zero rows past lens[u].  pred (B, L) fp32, control (B,) fp32, x bf16 (B * L, D), lens (B,) int64 -> (x_out, scaled, idx)."""
+    _dev(pred, control, bins, table, x, lens)
+    if lens.dtype != torch.int64 or control.dtype != torch.float32 or pred.dtype != torch.float32:
+        raise L.TtskError("embed_step: pred / control must be fp32, lens int64")
+    pred = pred.contiguous()
+    rows, D = x.shape
+    Bn = rows // max(int(seg_len), 1)
+    if seg_len <= 0 or Bn * seg_len != rows or pred.numel() != rows or control.numel() != Bn or lens.numel() != Bn or table.shape[0] <= bins.numel() \
+            or not (x.is_contiguous() and control.is_contiguous() and lens.is_contiguous()):
+        raise L.TtskError("embed_step: %d rows of seg_len %d need %d predictions, contiguous control and lens of %d entries and a table of more than "
+                          "%d rows; got %d, %d, %d, %d" % (rows, seg_len, rows, Bn, bins.numel(), pred.numel(), control.numel(), lens.numel(), table.shape[0]))
+    out = torch.empty(rows, D, dtype=bf16, device=x.device)
+    scaled = torch.empty_like(pred)
+    idx = torch.empty(pred.shape, dtype=torch.int32, device=x.device)
+    check(L.load().ttsk_embed_step(_ptr(pred), _ptr(control), _ptr(bins), bins.numel(), _ptr(table), _ptr(x), _ptr(lens), seg_len,
+                                   _ptr(out), _ptr(scaled), _ptr(idx), rows, D, _stream()), "ttsk_embed_step")
+    return out, scaled, idx
 
 
 def scatter_sum(dx, idx, dtable, idx_div=1, skip_row=-1, accumulate=True, defer=None):
@@ -1292,6 +1342,22 @@ def zero_frames_from(x, frame_limit):
     return x
 
 
+def _check_lens(what, lens, rows, seg_len):
+    """The kernels clamp the VALUES of a per-utterance limit; its extent (one int64 per utterance) is checked here."""
+    if seg_len <= 0 or rows % seg_len or lens.dtype != torch.int64 or not lens.is_contiguous() or lens.numel() != rows // seg_len:
+        raise L.TtskError("%s: %d rows of seg_len %d need a contiguous int64 lens of %d entries, got %s %s"
+                          % (what, rows, seg_len, rows // max(seg_len, 1), lens.dtype, tuple(lens.shape)))
+
+
+def zero_frames_lens(x, lens, seg_len):
+    """x (rows, C) bf16/fp32, rows = utterances * seg_len: frames t >= lens[u] of utterance u := 0 (lens (B,) int64)."""
+    _dev(x, lens)
+    rows, Cn = x.shape
+    _check_lens("zero_frames_lens", lens, rows, seg_len)
+    check(L.load().ttsk_zero_frames_lens(_ptr(x), x.element_size(), rows, Cn, seg_len, _ptr(lens), _stream()), "ttsk_zero_frames_lens")
+    return x
+
+
 BN_SLAB = True      # two-launch BatchNorm (channel slabs) where the channel count allows; the three-launch kernels serve the rest and inference
 
 
@@ -1322,6 +1388,18 @@ def bn_apply(x, mean, rstd, gamma, beta, use_tanh, p=0.0, site=0, rng=None, resi
     o32 = _f32(rows, Cn, device=x.device) if out_f32 else None
     check(L.load().ttsk_bn_apply(_ptr(x), int(x.dtype == torch.float32), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), rows, Cn, int(use_tanh), p, site,
                                  _ptr(rng), _ptr(resid), _ptr(o16), _ptr(o32), *_lim(frame_limit), _stream()), "ttsk_bn_apply")
+    return o32 if out_f32 else o16
+
+
+def bn_apply_lens(x, mean, rstd, gamma, beta, use_tanh, lens, seg_len, resid=None, out_f32=False):
+    """Inference `bn_apply` whose frames t >= lens[u] come out as zero rows (lens (B,) int64, rows = B * seg_len)."""
+    _dev(x, lens)
+    rows, Cn = x.shape
+    _check_lens("bn_apply_lens", lens, rows, seg_len)
+    o16 = None if out_f32 else torch.empty(rows, Cn, dtype=bf16, device=x.device)
+    o32 = _f32(rows, Cn, device=x.device) if out_f32 else None
+    check(L.load().ttsk_bn_apply_lens(_ptr(x), int(x.dtype == torch.float32), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), rows, Cn,
+                                      int(use_tanh), _ptr(resid), _ptr(o16), _ptr(o32), _ptr(lens), seg_len, _stream()), "ttsk_bn_apply_lens")
     return o32 if out_f32 else o16
 
 

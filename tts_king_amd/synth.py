@@ -4,11 +4,15 @@ reference path: tts_king.py:25-49 (`generate_mel` -> `mel_to_wav`), fsapi.py:38-
 launches ~400 small ATen ops per utterance and syncs per phoneme in the LengthRegulator; here the path is three replayed
 graphs: A = encoder + variance adaptor + duration totals (shape key: phonemes L, controls), then ONE host read of the
 frame count T (the only data-dependent shape), B = LengthRegulator + decoder + PostNet (key: L, T), C = HiFi-GAN
-generator (key: T; `wav_ragged`: the windowed generator, key: the number of windows N, whatever the lengths).  Graphs are cached per key (utterances of equal L and T replay the same graphs); a key's first call
+generator (key: T; `wav_ragged`: the windowed generator, key: the number of windows N, whatever the lengths).  `mel_ragged` runs texts of
+different lengths as one call on graphs keyed by shape buckets only (tts_king_amd/batching.py).  Graphs are cached per key (utterances of equal L and T replay the same graphs); a key's first call
 runs eagerly once (warm-up: lazy allocations, weight packing) and is captured on the second.
 """
 import torch
 
+import numpy as np
+
+from . import batching
 from . import ops
 from . import windows
 
@@ -29,14 +33,16 @@ class _Graph:
 
 
 class GraphedSynthesizer:
-    def __init__(self, fs2, vocoder=None, max_graphs=32):
+    def __init__(self, fs2, vocoder=None, max_graphs=32, graphs=True, l_bucket=batching.L_BUCKET, t_bucket=batching.T_BUCKET):
+        """`graphs=False`: the same kernels launched plainly, nothing captured (the facades' `hip_graph: false`)."""
         self.fs2, self.vocoder, self.max_graphs = fs2, vocoder, max_graphs
+        self.graphs, self.l_bucket, self.t_bucket = graphs, int(l_bucket), int(t_bucket)
         self._front, self._back, self._voc, self._rag = {}, {}, {}, {}
         self._seen = set()
 
     def _get(self, cache, key, fn, inputs):
         """Eager on first sight of `key`, captured on the second, replayed afterwards."""
-        if key is None:                 # not capturable (host-side position table for > max_seq_len): plain launches
+        if key is None or not self.graphs:      # not capturable (host-side position table for > max_seq_len), or graphs off: plain launches
             return fn(*inputs)
         g = cache.get(key)
         if g is not None:
@@ -64,10 +70,70 @@ class GraphedSynthesizer:
         x3, dur, total, _ = self._get(self._front, kf, front, (speaker, texts, src_lens))
         T = max(int(total.max().item()), 1)                 # the path's one host read
         back = lambda x, dd: m.eval_back(x, dd, Lp, T)
-        kb = ("back", Bn, Lp, T) if T <= m.max_seq_len else None
+        # "exact": T here is the frame count itself; `mel_ragged` keeps ("back", B, L_bucket, T_bucket) in the same cache, and the two graphs differ
+        kb = ("back", Bn, Lp, T, "exact") if T <= m.max_seq_len else None
         mel, post, mel_lens, _ = self._get(self._back, kb, back, (x3, dur))
         # a replayed graph returns its private static buffers: hand out copies, or the caller's mel changes at the next call
         return post.clone(), mel_lens.clone()
+
+    @torch.no_grad()
+    def mel_ragged(self, speakers, texts, p_control=1.0, e_control=1.0, d_control=1.0, aux=False):
+        """Texts of different lengths in one call, every utterance as the model gives it alone (not as the reference's padded batch
+        gives it: DESIGN.md section 12).  speakers: one id or one per utterance; texts: a list of 1-D phoneme-id arrays; each control
+        a scalar or one value per utterance.  -> (a list of (T_u, 80) fp32 postnet mels on the device, the frame counts [T_u]).
+        The texts are padded to `l_bucket` phonemes and the frames to `t_bucket`, and the graph keys are ("front", B, L_bucket) and
+        ("back", B, L_bucket, T_bucket): speakers, lengths and the control arrays are static inputs copied in before replay, so
+        neither a new length nor a new control value captures anything.  One host read (the B frame totals).  An utterance whose
+        text or predicted frame count exceeds max_seq_len leaves the batch for `mel`.  An utterance predicted to have no frame at all comes
+        back as an empty (0, 80) mel with count 0 (`mel` returns one padding frame there, which is no frame of the utterance either); its
+        decoder rows then attend over zero keys in the batched graph, and nothing reads what they produce.  `aux`: also a list of per-utterance dicts
+        (logd, pitch, energy, dur over the utterance's own phonemes, mel = the pre-PostNet mel; None for an utterance that left the batch)."""
+        m = self.fs2
+        m.eval()
+        rows = batching.as_id_rows(texts)
+        Bn = len(rows)
+        spk = batching.per_utterance(speakers.cpu().numpy() if torch.is_tensor(speakers) else speakers, Bn, "speakers", np.int64)
+        ctl = [batching.per_utterance(c, Bn, n) for c, n in ((p_control, "p_control"), (e_control, "e_control"), (d_control, "d_control"))]
+        mels, lens, extra = [None] * Bn, [0] * Bn, ([None] * Bn if aux else None)
+        self._ragged(rows, spk, ctl, list(range(Bn)), mels, lens, extra)
+        return (mels, lens, extra) if aux else (mels, lens)
+
+    def _solo(self, rows, spk, ctl, i, mels, lens):
+        dev = self.fs2.device
+        post, ml = self.mel(torch.from_numpy(spk[i:i + 1]).to(dev), torch.from_numpy(rows[i][None]).to(dev), float(ctl[0][i]), float(ctl[1][i]),
+                            float(ctl[2][i]))
+        mels[i], lens[i] = post[0], int(post.shape[1])
+
+    def _ragged(self, rows, spk, ctl, only, mels, lens, extra):
+        m, dev = self.fs2, self.fs2.device
+        plan = batching.plan_texts(rows, m.max_seq_len, self.l_bucket, only)
+        for i in plan.solo:
+            self._solo(rows, spk, ctl, i, mels, lens)
+        if not plan.batch:
+            return
+        Bn, Lp = len(plan.batch), plan.L
+        sel = np.asarray(plan.batch)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+        inputs = (up(spk[sel]), up(plan.ids), up(plan.lens), up(ctl[0][sel]), up(ctl[1][sel]), up(ctl[2][sel]))
+        front = lambda s, t, sl, pc, ec, dc: m.eval_front_ragged(s, t, sl, Lp, pc, ec, dc)
+        x3, dur, total, (pitch, energy, logd) = self._get(self._front, plan.key, front, inputs)
+        totals = total.cpu().tolist()                        # the path's one host read
+        keep, over, T = batching.plan_frames(totals, m.max_seq_len, self.t_bucket)
+        if over:            # a predicted frame count past the position table: those utterances alone, the others again as their own batch
+            for r in over:
+                self._solo(rows, spk, ctl, plan.batch[r], mels, lens)
+            if keep:
+                self._ragged(rows, spk, ctl, [plan.batch[r] for r in keep], mels, lens, extra)
+            return
+        back = lambda x, dd: m.eval_back_ragged(x, dd, Lp, T)
+        mel_pre, post, _ = self._get(self._back, batching.back_key(Bn, Lp, T), back, (x3, dur))
+        for r, i in enumerate(plan.batch):
+            # slices of a replayed graph's private buffers: hand out copies
+            n, Lu = max(totals[r], 0), int(plan.lens[r])
+            mels[i], lens[i] = post[r, :n].clone(), n
+            if extra is not None:
+                extra[i] = {"logd": logd[r, :Lu].clone(), "pitch": pitch[r, :Lu].clone(), "energy": energy[r, :Lu].clone(),
+                            "dur": dur.view(Bn, Lp)[r, :Lu].clone(), "mel": mel_pre[r, :n].clone()}
 
     @torch.no_grad()
     def wav(self, mel_bct):
