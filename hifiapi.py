@@ -82,9 +82,9 @@ class HIFIapi:
     def generate_ragged(self, mels, frames_first=False):
         """mels: a list of (80, T_i) or (1, 80, T_i) mels of any lengths (`frames_first`: FastSpeech2's (T_i, 80) / (1, T_i, 80) rows) ->
         a list of int16 ndarrays (1, 1, 256 T_i) on the host, each the truncation of what the generator gives for that mel alone.
-        Utterances of at least `tts_king_amd.windows.W` frames run together as fixed-size windows (`Generator.forward_ragged`; with
-        `hip_graph` one replayed graph per window count) and come back in ONE device-to-host copy; shorter ones go through the
-        generator one by one."""
+        The utterances run together as fixed-size windows of `tts_king_amd.windows.W` frames (`Generator.forward_ragged`; with
+        `hip_graph` one replayed graph per window count) and come back in ONE device-to-host copy; a shorter one is a row of the same
+        batch with its own length, and goes through the generator alone only where `Generator.short_rows()` is False."""
         from tts_king_amd import windows
         self.model.eval()
         scale = float(self.cfg.hifi.MAX_WAV_VALUE)

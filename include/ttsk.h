@@ -467,15 +467,20 @@ int ttsk_to_int16(const float* src, int16_t* dst, int64_t n, float scale, void* 
  * kernels are driven by the device-resident plan table, TTSK_WIN_ROW int32 per window:
  *   [0] utterance   [1] start frame of the window in its utterance   [2],[3] kept frames [lo, hi) of the utterance
  *   [4] frame of the flat output where frame lo goes   [5] frame of the mel staging buffer where the window starts,
- *   -1 = padding window (reads zeros, keeps nothing)   [6],[7] zero
+ *   -1 = padding window (reads zeros, keeps nothing)
+ *   [6] (TTSK_WIN_VALID) valid frames of the row: 0 = all W (what a window of a long utterance holds); v in 1..W = an utterance
+ *   shorter than the window as a row of its own (start 0, kept [0, v)): frames >= v of the row do not exist   [7] zero
  * so lengths are data and a captured graph holds for every call with the same N.
  * mel_windows: mel staging (fp32; frame f, channel c at src[f * stride_t + c * stride_c]: (C, frames) rows with stride_t = 1, or
  *              FastSpeech2's (frames, C) rows with stride_c = 1) -> (N, W, C) bf16 / fp16 channels-last, what ttsk_nct_to_ntc
  *              writes for a (N, C, W) batch.  W a multiple of 32, C a multiple of 8, n_src_frames = frames the staging holds.
+ *              A row with v valid frames reads v frames of the staging buffer (checked against n_src_frames with v, not W) and is
+ *              zero from frame v on.
  * wav_stitch:  (N, spf * W) fp32 window waveforms (spf samples per frame, a multiple of 8) -> the kept samples of every window at
  *              dst[plan[4] * spf ...]; to_i16 = 0: fp32, 1: int16 = (x * scale) truncated toward zero (ttsk_to_int16's arithmetic).
  *              n_dst_frames = frames the destination holds. */
 #define TTSK_WIN_ROW 8
+#define TTSK_WIN_VALID 6
 int ttsk_mel_windows(const float* src, int64_t stride_t, int64_t stride_c, int64_t n_src_frames, const int32_t* plan, void* dst16,
                      int f16, int N, int W, int C, void* stream);
 int ttsk_wav_stitch(const float* src, const int32_t* plan, void* dst, int64_t n_dst_frames, int to_i16, float scale, int N, int W,
@@ -566,6 +571,37 @@ int ttsk_hifi_mrf32_post_supported(int C, int k0, int k1, int k2, int k_post);
 int ttsk_hifi_mrf32_post(const void* x16, float* out, void* stage_out16, int f16, const void* const* weights, const float* const* biases,
                          const int32_t* dilations, const void* w_post16, const float* b_post, int B, int len, int C, int k0, int k1, int k2,
                          int k_post, float slope, float final_slope, float scale, void* stream);
+
+/* ---- a per-row length beside the batch stride (short utterances as rows of the windowed batch)
+ * The fused generator kernels above carry one `len`: the row stride of the (B, len, C) batch AND the edge beyond which a conv reads and
+ * writes zero.  The *_rowlen forms part the two.  row_frames[b * row_stride] (int32 on the device: column TTSK_WIN_VALID of the plan
+ * table with row_stride = TTSK_WIN_ROW, or a compact copy with row_stride = 1) is the number of valid MEL frames of row b and spf the
+ * samples per mel frame at the kernel's stage: positions >= row_frames * spf of the row are conv zero padding for every read and
+ * every in-kernel intermediate, and nothing is stored there (a tile wholly past the edge returns at once), so `out16` must be ZERO
+ * past the edge on entry wherever a later kernel reads it without a length (the upsamplers, conv_post): modes 1 / 2 accumulate into
+ * it, mode 0 leaves it.  A value <= 0 means the whole row, a larger one is clamped to len inside the kernel (a wrong table gives
+ * wrong audio, never an access outside the row); row_frames = NULL: every row full — the same results as the plain entry point, bit for
+ * bit.  row_stride and spf must be positive.  Everything else as the entry point of the same name. */
+int ttsk_hifi_conv_pair_rowlen(const void* x16, const void* w1_pack, const float* bias1, const void* w2_pack, const float* bias2, void* out16,
+                             int f16, int B, int len, int C, int K, int dil, float slope, int mode, float scale, float final_slope,
+                             const int32_t* row_frames, int row_stride, int spf, void* stream);
+int ttsk_hifi_conv_pair_ws_rowlen(const void* x16, const void* w1_pack, const float* bias1, const void* w2_pack, const float* bias2,
+                                void* out16, int f16, int B, int len, int C, int K, int dil, float slope, int mode, float scale,
+                                float final_slope, int max_wgs, const int32_t* row_frames, int row_stride, int spf, void* stream);
+int ttsk_hifi_resblock2_rowlen(const void* x16, const void* w0_pack, const float* bias0, const void* w1_pack, const float* bias1, void* out16,
+                             int f16, int B, int len, int C, int K, int d0, int d1, float slope, int mode, float scale, float final_slope,
+                             const int32_t* row_frames, int row_stride, int spf, void* stream);
+int ttsk_hifi_resblock1_rowlen(const void* x16, void* out16, int f16, const void* const* weights, const float* const* biases,
+                             const int32_t* dilations, int B, int len, int C, int K, int mode, float scale, float slope,
+                             float final_slope, const int32_t* row_frames, int row_stride, int spf, void* stream);
+/* (out past a row's edge is not written: those samples belong to no utterance and ttsk_wav_stitch keeps none of them) */
+int ttsk_hifi_mrf32_post_rowlen(const void* x16, float* out, void* stage_out16, int f16, const void* const* weights,
+                              const float* const* biases, const int32_t* dilations, const void* w_post16, const float* b_post, int B,
+                              int len, int C, int k0, int k1, int k2, int k_post, float slope, float final_slope, float scale,
+                              const int32_t* row_frames, int row_stride, int spf, void* stream);
+/* x16 (B, len, C) 16-bit, C a multiple of 8: the positions of row b from row_frames[b * row_stride] * spf on are set to zero (same
+ * clamping; NULL: nothing to do).  The short-row route's fill behind conv_pre, whose activated output the first upsampler reads. */
+int ttsk_zero_rows_past(void* x16, int B, int len, int C, const int32_t* row_frames, int row_stride, int spf, void* stream);
 
 /* rows (u, t) with t >= frame_limit[0] of x [rows][C] (elem_bytes 2 or 4, row = u*seg_len + t) are set to zero: the mel
  * frames / mel gradients past the batch's own longest utterance under shape-bucketed training (see BatchNorm below). */

@@ -9,6 +9,7 @@
 // pack, coalesced).  D[cout][frame] orientation, fragment layouts and padding are those of resblock.hip.
 #include <type_traits>
 #include "common.h"
+#include "rowlens.h"
 #include "tapring.h"
 #include <cstdlib>
 
@@ -201,8 +202,8 @@ struct PairArgs {
 #define TTSK_STAMP(i) do {} while (0)      // the product library carries no stamp code and no global state for it
 #endif
 
-template <bool F16>
-__global__ __launch_bounds__(C2_NT, 2) void conv_pair_kernel(const PairArgs a) {
+template <bool F16, typename A = PairArgs>
+__global__ __launch_bounds__(C2_NT, 2) void conv_pair_kernel(const A a) {
   constexpr int C = CW_C, TT = CP_TT, RS = CW_RS, NC = CW_NC, KS = CW_KS, NT = C2_NT, CH8 = C / 8, CT = C2_CT;
   constexpr int NF1 = CP_TROWS / 16, NF2 = TT / 16;
   __shared__ __attribute__((aligned(16))) unsigned char smem[CP_SMEM];
@@ -212,9 +213,13 @@ __global__ __launch_bounds__(C2_NT, 2) void conv_pair_kernel(const PairArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, q = lane >> 4;
   const int bi = blockIdx.y, t0 = blockIdx.x * TT;
-  const int len = a.len, K = a.K, d = a.dil;
+  const int slen = a.len, K = a.K, d = a.dil;      // slen: the batch's row stride; len: this row's edge (rowlens.h)
+  const int len = edge_len(a, bi);
+  if constexpr (HasRows<A>::value) {
+    if (t0 >= len) return;      // a tile wholly past the row's end: nothing to read, nothing to store (`out` is zero there)
+  }
   const int HK = (K - 1) / 2;
-  const bf16_t* __restrict__ xb = a.x + (int64_t)bi * len * C;
+  const bf16_t* __restrict__ xb = a.x + (int64_t)bi * slen * C;
 
   // The wave's 32 output channels, rows of the A operand PERMUTED (round 6, as csrc/pairws.hip): row l15 of tile cc is channel
   // 32 * wave + 8 * (l15 >> 2) + 4 * cc + (l15 & 3), so that a lane's 4 + 4 accumulator rows of the two tiles are 8 CONSECUTIVE channels of
@@ -350,7 +355,7 @@ __global__ __launch_bounds__(C2_NT, 2) void conv_pair_kernel(const PairArgs a) {
     rres[i] = rout[i] = make_uint4(0u, 0u, 0u, 0u);
     if (t < len) {
       rres[i] = *(const uint4*)(xb + (int64_t)t * C + co8);
-      if (a.mode) rout[i] = *(const uint4*)(a.out + ((int64_t)bi * len + t) * C + co8);
+      if (a.mode) rout[i] = *(const uint4*)(a.out + ((int64_t)bi * slen + t) * C + co8);
     }
   }
   // ---- c2 (dilation 1) over the tile's 96 frames; sequence taps K .. 2K-1: tap K is on set b, K+1 on set a, ...
@@ -385,7 +390,7 @@ __global__ __launch_bounds__(C2_NT, 2) void conv_pair_kernel(const PairArgs a) {
 
   TTSK_STAMP(5);
   // ---- epilogue: + b2 + raw x (+ the running sum), 16 bytes per frame tile and lane straight to memory
-  bf16_t* __restrict__ ob = a.out + (int64_t)bi * len * C;
+  bf16_t* __restrict__ ob = a.out + (int64_t)bi * slen * C;
 #pragma unroll
   for (int i = 0; i < NF2; ++i) {
     const int t = t0 + i * 16 + l15;
@@ -431,8 +436,8 @@ constexpr int C256_NC = C256 / 16, C256_KH = 4;                      // 16 cout 
 constexpr int C256_TAP = C256_NC * (C256 / 32) * 1024;               // 128 KiB per tap
 constexpr int C256_SMEM = (CP_XROWS + CP_TROWS) * C256_RS;           // 149,056 B
 
-template <bool F16>
-__global__ __launch_bounds__(C256_NT, 1) void conv_pair256_kernel(const PairArgs a) {
+template <bool F16, typename A = PairArgs>
+__global__ __launch_bounds__(C256_NT, 1) void conv_pair256_kernel(const A a) {
   constexpr int C = C256, TT = CP_TT, RS = C256_RS, NC = C256_NC, KH = C256_KH, NT = C256_NT, CH8 = C / 8, CT = 2;
   constexpr int NF1 = CP_TROWS / 16, NF2 = TT / 16;
   __shared__ __attribute__((aligned(16))) unsigned char smem[C256_SMEM];
@@ -442,9 +447,13 @@ __global__ __launch_bounds__(C256_NT, 1) void conv_pair256_kernel(const PairArgs
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, q = lane >> 4;
   const int bi = blockIdx.y, t0 = blockIdx.x * TT;
-  const int len = a.len, K = a.K, d = a.dil;
+  const int slen = a.len, K = a.K, d = a.dil;      // slen: the batch's row stride; len: this row's edge (rowlens.h)
+  const int len = edge_len(a, bi);
+  if constexpr (HasRows<A>::value) {
+    if (t0 >= len) return;      // a tile wholly past the row's end: nothing to read, nothing to store (`out` is zero there)
+  }
   const int HK = (K - 1) / 2, K2 = 2 * K;
-  const bf16_t* __restrict__ xb = a.x + (int64_t)bi * len * C;
+  const bf16_t* __restrict__ xb = a.x + (int64_t)bi * slen * C;
 
   // half-tap g of the sequence c1 (2K half-taps) | c2 (2K): tap (g mod 2K) / 2, channel half g & 1
   bf16x8 wa[KH][CT], wb[KH][CT];
@@ -586,7 +595,7 @@ __global__ __launch_bounds__(C256_NT, 1) void conv_pair256_kernel(const PairArgs
     }
   }
   // ---- epilogue: + b2 + raw x (+ the running sum), 16 bytes per frame tile and lane straight to memory (no staging tile, no barrier)
-  bf16_t* __restrict__ ob = a.out + (int64_t)bi * len * C;
+  bf16_t* __restrict__ ob = a.out + (int64_t)bi * slen * C;
 #pragma unroll
   for (int i = 0; i < NF2; ++i) {
     const int t = t0 + i * 16 + l15;
@@ -655,8 +664,8 @@ template <int C, int NW_> struct FsGeom {
   static constexpr int OCC = SMEM <= 80 * 1024 ? 2 : 1; // workgroups per CU the LDS allows (at most two are asked for)
 };
 
-template <int C, int NW, bool F16>
-__global__ __launch_bounds__(NW * 64, (FsGeom<C, NW>::OCC * NW) / 4) void conv_pair_fs_kernel(const PairArgs a) {
+template <int C, int NW, bool F16, typename A = PairArgs>
+__global__ __launch_bounds__(NW * 64, (FsGeom<C, NW>::OCC * NW) / 4) void conv_pair_fs_kernel(const A a) {
   using Gm = FsGeom<C, NW>;
   constexpr int NT = Gm::NT, FW = Gm::FW, NF = Gm::NF, GU = Gm::GU, TT = Gm::TT, XROWS = Gm::XROWS, RS = Gm::RS, NC = Gm::NC, KS = Gm::KS,
                 CH8 = Gm::CH8, TAP = Gm::TAP, XH = GU + 25, CG = Gm::CG, CT = NC / CG;
@@ -668,9 +677,13 @@ __global__ __launch_bounds__(NW * 64, (FsGeom<C, NW>::OCC * NW) / 4) void conv_p
   const int l15 = lane & 15, q = lane >> 4;
   const int cgi = wave % CG, fg = wave / CG;             // this wave's output-channel group and frame group
   const int bi = blockIdx.y, t0 = blockIdx.x * TT;
-  const int len = a.len, K = a.K, d = a.dil;
+  const int slen = a.len, K = a.K, d = a.dil;      // slen: the batch's row stride; len: this row's edge (rowlens.h)
+  const int len = edge_len(a, bi);
+  if constexpr (HasRows<A>::value) {
+    if (t0 >= len) return;      // a tile wholly past the row's end: nothing to read, nothing to store (`out` is zero there)
+  }
   const int HK = (K - 1) / 2;
-  const bf16_t* __restrict__ xb = a.x + (int64_t)bi * len * C;
+  const bf16_t* __restrict__ xb = a.x + (int64_t)bi * slen * C;
 
   bf16x8 wa[KS][CT], wb[KS][CT];
   auto load_w = [&](int g, bf16x8 (&w)[KS][CT]) __attribute__((always_inline)) {      // tap g of the 2K-tap sequence c1 | c2
@@ -772,7 +785,7 @@ __global__ __launch_bounds__(NW * 64, (FsGeom<C, NW>::OCC * NW) / 4) void conv_p
       rres[c][i] = rout[c][i] = make_uint2(0u, 0u);
       if (mine) {
         rres[c][i] = *(const uint2*)(xb + (int64_t)t * C + (cgi * CT + c) * 16 + q * 4);
-        if (a.mode) rout[c][i] = *(const uint2*)(a.out + ((int64_t)bi * len + t) * C + (cgi * CT + c) * 16 + q * 4);
+        if (a.mode) rout[c][i] = *(const uint2*)(a.out + ((int64_t)bi * slen + t) * C + (cgi * CT + c) * 16 + q * 4);
       }
     }
   }
@@ -820,7 +833,7 @@ __global__ __launch_bounds__(NW * 64, (FsGeom<C, NW>::OCC * NW) / 4) void conv_p
     }
   }
   __syncthreads();
-  bf16_t* __restrict__ ob = a.out + (int64_t)bi * len * C;
+  bf16_t* __restrict__ ob = a.out + (int64_t)bi * slen * C;
   constexpr int NCO = (TT * CH8 + NT - 1) / NT;
 #pragma unroll
   for (int it = 0; it < NCO; ++it) {
@@ -869,9 +882,32 @@ extern "C" int ttsk_hifi_conv_pair_supported(int C, int K, int dil) {
   return (C == CW_C || C == C256 || C == 64 || C == 32) && K >= 3 && K <= 11 && (K & 1) == 1 && dil >= 1 && dil * ((K - 1) / 2) <= CP_XH - CP_TH && (K - 1) / 2 <= CP_TH;
 }
 
-extern "C" int ttsk_hifi_conv_pair(const void* x16, const void* w1_pack, const float* bias1, const void* w2_pack, const float* bias2,
-                                   void* out16, int f16, int B, int len, int C, int K, int dil, float slope, int mode, float scale,
-                                   float final_slope, void* stream) {
+// one body for both entry points: `rl` null = the plain kernels (ttsk_hifi_conv_pair), else their WithRows instantiations
+template <typename A>
+static void launch_pair(const A& a, int f16, int B, int len, int C, hipStream_t s) {
+  if (C == C256) {
+    dim3 grid((len + CP_TT - 1) / CP_TT, B);
+    if (f16) hipLaunchKernelGGL((conv_pair256_kernel<true, A>), grid, dim3(C256_NT), 0, s, a);
+    else hipLaunchKernelGGL((conv_pair256_kernel<false, A>), grid, dim3(C256_NT), 0, s, a);
+  } else if (C == CW_C) {
+    dim3 grid((len + CP_TT - 1) / CP_TT, B);
+    if (f16) hipLaunchKernelGGL((conv_pair_kernel<true, A>), grid, dim3(C2_NT), 0, s, a);
+    else hipLaunchKernelGGL((conv_pair_kernel<false, A>), grid, dim3(C2_NT), 0, s, a);
+  } else {
+    dim3 grid((len + FsGeom<64, 4>::TT - 1) / FsGeom<64, 4>::TT, B);
+    if (C == 64) {
+      if (f16) hipLaunchKernelGGL((conv_pair_fs_kernel<64, 4, true, A>), grid, dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((conv_pair_fs_kernel<64, 4, false, A>), grid, dim3(256), 0, s, a);
+    } else {
+      if (f16) hipLaunchKernelGGL((conv_pair_fs_kernel<32, 4, true, A>), grid, dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((conv_pair_fs_kernel<32, 4, false, A>), grid, dim3(256), 0, s, a);
+    }
+  }
+}
+
+static int conv_pair_impl(const void* x16, const void* w1_pack, const float* bias1, const void* w2_pack, const float* bias2, void* out16,
+                          int f16, int B, int len, int C, int K, int dil, float slope, int mode, float scale, float final_slope,
+                          const RowLens* rl, void* stream) {
   TTSK_REQUIRE(x16 && w1_pack && bias1 && w2_pack && bias2 && out16, "ttsk_hifi_conv_pair: null pointer");
   TTSK_REQUIRE(B > 0 && len > 0 && B <= 65535 && x16 != out16, "ttsk_hifi_conv_pair: bad sizes / in-place output");
   TTSK_REQUIRE(ttsk_hifi_conv_pair_supported(C, K, dil), "ttsk_hifi_conv_pair: no instance for C=%d K=%d dil=%d", C, K, dil);
@@ -884,24 +920,28 @@ extern "C" int ttsk_hifi_conv_pair(const void* x16, const void* w1_pack, const f
 #ifdef TTSK_STAMPS
   a.stamps = g_pair_stamps;
 #endif
-  if (C == C256) {
-    dim3 grid((len + CP_TT - 1) / CP_TT, B);
-    if (f16) hipLaunchKernelGGL(conv_pair256_kernel<true>, grid, dim3(C256_NT), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(conv_pair256_kernel<false>, grid, dim3(C256_NT), 0, (hipStream_t)stream, a);
-  } else if (C == CW_C) {
-    dim3 grid((len + CP_TT - 1) / CP_TT, B);
-    if (f16) hipLaunchKernelGGL(conv_pair_kernel<true>, grid, dim3(C2_NT), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(conv_pair_kernel<false>, grid, dim3(C2_NT), 0, (hipStream_t)stream, a);
+  if (rl) {
+    WithRows<PairArgs> ar;
+    static_cast<PairArgs&>(ar) = a;
+    ar.rl = *rl;
+    launch_pair(ar, f16, B, len, C, (hipStream_t)stream);
   } else {
-    dim3 grid((len + FsGeom<64, 4>::TT - 1) / FsGeom<64, 4>::TT, B);
-    if (C == 64) {
-      if (f16) hipLaunchKernelGGL((conv_pair_fs_kernel<64, 4, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
-      else hipLaunchKernelGGL((conv_pair_fs_kernel<64, 4, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    } else {
-      if (f16) hipLaunchKernelGGL((conv_pair_fs_kernel<32, 4, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
-      else hipLaunchKernelGGL((conv_pair_fs_kernel<32, 4, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    }
+    launch_pair(a, f16, B, len, C, (hipStream_t)stream);
   }
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
+}
+
+extern "C" int ttsk_hifi_conv_pair(const void* x16, const void* w1_pack, const float* bias1, const void* w2_pack, const float* bias2,
+                                   void* out16, int f16, int B, int len, int C, int K, int dil, float slope, int mode, float scale,
+                                   float final_slope, void* stream) {
+  return conv_pair_impl(x16, w1_pack, bias1, w2_pack, bias2, out16, f16, B, len, C, K, dil, slope, mode, scale, final_slope, nullptr, stream);
+}
+
+extern "C" int ttsk_hifi_conv_pair_rowlen(const void* x16, const void* w1_pack, const float* bias1, const void* w2_pack, const float* bias2,
+                                        void* out16, int f16, int B, int len, int C, int K, int dil, float slope, int mode, float scale,
+                                        float final_slope, const int32_t* row_frames, int row_stride, int spf, void* stream) {
+  TTSK_REQUIRE_ROWS("ttsk_hifi_conv_pair_rowlen", row_stride, spf);
+  const RowLens rl{row_frames, row_stride, spf};
+  return conv_pair_impl(x16, w1_pack, bias1, w2_pack, bias2, out16, f16, B, len, C, K, dil, slope, mode, scale, final_slope, &rl, stream);
 }

@@ -18,6 +18,7 @@
 // Bit-identical to ttsk_hifi_resblock1 x 3 (modes 0 / 1 / 2) + ttsk_hifi_conv_post (tests/test_hifigan_gpu.py).
 #include <type_traits>
 #include "common.h"
+#include "rowlens.h"
 #include "conv_post.h"
 
 namespace {
@@ -47,8 +48,8 @@ struct MrfArgs {
   float slope, final_slope, scale;
 };
 
-template <int K0, int K1, int K2, bool F16>
-__global__ __launch_bounds__(M_NT, 1) void mrf32_post_kernel(const MrfArgs a) {
+template <int K0, int K1, int K2, bool F16, typename A = MrfArgs>
+__global__ __launch_bounds__(M_NT, 1) void mrf32_post_kernel(const A a) {
   constexpr int C = M_C, NT = M_NT, NW = M_NW, NTILE = M_NTILE, NSLOT = M_NSLOT, G = M_G, LROWS = M_LROWS, RS = M_RS, NC = M_NC,
                 CH8 = M_CH8, NLD = M_NLD, WSTAGE = M_WSTAGE, HP = M_HP, TT = M_TT, NCONV = 18;
   static_assert(K0 <= M_KMAX && K1 <= M_KMAX && K2 <= M_KMAX && 5 * ((M_KMAX - 1) / 2) <= M_G, "tap reach exceeds the guard rows");
@@ -61,8 +62,12 @@ __global__ __launch_bounds__(M_NT, 1) void mrf32_post_kernel(const MrfArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, q = lane >> 4;
   const int bi = blockIdx.y, t0 = blockIdx.x * TT;
-  const int len = a.len;
-  const bf16_t* __restrict__ xb = a.x + (int64_t)bi * len * C;
+  const int slen = a.len;             // the batch's row stride; len: this row's edge (rowlens.h)
+  const int len = edge_len(a, bi);
+  if constexpr (HasRows<A>::value) {
+    if (t0 >= len) return;            // a tile wholly past the row's end: its samples belong to no utterance and are not written
+  }
+  const bf16_t* __restrict__ xb = a.x + (int64_t)bi * slen * C;
   const float slope = a.slope;
   auto swz = [](int row) __attribute__((always_inline)) { return (row >> 1) & 3; };
 
@@ -305,7 +310,7 @@ __global__ __launch_bounds__(M_NT, 1) void mrf32_post_kernel(const MrfArgs a) {
   // ---- XL rows [60, 452) hold lrelu(mean, 0.01) for frames t0 - 3 .. t0 + 389 (zero outside the utterance): conv_post + tanh, one
   //      output sample per thread, in ttsk_hifi_conv_post's summation order
   if (a.stage_out) {
-    bf16_t* __restrict__ ob = a.stage_out + (int64_t)bi * len * C;
+    bf16_t* __restrict__ ob = a.stage_out + (int64_t)bi * slen * C;
     for (int idx = tid; idx < TT * CH8; idx += NT) {
       const int rr = idx / CH8, ch = idx - rr * CH8;
       const int t = t0 + rr, row = rr + HP + G;
@@ -326,7 +331,7 @@ __global__ __launch_bounds__(M_NT, 1) void mrf32_post_kernel(const MrfArgs a) {
         accp += conv_post_dot8<F16>(v, wj + ch * 8);
       }
     }
-    a.out[(int64_t)bi * len + t0 + tid] = tanhf(accp);
+    a.out[(int64_t)bi * slen + t0 + tid] = tanhf(accp);
   }
 }
 
@@ -336,10 +341,10 @@ extern "C" int ttsk_hifi_mrf32_post_supported(int C, int k0, int k1, int k2, int
   return C == 32 && k0 == 3 && k1 == 7 && k2 == 11 && k_post == M_KP;
 }
 
-extern "C" int ttsk_hifi_mrf32_post(const void* x16, float* out, void* stage_out16, int f16, const void* const* weights /* 18 packs */,
-                                    const float* const* biases /* 18 x [32] */, const int32_t* dilations /* 3 x 3 */,
-                                    const void* w_post16, const float* b_post, int B, int len, int C, int k0, int k1, int k2, int k_post,
-                                    float slope, float final_slope, float scale, void* stream) {
+static int mrf32_post_impl(const void* x16, float* out, void* stage_out16, int f16, const void* const* weights /* 18 packs */,
+                           const float* const* biases /* 18 x [32] */, const int32_t* dilations /* 3 x 3 */,
+                           const void* w_post16, const float* b_post, int B, int len, int C, int k0, int k1, int k2, int k_post,
+                           float slope, float final_slope, float scale, const RowLens* rl, void* stream) {
   TTSK_REQUIRE(x16 && out && weights && biases && dilations && w_post16 && b_post, "ttsk_hifi_mrf32_post: null pointer");
   TTSK_REQUIRE(ttsk_hifi_mrf32_post_supported(C, k0, k1, k2, k_post),
                "ttsk_hifi_mrf32_post: built for C = 32, resblock kernel sizes (3, 7, 11), conv_post k = 7 (got C=%d, k=(%d,%d,%d), post %d)", C, k0, k1,
@@ -364,8 +369,33 @@ extern "C" int ttsk_hifi_mrf32_post(const void* x16, float* out, void* stage_out
   a.wpost = (const bf16_t*)w_post16; a.bpost = b_post;
   a.len = len; a.slope = slope; a.final_slope = final_slope; a.scale = scale;
   dim3 grid((len + M_TT - 1) / M_TT, B);
-  if (f16) hipLaunchKernelGGL((mrf32_post_kernel<3, 7, 11, true>), grid, dim3(M_NT), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((mrf32_post_kernel<3, 7, 11, false>), grid, dim3(M_NT), 0, (hipStream_t)stream, a);
+  if (rl) {
+    WithRows<MrfArgs> ar;
+    static_cast<MrfArgs&>(ar) = a;
+    ar.rl = *rl;
+    if (f16) hipLaunchKernelGGL((mrf32_post_kernel<3, 7, 11, true, WithRows<MrfArgs>>), grid, dim3(M_NT), 0, (hipStream_t)stream, ar);
+    else hipLaunchKernelGGL((mrf32_post_kernel<3, 7, 11, false, WithRows<MrfArgs>>), grid, dim3(M_NT), 0, (hipStream_t)stream, ar);
+  } else {
+    if (f16) hipLaunchKernelGGL((mrf32_post_kernel<3, 7, 11, true>), grid, dim3(M_NT), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((mrf32_post_kernel<3, 7, 11, false>), grid, dim3(M_NT), 0, (hipStream_t)stream, a);
+  }
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
+}
+
+extern "C" int ttsk_hifi_mrf32_post(const void* x16, float* out, void* stage_out16, int f16, const void* const* weights, const float* const* biases,
+                                    const int32_t* dilations, const void* w_post16, const float* b_post, int B, int len, int C, int k0, int k1,
+                                    int k2, int k_post, float slope, float final_slope, float scale, void* stream) {
+  return mrf32_post_impl(x16, out, stage_out16, f16, weights, biases, dilations, w_post16, b_post, B, len, C, k0, k1, k2, k_post, slope,
+                         final_slope, scale, nullptr, stream);
+}
+
+extern "C" int ttsk_hifi_mrf32_post_rowlen(const void* x16, float* out, void* stage_out16, int f16, const void* const* weights,
+                                         const float* const* biases, const int32_t* dilations, const void* w_post16, const float* b_post, int B,
+                                         int len, int C, int k0, int k1, int k2, int k_post, float slope, float final_slope, float scale,
+                                         const int32_t* row_frames, int row_stride, int spf, void* stream) {
+  TTSK_REQUIRE_ROWS("ttsk_hifi_mrf32_post_rowlen", row_stride, spf);
+  const RowLens rl{row_frames, row_stride, spf};
+  return mrf32_post_impl(x16, out, stage_out16, f16, weights, biases, dilations, w_post16, b_post, B, len, C, k0, k1, k2, k_post, slope,
+                         final_slope, scale, &rl, stream);
 }

@@ -21,6 +21,7 @@
 // Same fp16 / bf16 roundings, same MFMA shape and the same (tap, k-step) accumulation order as ttsk_hifi_conv_pair: bit-identical.
 #include <type_traits>
 #include "common.h"
+#include "rowlens.h"
 #include "gemm_common.h"      // dma16: buffer_load_dwordx4 ... lds from inline asm
 
 namespace {
@@ -80,8 +81,8 @@ constexpr int ws_tile_frames(int C) { return C == 64 ? 192 : 96; }
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int WS_PAD = 0x7F000000;                     // a buffer offset past every utterance (< 2^30 bytes each): such a load returns 0, such a store is dropped
 
-template <int C, int K, int D, int MODE, bool F16>
-__global__ __launch_bounds__(512, 2) void pair_ws_kernel(const WsArgs a) {
+template <int C, int K, int D, int MODE, bool F16, typename A = WsArgs>
+__global__ __launch_bounds__(512, 2) void pair_ws_kernel(const A a) {
   using G = WsGeom<C, K, D>;
   constexpr int HK = G::HK, RS = G::RS, XROWS = G::XROWS, NPIECE = G::NPIECE, PPW = G::PPW, DR = G::DR, NFR = G::NFR, KS = G::KS, NCG = G::NCG,
                 TT = G::TT, NT1 = G::NT1, R1 = G::R1, T1A = G::T1A, T2 = G::T2;
@@ -98,7 +99,13 @@ __global__ __launch_bounds__(512, 2) void pair_ws_kernel(const WsArgs a) {
   // utterance is an offset outside the buffer — the load returns 0 (the convs' zero padding), the store is dropped — with no compare, no
   // select and no branch.  Branches would cut the tile loops into basic blocks the instruction scheduler cannot move MFMAs and LDS reads
   // across, and the address arithmetic of a masked access costs as many VALU slots as the MFMAs leave free.
+  // (WithRows: the buffer of row bi ends at that row's own edge, rowlens.h — the same zeros and drops, nearer)
   const unsigned ubytes = (unsigned)len * (C * 2);
+  auto row_len = [&](int bi) __attribute__((always_inline)) { return edge_len(a, bi); };
+  auto row_bytes = [&](int bi) __attribute__((always_inline)) {
+    if constexpr (HasRows<A>::value) return (unsigned)row_len(bi) * (C * 2);
+    else return ubytes;
+  };
   auto utt_rsrc = [&](const bf16_t* base, int bi, unsigned bytes) __attribute__((always_inline)) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base) + (int64_t)bi * len * C, 0, bytes, 0x00020000);
   };
@@ -146,7 +153,7 @@ __global__ __launch_bounds__(512, 2) void pair_ws_kernel(const WsArgs a) {
   auto win_request = [&](int tau, unsigned xw_lds) __attribute__((always_inline)) {
     int bi, t0;
     tile_pos(tau, bi, t0);
-    const __amdgpu_buffer_rsrc_t rxu = utt_rsrc(a.x, bi, ubytes);
+    const __amdgpu_buffer_rsrc_t rxu = utt_rsrc(a.x, bi, row_bytes(bi));
     const int lo = (t0 - HK - HK * D) * (C * 2);
 #pragma unroll
     for (int j = 0; j < PPW; ++j)
@@ -225,8 +232,8 @@ __global__ __launch_bounds__(512, 2) void pair_ws_kernel(const WsArgs a) {
     int bi, t0;
     tile_pos(tau, bi, t0);
     const int off = lc2 + (t0 + (i0c + j) * 16) * (C * 2);      // (rows behind the utterance: outside the buffer)
-    rres[slot] = __builtin_amdgcn_raw_buffer_load_b128(utt_rsrc(a.x, bi, ubytes), off, 0, 0);
-    if (MODE) rout[slot] = __builtin_amdgcn_raw_buffer_load_b128(utt_rsrc(a.out, bi, ubytes), off, 0, 0);
+    rres[slot] = __builtin_amdgcn_raw_buffer_load_b128(utt_rsrc(a.x, bi, row_bytes(bi)), off, 0, 0);
+    if (MODE) rout[slot] = __builtin_amdgcn_raw_buffer_load_b128(utt_rsrc(a.out, bi, row_bytes(bi)), off, 0, 0);
   };
 
 #pragma unroll 1
@@ -243,7 +250,8 @@ __global__ __launch_bounds__(512, 2) void pair_ws_kernel(const WsArgs a) {
         const unsigned char* XWb = XW0 + (s & 1) * G::XBYTES + l15 * RS + q * 16;
         unsigned char* TWb = TW0 + (s & 1) * G::TBYTES + l15 * RS + ch * 64 + q * 16;
         const int i0 = fh ? T1A : 0, i1 = (fh || G::NFG == 1) ? NT1 : T1A;
-        const bool edge = t0 - HK < 0 || t0 - HK + R1 > len;      // the tile touches an end of the utterance: t is zero outside it (c2's padding)
+        const int rlen = row_len(bi);
+        const bool edge = t0 - HK < 0 || t0 - HK + R1 > rlen;      // the tile touches an end of the utterance: t is zero outside it (c2's padding)
         WS_TSTAMP(0);
         ring_prime(DilC1{}, XWb + i0 * 16 * RS);
         auto c1_tile = [&](auto rotc, int i) __attribute__((always_inline)) {
@@ -260,7 +268,7 @@ __global__ __launch_bounds__(512, 2) void pair_ws_kernel(const WsArgs a) {
           }
           if (edge) {
             const int t = t0 - HK + i * 16 + l15;
-            if (t < 0 || t >= len) o[0] = o[1] = o[2] = o[3] = 0u;
+            if (t < 0 || t >= rlen) o[0] = o[1] = o[2] = o[3] = 0u;
           }
           *(uint4*)(TWb + i * 16 * RS) = make_uint4(o[0], o[1], o[2], o[3]);
           WS_TSTAMP(1 + i - i0);
@@ -284,7 +292,7 @@ __global__ __launch_bounds__(512, 2) void pair_ws_kernel(const WsArgs a) {
       } else {
         int bi, t0;
         tile_pos(tau0 + s - 1, bi, t0);
-        const __amdgpu_buffer_rsrc_t rou = utt_rsrc(a.out, bi, ubytes);
+        const __amdgpu_buffer_rsrc_t rou = utt_rsrc(a.out, bi, row_bytes(bi));
         const int off0 = lc2 + (t0 + i0c * 16) * (C * 2);
         const unsigned char* TWb = TW0 + ((s - 1) & 1) * G::TBYTES + l15 * RS + q * 16;
         WS_TSTAMP(0);
@@ -327,17 +335,35 @@ __global__ __launch_bounds__(512, 2) void pair_ws_kernel(const WsArgs a) {
   }
 }
 
-template <int C, int K, int D>
-void launch_ws(const WsArgs& a, int f16, int grid, hipStream_t s) {
+template <int C, int K, int D, typename A>
+void launch_ws(const A& a, int f16, int grid, hipStream_t s) {
   dim3 g(grid), b(512);
   if (f16) {
-    if (a.mode == 0) hipLaunchKernelGGL((pair_ws_kernel<C, K, D, 0, true>), g, b, 0, s, a);
-    else if (a.mode == 1) hipLaunchKernelGGL((pair_ws_kernel<C, K, D, 1, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((pair_ws_kernel<C, K, D, 2, true>), g, b, 0, s, a);
+    if (a.mode == 0) hipLaunchKernelGGL((pair_ws_kernel<C, K, D, 0, true, A>), g, b, 0, s, a);
+    else if (a.mode == 1) hipLaunchKernelGGL((pair_ws_kernel<C, K, D, 1, true, A>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((pair_ws_kernel<C, K, D, 2, true, A>), g, b, 0, s, a);
   } else {
-    if (a.mode == 0) hipLaunchKernelGGL((pair_ws_kernel<C, K, D, 0, false>), g, b, 0, s, a);
-    else if (a.mode == 1) hipLaunchKernelGGL((pair_ws_kernel<C, K, D, 1, false>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((pair_ws_kernel<C, K, D, 2, false>), g, b, 0, s, a);
+    if (a.mode == 0) hipLaunchKernelGGL((pair_ws_kernel<C, K, D, 0, false, A>), g, b, 0, s, a);
+    else if (a.mode == 1) hipLaunchKernelGGL((pair_ws_kernel<C, K, D, 1, false, A>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((pair_ws_kernel<C, K, D, 2, false, A>), g, b, 0, s, a);
+  }
+}
+
+template <typename A>
+void dispatch_ws(const A& a, int f16, int grid, int C, int K, int dil, hipStream_t s) {
+  switch ((C == 128 ? 1000 : 0) + K * 10 + dil) {
+    case 31: launch_ws<64, 3, 1>(a, f16, grid, s); break;
+    case 33: launch_ws<64, 3, 3>(a, f16, grid, s); break;
+    case 35: launch_ws<64, 3, 5>(a, f16, grid, s); break;
+    case 71: launch_ws<64, 7, 1>(a, f16, grid, s); break;
+    case 73: launch_ws<64, 7, 3>(a, f16, grid, s); break;
+    case 75: launch_ws<64, 7, 5>(a, f16, grid, s); break;
+    case 111: launch_ws<64, 11, 1>(a, f16, grid, s); break;
+    case 113: launch_ws<64, 11, 3>(a, f16, grid, s); break;
+    case 115: launch_ws<64, 11, 5>(a, f16, grid, s); break;
+    case 1031: launch_ws<128, 3, 1>(a, f16, grid, s); break;
+    case 1033: launch_ws<128, 3, 3>(a, f16, grid, s); break;
+    default: launch_ws<128, 3, 5>(a, f16, grid, s); break;
   }
 }
 
@@ -356,9 +382,9 @@ extern "C" int ttsk_hifi_conv_pair_ws_supported(int C, int K, int dil) {
   return ((C == 64 && (K == 3 || K == 7 || K == 11)) || (C == 128 && K == 3)) && (dil == 1 || dil == 3 || dil == 5);
 }
 
-extern "C" int ttsk_hifi_conv_pair_ws(const void* x16, const void* w1_pack, const float* bias1, const void* w2_pack, const float* bias2,
-                                      void* out16, int f16, int B, int len, int C, int K, int dil, float slope, int mode, float scale,
-                                      float final_slope, int max_wgs, void* stream) {
+static int conv_pair_ws_impl(const void* x16, const void* w1_pack, const float* bias1, const void* w2_pack, const float* bias2,
+                             void* out16, int f16, int B, int len, int C, int K, int dil, float slope, int mode, float scale,
+                             float final_slope, int max_wgs, const RowLens* rl, void* stream) {
   TTSK_REQUIRE(x16 && w1_pack && bias1 && w2_pack && bias2 && out16, "ttsk_hifi_conv_pair_ws: null pointer");
   TTSK_REQUIRE(B > 0 && len > 0 && B <= 65535 && x16 != out16, "ttsk_hifi_conv_pair_ws: bad sizes / in-place output");
   TTSK_REQUIRE(ttsk_hifi_conv_pair_ws_supported(C, K, dil), "ttsk_hifi_conv_pair_ws: no instance for C=%d K=%d dil=%d", C, K, dil);
@@ -378,20 +404,30 @@ extern "C" int ttsk_hifi_conv_pair_ws(const void* x16, const void* w1_pack, cons
   int grid = max_wgs > 0 ? max_wgs : 256;        // one persistent workgroup per CU
   if (grid > n_tiles) grid = (int)n_tiles;
   hipStream_t s = (hipStream_t)stream;
-  switch ((C == 128 ? 1000 : 0) + K * 10 + dil) {
-    case 31: launch_ws<64, 3, 1>(a, f16, grid, s); break;
-    case 33: launch_ws<64, 3, 3>(a, f16, grid, s); break;
-    case 35: launch_ws<64, 3, 5>(a, f16, grid, s); break;
-    case 71: launch_ws<64, 7, 1>(a, f16, grid, s); break;
-    case 73: launch_ws<64, 7, 3>(a, f16, grid, s); break;
-    case 75: launch_ws<64, 7, 5>(a, f16, grid, s); break;
-    case 111: launch_ws<64, 11, 1>(a, f16, grid, s); break;
-    case 113: launch_ws<64, 11, 3>(a, f16, grid, s); break;
-    case 115: launch_ws<64, 11, 5>(a, f16, grid, s); break;
-    case 1031: launch_ws<128, 3, 1>(a, f16, grid, s); break;
-    case 1033: launch_ws<128, 3, 3>(a, f16, grid, s); break;
-    default: launch_ws<128, 3, 5>(a, f16, grid, s); break;
+  if (rl) {
+    WithRows<WsArgs> ar;
+    static_cast<WsArgs&>(ar) = a;
+    ar.rl = *rl;
+    dispatch_ws(ar, f16, grid, C, K, dil, s);
+  } else {
+    dispatch_ws(a, f16, grid, C, K, dil, s);
   }
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
+}
+
+extern "C" int ttsk_hifi_conv_pair_ws(const void* x16, const void* w1_pack, const float* bias1, const void* w2_pack, const float* bias2,
+                                      void* out16, int f16, int B, int len, int C, int K, int dil, float slope, int mode, float scale,
+                                      float final_slope, int max_wgs, void* stream) {
+  return conv_pair_ws_impl(x16, w1_pack, bias1, w2_pack, bias2, out16, f16, B, len, C, K, dil, slope, mode, scale, final_slope, max_wgs, nullptr,
+                           stream);
+}
+
+extern "C" int ttsk_hifi_conv_pair_ws_rowlen(const void* x16, const void* w1_pack, const float* bias1, const void* w2_pack, const float* bias2,
+                                           void* out16, int f16, int B, int len, int C, int K, int dil, float slope, int mode, float scale,
+                                           float final_slope, int max_wgs, const int32_t* row_frames, int row_stride, int spf, void* stream) {
+  TTSK_REQUIRE_ROWS("ttsk_hifi_conv_pair_ws_rowlen", row_stride, spf);
+  const RowLens rl{row_frames, row_stride, spf};
+  return conv_pair_ws_impl(x16, w1_pack, bias1, w2_pack, bias2, out16, f16, B, len, C, K, dil, slope, mode, scale, final_slope, max_wgs, &rl,
+                           stream);
 }

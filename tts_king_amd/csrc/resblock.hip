@@ -26,6 +26,7 @@
 // latency and epilogue with the other's MFMAs.
 #include <type_traits>
 #include "common.h"
+#include "rowlens.h"
 
 namespace {
 
@@ -64,8 +65,8 @@ struct RbGeom {
   static constexpr int SMEM = ACT + 2 * WSTAGE;
 };
 
-template <int C, int K, int TT, int NW, bool F16>
-__global__ __launch_bounds__(NW * 64, 1) void resblock1_kernel(const RbArgs a) {
+template <int C, int K, int TT, int NW, bool F16, typename A = RbArgs>
+__global__ __launch_bounds__(NW * 64, 1) void resblock1_kernel(const A a) {
   using Gm = RbGeom<C, K, TT, NW>;
   constexpr int NT = Gm::NT;
   constexpr int HK = Gm::HK, H = Gm::H, NTILE = Gm::NTILE, NSLOT = Gm::NSLOT, G = Gm::G, LROWS = Gm::LROWS, RS = Gm::RS,
@@ -80,8 +81,12 @@ __global__ __launch_bounds__(NW * 64, 1) void resblock1_kernel(const RbArgs a) {
   const int l15 = lane & 15, q = lane >> 4;
   const int bi = blockIdx.y;
   const int t0 = blockIdx.x * TT;
-  const int len = a.len;
-  const bf16_t* __restrict__ xb = a.x + (int64_t)bi * len * C;
+  const int slen = a.len;             // the batch's row stride; len: this row's edge (rowlens.h)
+  const int len = edge_len(a, bi);
+  if constexpr (HasRows<A>::value) {
+    if (t0 >= len) return;            // a tile wholly past the row's end: nothing to read, nothing to store (`out` is zero there)
+  }
+  const bf16_t* __restrict__ xb = a.x + (int64_t)bi * slen * C;
   const float slope = a.slope;
   // chunk swizzle of the activation rows: conflict-free ds_read_b128 fragments for any tap shift (C = 64: 8 chunks per
   // row, ^ row & 7; C = 32: 4 chunks per row, ^ (row >> 1) & 3); tile bases and the guard are multiples of 8 rows
@@ -258,7 +263,7 @@ __global__ __launch_bounds__(NW * 64, 1) void resblock1_kernel(const RbArgs a) {
   }
 
   // ---- XL rows [H, H+TT) now hold the block output: coalesced 16-byte copy-out (+ MRF sum / average / activation)
-  bf16_t* __restrict__ ob = a.out + (int64_t)bi * len * C;
+  bf16_t* __restrict__ ob = a.out + (int64_t)bi * slen * C;
   const float fsl = a.final_slope;
   constexpr int NCO = (TT * CH8 + NT - 1) / NT;
   uint4 prev[NCO];
@@ -320,12 +325,28 @@ int rb_kpad(int C, int K) {
   return (K + gt - 1) / gt * gt;
 }
 
-template <int C, int K, int TT, int NW>
-int launch_rb(const RbArgs& a, int B, int f16, hipStream_t s) {
+template <int C, int K, int TT, int NW, typename A>
+int launch_rb(const A& a, int B, int f16, hipStream_t s) {
   dim3 grid((a.len + TT - 1) / TT, B);
-  if (f16) hipLaunchKernelGGL((resblock1_kernel<C, K, TT, NW, true>), grid, dim3(NW * 64), 0, s, a);
-  else hipLaunchKernelGGL((resblock1_kernel<C, K, TT, NW, false>), grid, dim3(NW * 64), 0, s, a);
+  if (f16) hipLaunchKernelGGL((resblock1_kernel<C, K, TT, NW, true, A>), grid, dim3(NW * 64), 0, s, a);
+  else hipLaunchKernelGGL((resblock1_kernel<C, K, TT, NW, false, A>), grid, dim3(NW * 64), 0, s, a);
   return 0;
+}
+
+// C = 64: TT = 3 frame tiles per wave * 8 waves * 16 - 2 * halo, so every multiplied tile is a needed one (384 rows,
+// 147 KB of LDS; K = 11: 494 -> 401 us against TT = 128, whose 248-row tile multiplied 256).  C = 32 measured slower
+// with exact-fit tiles (360 / 568 / 520: 111 / 151 / 188 us against 82 / 137 / 176) and keeps the power-of-two ones.
+template <typename A>
+bool dispatch_rb(const A& a, int B, int f16, int C, int K, hipStream_t s) {
+  switch (C * 100 + K) {
+    case 3203: launch_rb<32, 3, 256, 8>(a, B, f16, s); return true;
+    case 3207: launch_rb<32, 7, 512, 8>(a, B, f16, s); return true;
+    case 3211: launch_rb<32, 11, 512, 8>(a, B, f16, s); return true;
+    case 6403: launch_rb<64, 3, 360, 8>(a, B, f16, s); return true;
+    case 6407: launch_rb<64, 7, 312, 8>(a, B, f16, s); return true;
+    case 6411: launch_rb<64, 11, 264, 8>(a, B, f16, s); return true;
+    default: return false;
+  }
 }
 
 }  // namespace
@@ -344,9 +365,9 @@ extern "C" int ttsk_pack_resblock_weight(const float* src, void* dst16, int f16,
   return TTSK_OK;
 }
 
-extern "C" int ttsk_hifi_resblock1(const void* x16, void* out16, int f16, const void* const* weights /* 6 fragment-major packs */,
-                                   const float* const* biases /* 6 x [C] */, const int32_t* dilations /* 3 */, int B, int len,
-                                   int C, int K, int mode, float scale, float slope, float final_slope, void* stream) {
+static int resblock1_impl(const void* x16, void* out16, int f16, const void* const* weights /* 6 fragment-major packs */,
+                          const float* const* biases /* 6 x [C] */, const int32_t* dilations /* 3 */, int B, int len,
+                          int C, int K, int mode, float scale, float slope, float final_slope, const RowLens* rl, void* stream) {
   TTSK_REQUIRE(x16 && out16 && weights && biases && dilations, "ttsk_hifi_resblock1: null pointer");
   TTSK_REQUIRE(B > 0 && len > 0 && B <= 65535, "ttsk_hifi_resblock1: bad sizes B=%d len=%d", B, len);
   TTSK_REQUIRE(mode >= 0 && mode <= 2, "ttsk_hifi_resblock1: mode");
@@ -367,23 +388,35 @@ extern "C" int ttsk_hifi_resblock1(const void* x16, void* out16, int f16, const 
   for (int i = 0; i < 3; ++i) a.dil[i] = dilations[i];
   a.len = len; a.mode = mode; a.scale = scale; a.slope = slope; a.final_slope = final_slope;
   hipStream_t s = (hipStream_t)stream;
-  const int key = C * 100 + K;
-  switch (key) {
-    // C = 64: TT = 3 frame tiles per wave * 8 waves * 16 - 2 * halo, so every multiplied tile is a needed one (384 rows,
-    // 147 KB of LDS; K = 11: 494 -> 401 us against TT = 128, whose 248-row tile multiplied 256).  C = 32 measured slower
-    // with exact-fit tiles (360 / 568 / 520: 111 / 151 / 188 us against 82 / 137 / 176) and keeps the power-of-two ones.
-    case 3203: launch_rb<32, 3, 256, 8>(a, B, f16, s); break;
-    case 3207: launch_rb<32, 7, 512, 8>(a, B, f16, s); break;
-    case 3211: launch_rb<32, 11, 512, 8>(a, B, f16, s); break;
-    case 6403: launch_rb<64, 3, 360, 8>(a, B, f16, s); break;
-    case 6407: launch_rb<64, 7, 312, 8>(a, B, f16, s); break;
-    case 6411: launch_rb<64, 11, 264, 8>(a, B, f16, s); break;
-    default:
-      ttsk_set_error("ttsk_hifi_resblock1: no fused instance for C=%d K=%d (C in {32,64}, K in {3,7,11})", C, K);
-      return TTSK_EINVAL;
+  bool found;
+  if (rl) {
+    WithRows<RbArgs> ar;
+    static_cast<RbArgs&>(ar) = a;
+    ar.rl = *rl;
+    found = dispatch_rb(ar, B, f16, C, K, s);
+  } else {
+    found = dispatch_rb(a, B, f16, C, K, s);
+  }
+  if (!found) {
+    ttsk_set_error("ttsk_hifi_resblock1: no fused instance for C=%d K=%d (C in {32,64}, K in {3,7,11})", C, K);
+    return TTSK_EINVAL;
   }
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
+}
+
+extern "C" int ttsk_hifi_resblock1(const void* x16, void* out16, int f16, const void* const* weights, const float* const* biases,
+                                   const int32_t* dilations, int B, int len, int C, int K, int mode, float scale, float slope,
+                                   float final_slope, void* stream) {
+  return resblock1_impl(x16, out16, f16, weights, biases, dilations, B, len, C, K, mode, scale, slope, final_slope, nullptr, stream);
+}
+
+extern "C" int ttsk_hifi_resblock1_rowlen(const void* x16, void* out16, int f16, const void* const* weights, const float* const* biases,
+                                        const int32_t* dilations, int B, int len, int C, int K, int mode, float scale, float slope,
+                                        float final_slope, const int32_t* row_frames, int row_stride, int spf, void* stream) {
+  TTSK_REQUIRE_ROWS("ttsk_hifi_resblock1_rowlen", row_stride, spf);
+  const RowLens rl{row_frames, row_stride, spf};
+  return resblock1_impl(x16, out16, f16, weights, biases, dilations, B, len, C, K, mode, scale, slope, final_slope, &rl, stream);
 }
 
 extern "C" int ttsk_hifi_resblock1_supported(int C, int K) {

@@ -13,6 +13,7 @@
 // C = 128: 4 cout groups x 96 frames (64 at the widest halo); C = 64: 2 x 2 x 96 frames; C = 32: 1 x 4 x 48 frames.  conv0 computes EW extra frame tiles
 // per wave (the conv1 halo, G1 = 8 * FG * EW frames either side); an instance is picked per (C, EW) from the halo HK * d1.
 #include "common.h"
+#include "rowlens.h"
 
 namespace {
 
@@ -51,8 +52,8 @@ template <int C, int EW> struct Rb2Geom {
   static_assert(SMEM <= 80 * 1024, "two workgroups per CU");
 };
 
-template <int C, int EW, bool F16>
-__global__ __launch_bounds__(256, 2) void resblock2_kernel(const Rb2Args a) {
+template <int C, int EW, bool F16, typename A = Rb2Args>
+__global__ __launch_bounds__(256, 2) void resblock2_kernel(const A a) {
   using Gm = Rb2Geom<C, EW>;
   constexpr int NT = Gm::NT, NF1 = Gm::NF1, NF2 = Gm::NF2, TT = Gm::TT, G1 = Gm::G1, TROWS = Gm::TROWS, XROWS = Gm::XROWS,
                 RS = Gm::RS, NC = Gm::NC, KS = Gm::KS, CH8 = Gm::CH8, CT = Gm::CT, CG = Gm::CG, TAP = Gm::TAP, H0M = RB2_H0;
@@ -65,9 +66,13 @@ __global__ __launch_bounds__(256, 2) void resblock2_kernel(const Rb2Args a) {
   const int l15 = lane & 15, q = lane >> 4;
   const int cgi = wave % CG, fg = wave / CG;
   const int bi = blockIdx.y, t0 = blockIdx.x * TT;
-  const int len = a.len, K = a.K, d0 = a.d0, d1 = a.d1;
+  const int slen = a.len, K = a.K, d0 = a.d0, d1 = a.d1;      // slen: the batch's row stride; len: this row's edge (rowlens.h)
+  const int len = edge_len(a, bi);
+  if constexpr (HasRows<A>::value) {
+    if (t0 >= len) return;      // a tile wholly past the row's end: nothing to read, nothing to store (`out` is zero there)
+  }
   const int HK = (K - 1) / 2;
-  const bf16_t* __restrict__ xb = a.x + (int64_t)bi * len * C;
+  const bf16_t* __restrict__ xb = a.x + (int64_t)bi * slen * C;
 
   bf16x8 wa[KS][CT], wb[KS][CT];
   auto load_w = [&](int g, bf16x8 (&w)[KS][CT]) __attribute__((always_inline)) {      // tap g of the 2K-tap sequence conv0 | conv1
@@ -181,7 +186,7 @@ __global__ __launch_bounds__(256, 2) void resblock2_kernel(const Rb2Args a) {
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
       rout[c][j] = make_uint2(0u, 0u);
-      if (a.mode && t < len) rout[c][j] = *(const uint2*)(a.out + ((int64_t)bi * len + t) * C + (cgi * CT + c) * 16 + q * 4);
+      if (a.mode && t < len) rout[c][j] = *(const uint2*)(a.out + ((int64_t)bi * slen + t) * C + (cgi * CT + c) * 16 + q * 4);
     }
   }
   // ---- conv1: output frame f = fg * NF2 * 16 + j * 16 + l15 <-> lrelu(x1) row f + G1; taps K .. 2K-1 of the sequence
@@ -247,7 +252,7 @@ __global__ __launch_bounds__(256, 2) void resblock2_kernel(const Rb2Args a) {
     }
   }
   __syncthreads();
-  bf16_t* __restrict__ ob = a.out + (int64_t)bi * len * C;
+  bf16_t* __restrict__ ob = a.out + (int64_t)bi * slen * C;
   constexpr int NCO = (TT * CH8 + NT - 1) / NT;
 #pragma unroll
   for (int it = 0; it < NCO; ++it) {
@@ -261,36 +266,16 @@ __global__ __launch_bounds__(256, 2) void resblock2_kernel(const Rb2Args a) {
 // conv1 halo G1 = 8 * FG * EW of each instance: C = 128 (FG = 1): 8 / 16 / 40; C = 64 (FG = 2): 16 / 48; C = 32 (FG = 4): 32 / 64
 int rb2_max_h1(int C) { return C == 128 ? 40 : (C == 64 ? 48 : 64); }
 
-template <int C, int EW>
-void launch_rb2(const Rb2Args& a, int B, int f16, hipStream_t s) {
+template <int C, int EW, typename A>
+void launch_rb2(const A& a, int B, int f16, hipStream_t s) {
   using Gm = Rb2Geom<C, EW>;
   dim3 grid((a.len + Gm::TT - 1) / Gm::TT, B);
-  if (f16) hipLaunchKernelGGL((resblock2_kernel<C, EW, true>), grid, dim3(Gm::NT), 0, s, a);
-  else hipLaunchKernelGGL((resblock2_kernel<C, EW, false>), grid, dim3(Gm::NT), 0, s, a);
+  if (f16) hipLaunchKernelGGL((resblock2_kernel<C, EW, true, A>), grid, dim3(Gm::NT), 0, s, a);
+  else hipLaunchKernelGGL((resblock2_kernel<C, EW, false, A>), grid, dim3(Gm::NT), 0, s, a);
 }
 
-}  // namespace
-
-extern "C" int ttsk_hifi_resblock2_supported(int C, int K, int d0, int d1) {
-  if (!(C == 128 || C == 64 || C == 32) || !(K == 3 || K == 5 || K == 7)) return 0;
-  const int HK = (K - 1) / 2;
-  return d0 >= 1 && d0 <= RB2_H0 && d1 >= 1 && d1 <= 64 && HK * d0 <= RB2_H0 && HK * d1 <= rb2_max_h1(C);
-}
-
-extern "C" int ttsk_hifi_resblock2(const void* x16, const void* w0_pack, const float* bias0, const void* w1_pack, const float* bias1,
-                                   void* out16, int f16, int B, int len, int C, int K, int d0, int d1, float slope, int mode, float scale,
-                                   float final_slope, void* stream) {
-  TTSK_REQUIRE(x16 && w0_pack && bias0 && w1_pack && bias1 && out16, "ttsk_hifi_resblock2: null pointer");
-  TTSK_REQUIRE(B > 0 && len > 0 && B <= 65535 && len <= (1 << 30) && x16 != out16, "ttsk_hifi_resblock2: bad sizes / in-place output");
-  TTSK_REQUIRE(ttsk_hifi_resblock2_supported(C, K, d0, d1), "ttsk_hifi_resblock2: no instance for C=%d K=%d d=(%d,%d)", C, K, d0, d1);
-  TTSK_REQUIRE(mode >= 0 && mode <= 2 && (final_slope > 0.f || mode != 2), "ttsk_hifi_resblock2: bad mode / final_slope");
-  TTSK_REQUIRE(slope > 0.f && slope < 1.f, "ttsk_hifi_resblock2: LeakyReLU slope %g outside (0, 1)", slope);
-  TTSK_REQUIRE(((((uintptr_t)x16) | ((uintptr_t)w0_pack) | ((uintptr_t)w1_pack) | ((uintptr_t)bias0) | ((uintptr_t)bias1) | ((uintptr_t)out16)) & 15) == 0,
-               "ttsk_hifi_resblock2: 16-byte alignment");
-  const Rb2Args a{(const bf16_t*)x16, (const bf16_t*)w0_pack, (const bf16_t*)w1_pack, bias0, bias1, (bf16_t*)out16, len, K, d0, d1, slope,
-                  mode, scale, final_slope};
-  const int h1 = (K - 1) / 2 * d1;
-  hipStream_t s = (hipStream_t)stream;
+template <typename A>
+void dispatch_rb2(const A& a, int B, int f16, int C, int h1, hipStream_t s) {
   if (C == 128) {
     if (h1 <= 8) launch_rb2<128, 1>(a, B, f16, s);
     else if (h1 <= 16) launch_rb2<128, 2>(a, B, f16, s);
@@ -302,6 +287,52 @@ extern "C" int ttsk_hifi_resblock2(const void* x16, const void* w0_pack, const f
     if (h1 <= 32) launch_rb2<32, 1>(a, B, f16, s);
     else launch_rb2<32, 2>(a, B, f16, s);
   }
+}
+
+}  // namespace
+
+extern "C" int ttsk_hifi_resblock2_supported(int C, int K, int d0, int d1) {
+  if (!(C == 128 || C == 64 || C == 32) || !(K == 3 || K == 5 || K == 7)) return 0;
+  const int HK = (K - 1) / 2;
+  return d0 >= 1 && d0 <= RB2_H0 && d1 >= 1 && d1 <= 64 && HK * d0 <= RB2_H0 && HK * d1 <= rb2_max_h1(C);
+}
+
+static int resblock2_impl(const void* x16, const void* w0_pack, const float* bias0, const void* w1_pack, const float* bias1,
+                          void* out16, int f16, int B, int len, int C, int K, int d0, int d1, float slope, int mode, float scale,
+                          float final_slope, const RowLens* rl, void* stream) {
+  TTSK_REQUIRE(x16 && w0_pack && bias0 && w1_pack && bias1 && out16, "ttsk_hifi_resblock2: null pointer");
+  TTSK_REQUIRE(B > 0 && len > 0 && B <= 65535 && len <= (1 << 30) && x16 != out16, "ttsk_hifi_resblock2: bad sizes / in-place output");
+  TTSK_REQUIRE(ttsk_hifi_resblock2_supported(C, K, d0, d1), "ttsk_hifi_resblock2: no instance for C=%d K=%d d=(%d,%d)", C, K, d0, d1);
+  TTSK_REQUIRE(mode >= 0 && mode <= 2 && (final_slope > 0.f || mode != 2), "ttsk_hifi_resblock2: bad mode / final_slope");
+  TTSK_REQUIRE(slope > 0.f && slope < 1.f, "ttsk_hifi_resblock2: LeakyReLU slope %g outside (0, 1)", slope);
+  TTSK_REQUIRE(((((uintptr_t)x16) | ((uintptr_t)w0_pack) | ((uintptr_t)w1_pack) | ((uintptr_t)bias0) | ((uintptr_t)bias1) | ((uintptr_t)out16)) & 15) == 0,
+               "ttsk_hifi_resblock2: 16-byte alignment");
+  const Rb2Args a{(const bf16_t*)x16, (const bf16_t*)w0_pack, (const bf16_t*)w1_pack, bias0, bias1, (bf16_t*)out16, len, K, d0, d1, slope,
+                  mode, scale, final_slope};
+  const int h1 = (K - 1) / 2 * d1;
+  hipStream_t s = (hipStream_t)stream;
+  if (rl) {
+    WithRows<Rb2Args> ar;
+    static_cast<Rb2Args&>(ar) = a;
+    ar.rl = *rl;
+    dispatch_rb2(ar, B, f16, C, h1, s);
+  } else {
+    dispatch_rb2(a, B, f16, C, h1, s);
+  }
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
+}
+
+extern "C" int ttsk_hifi_resblock2(const void* x16, const void* w0_pack, const float* bias0, const void* w1_pack, const float* bias1,
+                                   void* out16, int f16, int B, int len, int C, int K, int d0, int d1, float slope, int mode, float scale,
+                                   float final_slope, void* stream) {
+  return resblock2_impl(x16, w0_pack, bias0, w1_pack, bias1, out16, f16, B, len, C, K, d0, d1, slope, mode, scale, final_slope, nullptr, stream);
+}
+
+extern "C" int ttsk_hifi_resblock2_rowlen(const void* x16, const void* w0_pack, const float* bias0, const void* w1_pack, const float* bias1,
+                                        void* out16, int f16, int B, int len, int C, int K, int d0, int d1, float slope, int mode, float scale,
+                                        float final_slope, const int32_t* row_frames, int row_stride, int spf, void* stream) {
+  TTSK_REQUIRE_ROWS("ttsk_hifi_resblock2_rowlen", row_stride, spf);
+  const RowLens rl{row_frames, row_stride, spf};
+  return resblock2_impl(x16, w0_pack, bias0, w1_pack, bias1, out16, f16, B, len, C, K, d0, d1, slope, mode, scale, final_slope, &rl, stream);
 }

@@ -5,6 +5,7 @@
 // captured graph holds for every call with the same N.  No atomics, no host synchronisation; every row is checked against the
 // buffer sizes before it is used (a row that does not fit is skipped: a wrong plan gives wrong audio, never a wild access).
 #include "common.h"
+#include "rowlens.h"
 
 namespace {
 
@@ -24,26 +25,32 @@ __global__ __launch_bounds__(256) void mel_windows_kernel(const float* __restric
   for (int tix = blockIdx.x; tix < n_tiles; tix += gridDim.x) {
     const int n = tix / tiles_per_win, t0 = (tix - n * tiles_per_win) * TILE_T;
     const int64_t f0 = plan[n * TTSK_WIN_ROW + 5];
-    const bool live = f0 >= 0 && f0 + W <= n_src_frames;
-    if (live) {
+    // the row's valid frames (column [6]: 0 = all W): a short utterance's row reads v frames of the staging buffer, not W, and is
+    // zero from frame v on — what follows it in the buffer is another utterance, or nothing
+    const int vq = plan[n * TTSK_WIN_ROW + TTSK_WIN_VALID];
+    const int v = (vq <= 0 || vq > W) ? W : vq;
+    const bool live = f0 >= 0 && f0 + v <= n_src_frames;
+    const int nt = min(TILE_T, v - t0);                 // frames of this tile that exist (<= 0: none)
+    if (live && nt > 0) {
       const float* s = src + (f0 + t0) * st;
       if (vec) {
         const int q = C >> 2;
         for (int i = threadIdx.x; i < TILE_T * q; i += 256) {
           const int t = i / q, c4 = i - t * q;
-          const float4 v = *reinterpret_cast<const float4*>(s + (int64_t)t * st + 4 * c4);
+          if (t >= nt) continue;
+          const float4 x4 = *reinterpret_cast<const float4*>(s + (int64_t)t * st + 4 * c4);
           float* d = tile + t * ldt + 4 * c4;
-          d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+          d[0] = x4.x; d[1] = x4.y; d[2] = x4.z; d[3] = x4.w;
         }
       } else if (sc == 1) {
         for (int i = threadIdx.x; i < TILE_T * C; i += 256) {
           const int t = i / C, c = i - t * C;
-          tile[t * ldt + c] = s[(int64_t)t * st + c];
+          if (t < nt) tile[t * ldt + c] = s[(int64_t)t * st + c];
         }
       } else {
         for (int i = threadIdx.x; i < TILE_T * C; i += 256) {
           const int c = i / TILE_T, t = i - c * TILE_T;
-          tile[t * ldt + c] = s[(int64_t)t * st + (int64_t)c * sc];
+          if (t < nt) tile[t * ldt + c] = s[(int64_t)t * st + (int64_t)c * sc];
         }
       }
     }
@@ -52,8 +59,8 @@ __global__ __launch_bounds__(256) void mel_windows_kernel(const float* __restric
     const int q8 = C >> 3;
     for (int i = threadIdx.x; i < TILE_T * q8; i += 256) {
       uint4 o = make_uint4(0u, 0u, 0u, 0u);
-      if (live) {
-        const int t = i / q8, c8 = i - t * q8;
+      const int t = i / q8, c8 = i - t * q8;
+      if (live && t < nt) {
         const float* p = tile + t * ldt + 8 * c8;
         o = make_uint4(pack2<F16>(p[0], p[1]), pack2<F16>(p[2], p[3]), pack2<F16>(p[4], p[5]), pack2<F16>(p[6], p[7]));
       }
@@ -92,6 +99,17 @@ __global__ __launch_bounds__(256) void wav_stitch_kernel(const float* __restrict
       d[0] = a; d[1] = b;
     }
   }
+}
+
+// (B, len, C) 16-bit: the frames of row b from its edge on (rowlens.h) are set to zero; one thread per 16 bytes, grid-strided over the
+// rows' tails only.  What conv_pre leaves past a short row's end (its bias, and the taps that reach back into the row) must not
+// reach the first upsampler.
+__global__ __launch_bounds__(256) void zero_rows_past_kernel(uint4* __restrict__ x, int B, int len, int q8, RowLens rl) {
+  const int b = blockIdx.y;
+  const int e = row_edge(rl, b, len);
+  uint4* row = x + (int64_t)b * len * q8;
+  const int64_t n = (int64_t)(len - e) * q8;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) row[(int64_t)e * q8 + i] = make_uint4(0u, 0u, 0u, 0u);
 }
 
 // workgroups for a grid-strided kernel: `per_cu` per compute unit of the current device, never more than the work needs
@@ -142,6 +160,19 @@ extern "C" int ttsk_wav_stitch(const float* src, const int32_t* plan, void* dst,
   else
     hipLaunchKernelGGL(wav_stitch_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (const int*)plan, dst, n_dst_frames, scale,
                        N, W, spf);
+  TTSK_CHECK_LAUNCH();
+  return TTSK_OK;
+}
+
+extern "C" int ttsk_zero_rows_past(void* x16, int B, int len, int C, const int32_t* row_frames, int row_stride, int spf, void* stream) {
+  TTSK_REQUIRE(x16 && B > 0 && len > 0 && C > 0 && B <= 65535, "zero_rows_past: bad arguments");
+  TTSK_REQUIRE_ROWS("zero_rows_past", row_stride, spf);
+  TTSK_REQUIRE(C % 8 == 0 && (((uintptr_t)x16) & 15) == 0, "zero_rows_past: C=%d must be a multiple of 8 and the tensor 16-byte aligned", C);
+  if (!row_frames) return TTSK_OK;                      // every row full: nothing lies past an end
+  const int q8 = C >> 3;
+  const int64_t per_row = ((int64_t)len * q8 + 255) / 256;
+  const dim3 grid((unsigned)(per_row < 64 ? per_row : 64), B);
+  hipLaunchKernelGGL(zero_rows_past_kernel, grid, dim3(256), 0, (hipStream_t)stream, (uint4*)x16, B, len, q8, RowLens{row_frames, row_stride, spf});
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
 }

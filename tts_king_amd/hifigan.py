@@ -207,13 +207,15 @@ class Generator(nn.Module):
             xl = xl_next
         return x
 
-    def _pair_blocks(self, rbs, packs, a, nxt_slope, fused_for=()):
+    def _pair_blocks(self, rbs, packs, a, nxt_slope, fused_for=(), rows=None):
         """The stage's ResBlock1s on the pair kernel (hifi/models.py:88-95, :190-197): per block three launches, each one
         (c1 dilated -> lrelu -> c2 -> + x); every block's last launch adds into `out` and the last block's scales by 1/num_kernels and
         applies the consumer's LeakyReLU (the MRF average).  packs[j] = (weight packs, biases), both in the order c1_0, c2_0, c1_1,
-        c2_1, ...; blocks whose kernel size is in `fused_for` run on the six-conv fused kernel instead (same packs, same modes)."""
+        c2_1, ...; blocks whose kernel size is in `fused_for` run on the six-conv fused kernel instead (same packs, same modes).
+        `rows`: per-row lengths (ops._row_args): the kernels store nothing past a row's end, so `out` starts as zeros — what the next
+        upsampler must read there."""
         nk = len(rbs)
-        out = torch.empty_like(a)
+        out = torch.empty_like(a) if rows is None else torch.zeros_like(a)
         for j, rb in enumerate(rbs):
             ws, bs = packs[j]
             mode = 0 if j == 0 else (2 if j == nk - 1 else 1)
@@ -224,12 +226,12 @@ class Generator(nn.Module):
             ws_kernel = (self.pair_ws and a.is_contiguous() and a.shape[0] * ((a.shape[1] + tt - 1) // tt) >= self.pair_ws_min_tiles and
                          all(ops.hifi_conv_pair_ws_supported(a.shape[2], rb.k, d, a.shape[1]) for d in rb.dilation))
             if rb.k in fused_for and not ws_kernel:
-                ops.hifi_resblock1(a, ws, bs, rb.dilation, out, rb.k, mode=mode, scale=1.0 / nk, slope=LRELU_SLOPE, final_slope=fs)
+                ops.hifi_resblock1(a, ws, bs, rb.dilation, out, rb.k, mode=mode, scale=1.0 / nk, slope=LRELU_SLOPE, final_slope=fs, rows=rows)
                 continue
             x, nd = a, len(rb.dilation)
             for m, d in enumerate(rb.dilation):
                 kw = dict(out=out, mode=mode, scale=1.0 / nk, final_slope=fs) if m == nd - 1 else {}
-                x = ops.hifi_conv_pair(x, ws[2 * m], bs[2 * m], ws[2 * m + 1], bs[2 * m + 1], rb.k, d, slope=LRELU_SLOPE, ws=ws_kernel, **kw)
+                x = ops.hifi_conv_pair(x, ws[2 * m], bs[2 * m], ws[2 * m + 1], bs[2 * m + 1], rb.k, d, slope=LRELU_SLOPE, ws=ws_kernel, rows=rows, **kw)
         return out
 
     def _pair_packs(self, pk, i, nk, rbs, C):
@@ -305,19 +307,32 @@ class Generator(nn.Module):
             a0 = ops.nct_to_ntc(x.float(), self.act_dtype)                                 # (B, T, 80) 16-bit
             return self.forward_ntc(a0, pk)
 
-    def forward_ntc(self, a0, pk=None):
-        """`forward` from the channels-last 16-bit mel on: a0 (B, T, 80) in `act_dtype`, what `ops.nct_to_ntc` and `ops.mel_windows` write."""
+    def forward_ntc(self, a0, pk=None, row_frames=None):
+        """`forward` from the channels-last 16-bit mel on: a0 (B, T, 80) in `act_dtype`, what `ops.nct_to_ntc` and `ops.mel_windows` write.
+
+        `row_frames` (1-D int32 device tensor or view of B entries, e.g. column `windows.VALID` of a plan table; needs `short_rows()`):
+        row b holds an utterance of row_frames[b] frames (0 = all T) and its waveform is what the utterance gives alone — at a stage
+        with s samples per frame the positions >= row_frames[b] * s are zero padding for every conv.  a0 must be zero
+        there (ttsk_mel_windows writes it so); the samples of the output past a row's end are unspecified."""
         if pk is None:
             pk = self._prepare()
         h = self.h
         nk = self.num_kernels
+        rows, spf = None, 1
         with torch.no_grad():
             if pk["pre_win"] is not None:
                 al = ops.hifi_conv_pre_win(a0, pk["pre_win"], pk["pre"][1], pk["pre"][0].shape[0], pk["pre"][0].shape[1], LRELU_SLOPE)   # window kernel
             else:
                 al = ops.conv1d(a0, pk["pre"][0], pk["pre"][1], flags=ops.LRELU_OUT, out_slope=LRELU_SLOPE)   # lrelu(conv_pre(x))
+            if row_frames is not None:
+                # conv_pre and the upsamplers know no row length: what conv_pre leaves past a row's end (bias, the taps that reach back)
+                # is zeroed here, every MRF stage below masks its reads of the upsampler's output and hands on zeros past the end
+                ops.zero_rows_past(al, (row_frames, 1))
             for i, (u, k) in enumerate(zip(h.upsample_rates, h.upsample_kernel_sizes)):
                 self._mark("conv_pre" if i == 0 else "mrf%d" % (i - 1))
+                spf *= int(u)
+                if row_frames is not None:
+                    rows = (row_frames, spf)
                 wu, bu = pk["ups"][i]
                 # slope of the activation that consumes this stage's output: 0.1 before the next upsampler,
                 # F.leaky_relu's default 0.01 before conv_post (hifi/models.py:197)
@@ -329,12 +344,12 @@ class Generator(nn.Module):
                     # folded into the last block's epilogue (modes 0 / 1 / 2): no lrelu copy from the upsampler, no avg3 pass
                     a = self._upsample_raw(al, pk, i)
                     self._mark("ups%d" % i)
-                    out = torch.empty_like(a)
+                    out = torch.empty_like(a) if rows is None else torch.zeros_like(a)
                     for j, rb in enumerate(rbs):
                         (w0, w1), (b0, b1) = pk["rb2"][i * nk + j]
                         lastb = j == nk - 1
                         ops.hifi_resblock2(a, w0, b0, w1, b1, rb.k, rb.dilation, slope=LRELU_SLOPE, out=out, mode=0 if j == 0 else (2 if lastb else 1),
-                                           scale=1.0 / nk, final_slope=nxt_slope if lastb else 1.0)
+                                           scale=1.0 / nk, final_slope=nxt_slope if lastb else 1.0, rows=rows)
                     al = out
                     continue
                 # C = 32: the fused kernel is as fast or faster for every kernel size (86 / 143 / 181 us against 102 / 139 / 178)
@@ -347,7 +362,7 @@ class Generator(nn.Module):
                     # then bound by its HBM passes, and the fused kernel makes one instead of three)
                     fused_for = (3,) if C_out == 64 and all(pk["rbf"][i * nk + j] is not None for j in range(nk)) else ()
                     self._mark("ups%d" % i)
-                    al = self._pair_blocks(rbs, ppacks, a, nxt_slope, fused_for)
+                    al = self._pair_blocks(rbs, ppacks, a, nxt_slope, fused_for, rows)
                     continue
                 fused = self.fused and all(pk["rbf"][i * nk + j] is not None for j in range(nk)) and nk >= 2
                 if fused:
@@ -363,18 +378,20 @@ class Generator(nn.Module):
                         ws = [w for j in range(nk) for w in pk["rbf"][i * nk + j][0]]
                         bs = [b for j in range(nk) for b in pk["rbf"][i * nk + j][1]]
                         y = ops.hifi_mrf32_post(a, ws, bs, [rb.dilation for rb in rbs], [rb.k for rb in rbs], pk["post"][0], pk["post"][1],
-                                                slope=LRELU_SLOPE, final_slope=nxt_slope, scale=1.0 / nk)
+                                                slope=LRELU_SLOPE, final_slope=nxt_slope, scale=1.0 / nk, rows=rows)
                         self._mark("mrf%d" % i)
                         self._mark("conv_post")
                         return y
-                    out = torch.empty_like(a)
+                    out = torch.empty_like(a) if rows is None else torch.zeros_like(a)
                     for j, rb in enumerate(rbs):
                         ws, bs = pk["rbf"][i * nk + j]
                         lastb = j == nk - 1
                         ops.hifi_resblock1(a, ws, bs, rb.dilation, out, rb.k, mode=0 if j == 0 else (2 if lastb else 1),
-                                           scale=1.0 / nk, slope=LRELU_SLOPE, final_slope=nxt_slope if lastb else 1.0)
+                                           scale=1.0 / nk, slope=LRELU_SLOPE, final_slope=nxt_slope if lastb else 1.0, rows=rows)
                     al = out
                     continue
+                if rows is not None:
+                    raise ops.L.TtskError("HiFi-GAN stage %d runs conv by conv, which takes no per-row length (Generator.short_rows() is False)" % i)
                 windowed = self.window_conv and all(pk["rbw"][i * nk + j] is not None and ops.hifi_conv_window_supported(C_out, rbs[j].k, dd)
                                                     for j in range(nk) for dd in rbs[j].dilation)
                 axl = torch.empty(al.shape[0], al.shape[1] * u, wu.shape[1], dtype=al.dtype, device=al.device)
@@ -409,6 +426,43 @@ class Generator(nn.Module):
             n *= int(u)
         return n
 
+    def short_rows(self):
+        """True when an utterance shorter than a window can run as a row of the windowed batch: every MRF stage of this configuration, with
+        the kernel families as they are toggled on this object, runs on kernels that take a per-row length (ResBlock2 fused, the conv
+        pairs, the fused ResBlock1 / last-stage kernel).  False for a stage on the conv-by-conv implicit-GEMM path: such a generator keeps
+        the solo route for short utterances (`forward_short`).  The same walk as `forward_ntc`'s route choice."""
+        if self.conv_pre.bias.device.type != "cuda":
+            return False
+        # the answer depends on the configuration, the storage type and the toggles, not on the weights: kept per such key, so that a
+        # replayed list call does not walk the parameters (`_prepare`'s key) just to plan
+        key = (self.act_dtype, self.window_conv, self.conv_pair, self.conv_pair_small, self.fused, self.resblock2_fused, self.window_upsample)
+        if self._short_rows_memo is not None and self._short_rows_memo[0] == key:
+            return self._short_rows_memo[1]
+        self._short_rows_memo = (key, self._short_rows_walk())
+        return self._short_rows_memo[1]
+
+    _short_rows_memo = None
+
+    def _short_rows_walk(self):
+        pk, nk = self._prepare(), self.num_kernels
+        for i in range(self.num_upsamples):
+            idx = range(i * nk, (i + 1) * nk)
+            rbs = [self.resblocks[j] for j in idx]
+            C_out = pk["ups"][i][0].shape[1]
+            if self.resblock2_fused and nk >= 2 and all(pk["rb2"][j] is not None for j in idx):
+                continue
+            want_pair = (self.conv_pair and self.window_conv) if C_out >= 128 else (self.conv_pair_small and self.fused and C_out == 64)
+            if want_pair and self._pair_packs(pk, i, nk, rbs, C_out) is not None:
+                continue
+            if self.fused and nk >= 2 and all(pk["rbf"][j] is not None for j in idx):
+                continue
+            return False
+        return True
+
+    def plan(self, lens):
+        """The window plan of a call on this generator: short utterances as rows of the batch where `short_rows()` allows."""
+        return windows.plan_windows(lens, windows.W, self.halo(), short_rows=self.short_rows())
+
     def stage_mels(self, mels, plan, frames_first, stage=None):
         """The planned utterances back to back in the fp32 staging buffer the gather reads (N * W frames): (80, frames) rows, or,
         `frames_first`, (frames, 80) rows.  One copy per utterance (host or device source); frames past the call's own stay as they are,
@@ -423,12 +477,14 @@ class Generator(nn.Module):
             (v[o:o + T] if frames_first else v[:, o:o + T]).copy_(mels[i], non_blocking=True)
         return stage
 
-    def forward_windows(self, stage, table, frames_first=False, int16_scale=None):
+    def forward_windows(self, stage, table, frames_first=False, int16_scale=None, row_lengths=False):
         """Gather -> generator -> stitch on device-resident inputs (capturable: nothing here depends on a length): the staging buffer
-        and the plan table (N, 8) int32 -> one flat buffer of N * W * 256 samples, the kept samples of every utterance back to back."""
+        and the plan table (N, 8) int32 -> one flat buffer of N * W * 256 samples, the kept samples of every utterance back to back.
+        `row_lengths` (a plan with `has_short_rows`): the generator reads every row's valid frames from the table's column VALID, on
+        the kernels that take a per-row length; without it the launches are those of a batch of full windows."""
         with torch.no_grad():
             a0 = ops.mel_windows(stage, table, windows.W, self.act_dtype, frames_first)
-            y = self.forward_ntc(a0)
+            y = self.forward_ntc(a0, row_frames=table[:, windows.VALID] if row_lengths else None)
             return ops.wav_stitch(y, table, windows.W, int16_scale=int16_scale)
 
     @staticmethod
@@ -450,15 +506,16 @@ class Generator(nn.Module):
         dev = self.conv_pre.bias.device
         if dev.type != "cuda":
             raise ops.L.TtskError("HiFi-GAN ragged vocoding needs the generator's weights on a HIP device; there is no CPU path")
-        plan = windows.plan_windows(lens, windows.W, self.halo())
+        plan = self.plan(lens)
         if not plan.planned:
             return None, plan, self.samples_per_frame()
         stage = self.stage_mels(mels, plan, frames_first)
         table = torch.from_numpy(plan.table).to(dev)
-        return self.forward_windows(stage, table, frames_first, int16_scale), plan, self.samples_per_frame()
+        return self.forward_windows(stage, table, frames_first, int16_scale, plan.has_short_rows), plan, self.samples_per_frame()
 
     def forward_short(self, mels, plan, frames_first=False, int16_scale=None, forward=None):
-        """The utterances too short for a window, each through `forward` (or the caller's `forward`) on its own: {index: waveform}."""
+        """The utterances the plan left out (`plan.short`: those shorter than a window on a generator without `short_rows()`), each
+        through `forward` (or the caller's `forward`) on its own: {index: waveform}."""
         mels, _ = self.ragged_mels(mels, frames_first)
         out = {}
         for i in plan.short:
@@ -471,9 +528,10 @@ class Generator(nn.Module):
         """mels: a list of (80, T_i) or (1, 80, T_i) tensors of any lengths (`frames_first`: (T_i, 80) / (1, T_i, 80), FastSpeech2's
         layout) -> a list of (1, 1, 256 T_i) fp32 waveforms, each what `forward` gives for that mel alone (tts_king_amd/windows.py).
 
-        Utterances of at least `windows.W` frames run together as fixed-size windows: one gather launch, the generator on
-        (N, W, 80), one stitch launch.  An utterance shorter than a window cannot be windowed (a padded mel is not a solo run) and
-        goes through `forward` on its own, one utterance per call."""
+        The utterances run together as fixed-size windows: one gather launch, the generator on (N, W, 80), one stitch launch.  An
+        utterance shorter than a window is one row of that batch with its own length (a padded mel is not a solo run: the kernels
+        treat what lies past the row's end as the zero padding of every layer).  On a generator configuration whose
+        kernels take no row length (`short_rows()` False) it goes through `forward` on its own instead, one utterance per call."""
         mels = list(mels)
         flat, plan, spf = self.forward_ragged_flat(mels, frames_first)
         return windows.split(flat, plan, spf, self.forward_short(mels, plan, frames_first))

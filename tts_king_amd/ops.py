@@ -1302,6 +1302,32 @@ def wav_stitch(y, plan, W, out=None, int16_scale=None):
     return out
 
 
+def _row_args(what, rows, Bn):
+    """(pointer, element stride, samples per frame) of a per-row length for the *_rowlen entry points (include/ttsk.h): `rows` =
+    (frames, spf) with `frames` a 1-D int32 device tensor or view of Bn entries (column `windows.VALID` of a plan table, or a compact
+    copy) or None (every row full).  The kernels clamp the VALUES; the extent is checked here."""
+    frames, spf = rows
+    if int(spf) <= 0:
+        raise L.TtskError("%s: %d samples per frame" % (what, spf))
+    if frames is None:
+        return None, 1, int(spf)
+    _dev(frames)
+    if frames.dtype != torch.int32 or frames.dim() != 1 or frames.numel() != Bn or (Bn > 1 and frames.stride(0) <= 0):
+        raise L.TtskError("%s: %d rows need a 1-D int32 length tensor of %d entries, got %s %s" % (what, Bn, Bn, frames.dtype, tuple(frames.shape)))
+    return frames.data_ptr(), (int(frames.stride(0)) if Bn > 1 else 1), int(spf)
+
+
+def zero_rows_past(x, rows):
+    """x (B, len, C) 16-bit, in place: the positions of row b from frames[b] * spf on := 0 (`rows` as for `_row_args`)."""
+    _dev(x)
+    Bn, ln, Cn = x.shape
+    if not x.is_contiguous():
+        raise L.TtskError("zero_rows_past: needs a contiguous (B, len, C) tensor")
+    rp, rs, spf = _row_args("zero_rows_past", rows, Bn)
+    check(L.load().ttsk_zero_rows_past(_ptr(x), Bn, ln, Cn, rp, rs, spf, _stream()), "ttsk_zero_rows_past")
+    return x
+
+
 _PINNED = {}
 _PINNED_LOCK = threading.Lock()
 
@@ -1753,15 +1779,21 @@ def pack_resblock_weight(w, dtype=f16):
     return out
 
 
-def hifi_resblock1(x, weights, biases, dilations, out, K, mode=0, scale=1.0, slope=0.1, final_slope=1.0):
+def hifi_resblock1(x, weights, biases, dilations, out, K, mode=0, scale=1.0, slope=0.1, final_slope=1.0, rows=None):
     """Fused ResBlock1 (reference: hifi/models.py:88-95).  x/out (B, len, C) 16-bit; weights: six fragment-major packs
     (pack_resblock_weight) and biases six fp32 (C,) in the order convs1[0], convs2[0], convs1[1], convs2[1], convs1[2],
-    convs2[2].  mode 0: out = y, 1: out += y, 2: out = (out + y) * scale; final_slope: LeakyReLU on the stored value."""
+    convs2[2].  mode 0: out = y, 1: out += y, 2: out = (out + y) * scale; final_slope: LeakyReLU on the stored value.
+    rows (`_row_args`): a per-row length beside the batch stride (ttsk_hifi_resblock1_rowlen): nothing is read or stored past a row's end."""
     _dev(x, out, *weights, *biases)
     Bn, ln, Cn = x.shape
     wp = (C.c_void_p * 6)(*[w.data_ptr() for w in weights])
     bp = (C.c_void_p * 6)(*[b.data_ptr() for b in biases])
     dl = (C.c_int32 * 3)(*[int(d) for d in dilations])
+    if rows is not None:
+        check(L.load().ttsk_hifi_resblock1_rowlen(_ptr(x), _ptr(out), int(x.dtype == f16), C.cast(wp, C.c_void_p), C.cast(bp, C.c_void_p),
+                                                C.cast(dl, C.c_void_p), Bn, ln, Cn, K, mode, scale, slope, final_slope,
+                                                *_row_args("hifi_resblock1", rows, Bn), _stream()), "ttsk_hifi_resblock1_rowlen")
+        return out
     check(L.load().ttsk_hifi_resblock1(_ptr(x), _ptr(out), int(x.dtype == f16), C.cast(wp, C.c_void_p), C.cast(bp, C.c_void_p),
                                        C.cast(dl, C.c_void_p), Bn, ln, Cn, K, mode, scale, slope, final_slope, _stream()),
           "ttsk_hifi_resblock1")
@@ -1772,11 +1804,12 @@ def hifi_mrf32_post_supported(C_, ks, k_post):
     return len(ks) == 3 and bool(L.load().ttsk_hifi_mrf32_post_supported(C_, int(ks[0]), int(ks[1]), int(ks[2]), int(k_post)))
 
 
-def hifi_mrf32_post(x, weights, biases, dilations, ks, w_post, b_post, slope=0.1, final_slope=0.01, scale=1.0 / 3.0, stage_out=None):
+def hifi_mrf32_post(x, weights, biases, dilations, ks, w_post, b_post, slope=0.1, final_slope=0.01, scale=1.0 / 3.0, stage_out=None, rows=None):
     """The generator's whole last stage in one launch (reference: hifi/models.py:190-199; csrc/mrf32.hip): x (B, len, 32) 16-bit raw
     stage input -> (B, 1, len) fp32 waveform = tanh(conv_post(leaky_relu(mean_j ResBlock1_j(x), 0.01))).  weights / biases: 18 packs /
     (32,) fp32 vectors, block j's six convs at [6 j ..] in hifi_resblock1's order; dilations: three triples; ks: the three kernel sizes;
-    w_post (1, 7, 32) tap-major 16-bit.  stage_out (optional, like x): receives the activated average conv_post reads."""
+    w_post (1, 7, 32) tap-major 16-bit.  stage_out (optional, like x): receives the activated average conv_post reads.
+    rows (`_row_args`): a per-row length (ttsk_hifi_mrf32_post_rowlen); the samples past a row's end are not written."""
     _dev(x, w_post, b_post, stage_out, *weights, *biases)
     Bn, ln, Cn = x.shape
     assert len(weights) == 18 and len(biases) == 18 and x.is_contiguous()
@@ -1784,6 +1817,12 @@ def hifi_mrf32_post(x, weights, biases, dilations, ks, w_post, b_post, slope=0.1
     bp = (C.c_void_p * 18)(*[b.data_ptr() for b in biases])
     dl = (C.c_int32 * 9)(*[int(d) for tri in dilations for d in tri])
     out = torch.empty(Bn, 1, ln, dtype=torch.float32, device=x.device)
+    if rows is not None:
+        check(L.load().ttsk_hifi_mrf32_post_rowlen(_ptr(x), _ptr(out), _ptr(stage_out), int(x.dtype == f16), C.cast(wp, C.c_void_p),
+                                                 C.cast(bp, C.c_void_p), C.cast(dl, C.c_void_p), _ptr(w_post), _ptr(b_post), Bn, ln, Cn, int(ks[0]),
+                                                 int(ks[1]), int(ks[2]), int(w_post.shape[-2]), slope, final_slope, scale,
+                                                 *_row_args("hifi_mrf32_post", rows, Bn), _stream()), "ttsk_hifi_mrf32_post_rowlen")
+        return out
     check(L.load().ttsk_hifi_mrf32_post(_ptr(x), _ptr(out), _ptr(stage_out), int(x.dtype == f16), C.cast(wp, C.c_void_p), C.cast(bp, C.c_void_p),
                                         C.cast(dl, C.c_void_p), _ptr(w_post), _ptr(b_post), Bn, ln, Cn, int(ks[0]), int(ks[1]), int(ks[2]),
                                         int(w_post.shape[-2]), slope, final_slope, scale, _stream()), "ttsk_hifi_mrf32_post")
@@ -1913,16 +1952,30 @@ def hifi_conv_pair_ws_supported(Cn, K, dil, ln=0):
     return bool(L.load().ttsk_hifi_conv_pair_ws_supported(Cn, K, dil)) and ln * Cn * 2 < 2 ** 30
 
 
-def hifi_conv_pair(x, w1_pack, bias1, w2_pack, bias2, K, dilation, slope=0.1, out=None, mode=0, scale=1.0, final_slope=1.0, ws=False, max_wgs=0):
+def hifi_conv_pair(x, w1_pack, bias1, w2_pack, bias2, K, dilation, slope=0.1, out=None, mode=0, scale=1.0, final_slope=1.0, ws=False, max_wgs=0,
+                   rows=None):
     """y = c2(lrelu(c1_{K,dil}(lrelu(x)) + b1)) + b2 + x in one launch (C = 128; hifi/models.py:88-95, one dilation of ResBlock1).
     mode 0: out = y; 1: out += y; 2: out = lrelu((out + y) * scale, final_slope) (the MRF average, :190-197; ttsk_hifi_resblock1's modes).
-    ws: the weights-stationary persistent kernel (C = 64, or C = 128 with K = 3; ttsk_hifi_conv_pair_ws, bit-identical)."""
+    ws: the weights-stationary persistent kernel (C = 64, or C = 128 with K = 3; ttsk_hifi_conv_pair_ws, bit-identical).
+    rows (`_row_args`): a per-row length beside the batch stride (ttsk_hifi_conv_pair_rowlen / _ws_rowlen): nothing is read or stored past a
+    row's end, so an `out` a later kernel reads there must come in zeroed."""
     _dev(x, w1_pack, bias1, w2_pack, bias2, out)
     Bn, ln, Cn = x.shape
     if out is None:
         if mode >= 1:
             raise L.TtskError("hifi_conv_pair: mode %d accumulates into `out`" % mode)
         out = torch.empty_like(x)
+    if rows is not None:
+        ra = _row_args("hifi_conv_pair", rows, Bn)
+        if ws:
+            check(L.load().ttsk_hifi_conv_pair_ws_rowlen(_ptr(x.contiguous()), _ptr(w1_pack), _ptr(bias1), _ptr(w2_pack), _ptr(bias2), _ptr(out),
+                                                       int(x.dtype == f16), Bn, ln, Cn, K, dilation, slope, mode, scale, final_slope, int(max_wgs),
+                                                       *ra, _stream()), "ttsk_hifi_conv_pair_ws_rowlen")
+        else:
+            check(L.load().ttsk_hifi_conv_pair_rowlen(_ptr(x), _ptr(w1_pack), _ptr(bias1), _ptr(w2_pack), _ptr(bias2), _ptr(out), int(x.dtype == f16),
+                                                    Bn, ln, Cn, K, dilation, slope, mode, scale, final_slope, *ra, _stream()),
+                  "ttsk_hifi_conv_pair_rowlen")
+        return out
     if ws:
         check(L.load().ttsk_hifi_conv_pair_ws(_ptr(x.contiguous()), _ptr(w1_pack), _ptr(bias1), _ptr(w2_pack), _ptr(bias2), _ptr(out), int(x.dtype == f16),
                                               Bn, ln, Cn, K, dilation, slope, mode, scale, final_slope, int(max_wgs), _stream()), "ttsk_hifi_conv_pair_ws")
@@ -1936,10 +1989,11 @@ def hifi_resblock2_supported(Cn, K, d0, d1):
     return bool(L.load().ttsk_hifi_resblock2_supported(Cn, K, d0, d1))
 
 
-def hifi_resblock2(x, w0_pack, bias0, w1_pack, bias1, K, dilations, slope=0.1, out=None, mode=0, scale=1.0, final_slope=1.0):
+def hifi_resblock2(x, w0_pack, bias0, w1_pack, bias1, K, dilations, slope=0.1, out=None, mode=0, scale=1.0, final_slope=1.0, rows=None):
     """One ResBlock2 (hifi/models.py:134-140) in one launch: x1 = x + b0 + conv_{K,d0}(lrelu(x)), y = x1 + b1 + conv_{K,d1}(lrelu(x1)).
     x (B, len, C) 16-bit raw block input; packs from pack_resblock_weight.  mode 0: out = y; 1: out += y;
-    2: out = lrelu((out + y) * scale, final_slope) (the MRF average, :190-197; hifi_conv_pair's modes)."""
+    2: out = lrelu((out + y) * scale, final_slope) (the MRF average, :190-197; hifi_conv_pair's modes).
+    rows (`_row_args`): a per-row length beside the batch stride (ttsk_hifi_resblock2_rowlen), as for hifi_conv_pair."""
     _dev(x, w0_pack, bias0, w1_pack, bias1, out)
     x = x.contiguous()
     Bn, ln, Cn = x.shape
@@ -1952,6 +2006,11 @@ def hifi_resblock2(x, w0_pack, bias0, w1_pack, bias1, K, dilations, slope=0.1, o
         raise L.TtskError("hifi_resblock2: `out` must be a contiguous %s tensor of shape %s" % (x.dtype, tuple(x.shape)))
     if w0_pack.numel() < Cn * Cn * K or w1_pack.numel() < Cn * Cn * K or bias0.numel() < Cn or bias1.numel() < Cn:
         raise L.TtskError("hifi_resblock2: weight packs / biases too small for C=%d K=%d" % (Cn, K))
+    if rows is not None:
+        check(L.load().ttsk_hifi_resblock2_rowlen(_ptr(x), _ptr(w0_pack), _ptr(bias0), _ptr(w1_pack), _ptr(bias1), _ptr(out), int(x.dtype == f16), Bn,
+                                                ln, Cn, K, d0, d1, slope, mode, scale, final_slope, *_row_args("hifi_resblock2", rows, Bn), _stream()),
+              "ttsk_hifi_resblock2_rowlen")
+        return out
     check(L.load().ttsk_hifi_resblock2(_ptr(x), _ptr(w0_pack), _ptr(bias0), _ptr(w1_pack), _ptr(bias1), _ptr(out), int(x.dtype == f16), Bn,
                                        ln, Cn, K, d0, d1, slope, mode, scale, final_slope, _stream()), "ttsk_hifi_resblock2")
     return out

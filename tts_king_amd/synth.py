@@ -146,8 +146,9 @@ class GraphedSynthesizer:
         """mels: a list of (80, T_i) mels of any lengths (`frames_first`: (T_i, 80)) -> a list of (1, 1, 256 T_i) waveforms on the device,
         fp32, or int16 = truncation of waveform * `int16_scale`.  The utterances of at least `windows.W` frames run as N fixed-size
         windows (tts_king_amd/windows.py) on ONE graph per ladder value of N: gather -> generator -> stitch, with the mel staging buffer
-        and the plan table as its static inputs, so calls with different lengths and the same N replay the same graph.  Shorter
-        utterances go through `wav`, one at a time."""
+        and the plan table as its static inputs, so calls with different lengths and the same N replay the same graph.  An utterance
+        shorter than a window is a row of the same batch (its length is one more number in the table; such calls share one graph per
+        N of their own); only on a generator without `short_rows()` does it go through `wav`, alone."""
         mels = list(mels)
         flat, plan, spf = self.wav_ragged_flat(mels, frames_first, int16_scale)
         flat = None if flat is None else flat.clone()          # the graph's private output buffer: hand out a copy, as `wav` does
@@ -159,17 +160,19 @@ class GraphedSynthesizer:
         per frame).  After a replay the buffer is the graph's own: valid until the next call with the same N."""
         gen = self.vocoder
         mels, lens = gen.ragged_mels(mels, frames_first)
-        plan = windows.plan_windows(lens, windows.W, gen.halo())
+        plan = gen.plan(lens)
         spf = gen.samples_per_frame()
         if not plan.planned:
             return None, plan, spf
-        key = ("rag", plan.N, plan.W, bool(frames_first), None if int16_scale is None else float(int16_scale))
+        # short rows: the same N on the kernels that read each row's length from the table (a call of full windows keeps its own graph)
+        rl = plan.has_short_rows
+        key = ("rag", plan.N, plan.W, bool(frames_first), None if int16_scale is None else float(int16_scale)) + (("rows",) if rl else ())
         table = torch.from_numpy(plan.table)
         g = self._rag.get(key)
         if g is None:
             stage = gen.stage_mels(mels, plan, frames_first)
             table = table.to(stage.device)
-            fn = lambda st, tb: gen.forward_windows(st, tb, frames_first, int16_scale)
+            fn = lambda st, tb: gen.forward_windows(st, tb, frames_first, int16_scale, rl)
             if key not in self._seen:                      # first sight: eager (lazy allocations, weight packing)
                 self._seen.add(key)
                 return fn(stage, table), plan, spf

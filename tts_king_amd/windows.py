@@ -17,6 +17,7 @@ import numpy as np
 # the batch up in coarser steps.  96 and 128 are within 2 % of each other and ahead of the rest; 96 is the faster on all three workloads.
 W = 96
 ROW = 8                     # int32 per plan row (TTSK_WIN_ROW)
+VALID = 6                   # column of a row's valid frames (TTSK_WIN_VALID): 0 = all W, v in 1..W = a short utterance's v frames
 
 
 def _get(h, key):
@@ -72,30 +73,42 @@ def window_starts(T, Wn, H):
 
 class Plan:
     """table      (N, ROW) int32 numpy, one row per window, padding rows last (include/ttsk.h: utterance, start, kept lo, kept hi,
-                  output frame of lo, staging frame of the window's start or -1)
+                  output frame of lo, staging frame of the window's start or -1, valid frames of the row or 0 = all W)
        n_windows  rows that are real windows;  N = len(table) is on the ladder
-       planned    indices (into `lens`) of the utterances with T >= W, in table order;  short = the others
+       planned    indices (into `lens`) of the utterances that have rows, in table order (T >= W; with `short_rows` every T >= 1);
+                  short = the others
        offsets    planned utterance -> its first frame in the staging buffer and in the flat output (both hold the planned utterances
-                  back to back); frames = their total, never more than N * W"""
+                  back to back); frames = their total, never more than N * W
+       has_short_rows  some row holds an utterance shorter than the window (0 < column VALID < W): the generator needs the row lengths"""
 
     def __init__(self, table, n_windows, planned, short, offsets, frames, lens, Wn, H):
         self.table, self.n_windows, self.planned, self.short = table, n_windows, planned, short
         self.offsets, self.frames, self.lens, self.W, self.H = offsets, frames, lens, Wn, H
         self.N = int(table.shape[0])
+        self.has_short_rows = bool(self.N) and bool(((table[:, VALID] > 0) & (table[:, VALID] < Wn)).any())
 
 
-def plan_windows(lens, Wn=None, H=14):
+def plan_windows(lens, Wn=None, H=14, short_rows=False):
     """Plan the windows of a call: `lens` = mel frames of every utterance.  Utterances shorter than a window are not planned
-    (`Plan.short`): a zero-padded mel is not a solo run, since the reference zero-pads the activations of every layer at the end."""
+    (`Plan.short`): a zero-padded mel is not a solo run, since the reference zero-pads the activations of every layer at the end.
+    `short_rows` (for a generator whose kernels take a per-row length, `Generator.short_rows()`): an utterance of 1 <= T < W frames is
+    planned too, as ONE row of its own that starts at frame 0, keeps [0, T) and carries T in column VALID — the generator then treats
+    the row's frames >= T as non-existent, which is the solo run's zero padding at every layer.  Only empty utterances stay in
+    `Plan.short`; a call without short utterances gets the same table either way."""
     Wn = W if Wn is None else int(Wn)
     lens = [int(t) for t in lens]
-    planned = [i for i, t in enumerate(lens) if t >= Wn]
-    short = [i for i, t in enumerate(lens) if t < Wn]
+    least = 1 if short_rows else Wn
+    planned = [i for i, t in enumerate(lens) if t >= least]
+    short = [i for i, t in enumerate(lens) if t < least]
     rows, offsets, off = [], {}, 0
     for i in planned:
         T = lens[i]
-        starts = window_starts(T, Wn, H)
         offsets[i] = off
+        if T < Wn:
+            rows.append((i, 0, 0, T, off, off, T, 0))
+            off += T
+            continue
+        starts = window_starts(T, Wn, H)
         for j, s in enumerate(starts):
             lo = 0 if j == 0 else s + H
             hi = T if j == len(starts) - 1 else starts[j + 1] + H
