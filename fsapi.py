@@ -67,12 +67,19 @@ class FSTWOapi:
             raise Exception(f"Speaker {speaker_name} was not found in speakers.json")
         return self.speakers_dict[speaker_name]
 
-    def generate_batch(self, phonemes_list, duration_control=1.0, pitch_control=1.0, energy_control=1.0, speaker_names=None, aux=False):
+    def generate_batch(self, phonemes_list, duration_control=1.0, pitch_control=1.0, energy_control=1.0, speaker_names=None, aux=False,
+                       durations=None, pitch=None, energy=None, target_frames=None, return_prosody=False):
         """phonemes_list: a list of int arrays (L_i,) or (1, L_i) of any lengths -> a list of postnet mels (1, T_i, 80) fp32 on the
         device, each what `generate` gives for that text alone (NOT what the reference's padded batch gives: there an utterance's last
         phoneme and length depend on what it is batched with).  Each control is a scalar or one value per
         utterance, `speaker_names` a name or a list of names.  With `hip_graph` the call replays two graphs keyed by shape buckets;
-        without it the same kernels are launched plainly.  `aux`: also the per-utterance predictions (`GraphedSynthesizer.mel_ragged`)."""
+        without it the same kernels are launched plainly.  `aux`: also the per-utterance predictions (`GraphedSynthesizer.mel_ragged`).
+
+        Per-phoneme prosody (DESIGN.md section 14): a control may hold, per utterance, an array over that utterance's phonemes;
+        `durations` / `pitch` / `energy` set explicit per-phoneme values (per utterance None, a scalar, or an array in which NaN leaves
+        the model's own prediction) and `target_frames` (an integer or one per utterance, None = free) fits the durations to exactly
+        that many frames.  `return_prosody`: also a list of {"logd", "dur", "pitch", "energy"} over each utterance's own phonemes --
+        what was used, ready to be edited and passed back in (None for an utterance that left the batch for the solo route)."""
         from tts_king_amd import batching
         texts = batching.as_id_rows(phonemes_list)
         names = batching.per_utterance_names(speaker_names, len(texts), "speaker_names")
@@ -83,9 +90,15 @@ class FSTWOapi:
                 from tts_king_amd.synth import GraphedSynthesizer
                 self._batch_synth = GraphedSynthesizer(self.model, graphs=False, **self._buckets)
             synth = self._batch_synth
-        out = synth.mel_ragged(speakers, texts, pitch_control, energy_control, duration_control, aux=aux)
-        mels = [mel.unsqueeze(0) for mel in out[0]]
-        return (mels, out[2]) if aux else mels
+        want = aux or return_prosody
+        out = synth.mel_ragged(speakers, texts, pitch_control, energy_control, duration_control, aux=want, durations=durations, pitch=pitch,
+                               energy=energy, target_frames=target_frames)
+        res = ([mel.unsqueeze(0) for mel in out[0]],)
+        if aux:
+            res += (out[2],)
+        if return_prosody:
+            res += ([None if a is None else {k: a[k] for k in ("logd", "dur", "pitch", "energy")} for a in out[2]],)
+        return res if len(res) > 1 else res[0]
 
 
 def load_speakers_json(dir_path):

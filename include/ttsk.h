@@ -447,6 +447,22 @@ int ttsk_embed_step(const float* pred, const float* control, const float* bins, 
                     const void* x_bf16, const int64_t* lens, int seg_len, void* x_out_bf16, float* scaled_out,
                     int32_t* idx_out, int rows, int D, void* stream);
 int ttsk_duration_round_dev(const float* logd, const float* d_control, int L, float* out, int n, void* stream);
+/* ---- per-phoneme prosody (tts_king_amd/synth.py `mel_ragged` with per-phoneme controls, explicit values or a frame budget)
+ * embed_step_rows: ttsk_embed_step with control (rows,) and an explicit value per row -- scaled[row] = has[row] ? value[row] :
+ *   pred[row] * control[row] (a set value is not multiplied: the reference's `target`, modules.py:92-101,131-140).  scaled_out /
+ *   idx_out report what was used.  Constant control rows with has = 0 give ttsk_embed_step's bits.
+ * duration_rows: v[i] = has[i] ? durations[i] : max(rint(exp(logd[i]) - 1) * d_control[i], 0)   (modules.py:195-205).
+ * duration_fit: one workgroup per utterance u (seg_len <= 1024), l < lens[u] (clamped to [0, seg_len]); target[u] < 0 copies row u.
+ *   Fixed phonemes (has) keep trunc(v), F = their sum; the free ones share budget = max(target[u] - F, 0): q = v * budget / S with
+ *   S = the free phonemes' sum, out = floor(q) + 1 for the (budget - sum floor(q)) largest fractional parts, ties to the lower l;
+ *   v = 0 stays 0; S = 0 leaves F frames.  Sums in a fixed order that depends on l only.  Positions past lens[u] are copied. */
+int ttsk_embed_step_rows(const float* pred, const float* control, const float* value, const uint8_t* has, const float* bins,
+                         int n_bins, const float* table, const void* x_bf16, const int64_t* lens, int seg_len, void* x_out_bf16,
+                         float* scaled_out, int32_t* idx_out, int rows, int D, void* stream);
+int ttsk_duration_rows(const float* logd, const float* d_control, const float* durations, const uint8_t* has, float* out, int n,
+                       void* stream);
+int ttsk_duration_fit(const float* v, const uint8_t* has, const int32_t* target, const int64_t* lens, int seg_len, float* out,
+                      int B, void* stream);
 /* the same for up to 8 independent tables per launch (all embedding-table gradients of a backward pass) */
 typedef struct ttsk_scatter_item {
   const void* dx;      /* (n_idx * idx_div, D) bf16 */

@@ -21,15 +21,28 @@ class TTSKing:
         self.vocoder = HIFIapi(self.cfg, self.cfg.gpu)
         self.speakers = self.tts.speaker_names
 
-    def generate_mel(self, text, duration_control=1.0, pitch_control=1.0, energy_control=1.0, speaker=0):
+    def generate_mel(self, text, duration_control=1.0, pitch_control=1.0, energy_control=1.0, speaker=0, durations=None, pitch=None,
+                     energy=None, target_frames=None, return_prosody=False):
         """One text -> (1, T, 80) mel (reference: tts_king.py:25-45).  A list of texts -> a list of such mels, run together
-        (`FSTWOapi.generate_batch`): each is what its text gives alone; `speaker` and the controls may then be lists, one per text."""
+        (`FSTWOapi.generate_batch`): each is what its text gives alone; `speaker` and the controls may then be lists, one per text.
+
+        Per-phoneme prosody (`FSTWOapi.generate_batch`): for one text a control may be a 1-D array over its
+        phonemes, `durations` / `pitch` / `energy` a scalar or such an array (NaN = keep the prediction) and `target_frames` the exact
+        number of frames wanted; for a list of texts each of these is a list with one entry per text.  `return_prosody`: (mel,
+        {"logd", "dur", "pitch", "energy"}) -- lists of both for a list of texts.  One text with any of this runs as a batch of one."""
+        new = dict(durations=durations, pitch=pitch, energy=energy, target_frames=target_frames, return_prosody=return_prosody)
         if isinstance(text, (list, tuple)):
             from tts_king_amd import batching
             phonemes = [t if isinstance(t, np.ndarray) else self.text_preprocess(t) for t in text]
             names = [self.speakers[s] if isinstance(s, (int, np.integer)) else s
                      for s in batching.per_utterance_names(speaker, len(phonemes), "speaker")]
-            return self.tts.generate_batch(phonemes, duration_control, pitch_control, energy_control, speaker_names=names)
+            return self.tts.generate_batch(phonemes, duration_control, pitch_control, energy_control, speaker_names=names, **new)
+        controls = (duration_control, pitch_control, energy_control)
+        if return_prosody or any(v is not None for v in (durations, pitch, energy, target_frames)) or any(np.ndim(c) > 0 for c in controls):
+            one = lambda v: None if v is None else [v]
+            out = self.generate_mel([text], *[one(c) for c in controls], speaker=[speaker], durations=one(durations), pitch=one(pitch),
+                                    energy=one(energy), target_frames=one(target_frames), return_prosody=return_prosody)
+            return (out[0][0], out[1][0]) if return_prosody else out[0]
         phonemes = text if isinstance(text, np.ndarray) else self.text_preprocess(text)
         if isinstance(speaker, int):
             speaker = self.speakers[speaker]
@@ -43,14 +56,19 @@ class TTSKing:
             return self.vocoder.generate_ragged(mel_spec, frames_first=True)
         return self.vocoder.generate(mel_spec.transpose(1, 2))
 
-    def speak(self, text, duration_control=1.0, pitch_control=1.0, energy_control=1.0, speaker=0):
+    def speak(self, text, duration_control=1.0, pitch_control=1.0, energy_control=1.0, speaker=0, durations=None, pitch=None, energy=None,
+              target_frames=None, return_prosody=False):
         """reference: tts_king.py:51-57 calls a missing `generate_mel_batch`; here: mel -> float waveform.  A list of texts -> a list
-        of float waveforms (1, 1, 256 T_i) on the device: the batched mels go straight into the vocoder's ragged route."""
+        of float waveforms (1, 1, 256 T_i) on the device: the batched mels go straight into the vocoder's ragged route.  The prosody
+        arguments are `generate_mel`'s (`target_frames` frames are 256 * target_frames samples); `return_prosody`: (waveforms, prosody)."""
+        out = self.generate_mel(text, duration_control, pitch_control, energy_control, speaker, durations=durations, pitch=pitch, energy=energy,
+                                target_frames=target_frames, return_prosody=return_prosody)
+        mels, prosody = out if return_prosody else (out, None)
         if isinstance(text, (list, tuple)):
-            mels = self.generate_mel(text, duration_control, pitch_control, energy_control, speaker)
-            return self.vocoder.call_ragged(mels, frames_first=True)
-        mel = self.generate_mel(text, duration_control, pitch_control, energy_control, speaker)
-        return self.vocoder(mel.transpose(1, 2))
+            wav = self.vocoder.call_ragged(mels, frames_first=True)
+        else:
+            wav = self.vocoder(mels.transpose(1, 2))
+        return (wav, prosody) if return_prosody else wav
 
     def text_preprocess(self, text):
         """reference: tts_king.py:59-60 -> input_process.preprocess_rus (needs russian_g2p).  A string that already is in

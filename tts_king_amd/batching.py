@@ -99,3 +99,136 @@ def plan_frames(totals, max_seq_len, t_bucket=T_BUCKET):
     over = [r for r, t in enumerate(totals) if t > max_seq_len]
     T = bucket(max(totals[r] for r in keep), t_bucket, max_seq_len) if keep else 0
     return keep, over, T
+
+
+# ---------------------------------------------------------------------------------------------- per-phoneme prosody
+# `mel_ragged(..., durations=, pitch=, energy=, target_frames=)` and per-phoneme arrays in the three controls.
+# Every argument is None, a scalar, or one entry per utterance; an entry is None, a scalar or an array over the utterance's own
+# phonemes in which NaN means "not set here".  The graphs of that route read all of it from (B, L_bucket) device arrays.
+
+CONTROLS = ("p_control", "e_control", "d_control")
+VALUES = ("pitch", "energy", "durations")
+
+
+def rows_key(B, L_bucket):
+    """The front graph of the per-phoneme route: one per shape, whatever inputs are given and whatever their values."""
+    return ("front", int(B), int(L_bucket), "rows")
+
+
+def _is_scalar(x):
+    if isinstance(x, (bool, int, float, np.number)):
+        return True
+    return hasattr(x, "ndim") and not isinstance(x, (list, tuple)) and x.ndim == 0
+
+
+def wants_rows(B, controls, values, target_frames):
+    """Does a call need the per-phoneme route?  Yes when an explicit value or a frame budget is given, or when a control is
+    anything but a scalar or B scalars (today's forms, which keep today's route)."""
+    if target_frames is not None or any(v is not None for v in values):
+        return True
+    for c in controls:
+        if c is None or _is_scalar(c):
+            continue
+        if isinstance(c, np.ndarray) and c.ndim == 1 and c.dtype != object:
+            continue
+        if isinstance(c, (list, tuple)) and all(_is_scalar(x) for x in c):
+            continue
+        return True
+    return False
+
+
+def _entries(value, B, name):
+    """One entry per utterance out of None / a scalar / a sequence of B entries."""
+    if value is None or _is_scalar(value):
+        return [value] * B
+    if isinstance(value, np.ndarray) and value.dtype != object:
+        value = list(value)
+    try:
+        value = list(value)
+    except TypeError:
+        raise ValueError("%s: expected None, a scalar or %d entries (one per utterance), got %r" % (name, B, type(value).__name__))
+    if len(value) != B:
+        raise ValueError("%s: expected a scalar or %d entries (one per utterance), got %d" % (name, B, len(value)))
+    return value
+
+
+def _phoneme_row(entry, n, name, u, fill):
+    """One utterance's entry as (values (n,) fp32, set (n,) bool): None -> nothing set, a scalar -> every phoneme, an array of n with
+    NaN = not set.  Unset positions hold `fill`.  Infinite values are refused."""
+    what = "%s[%d]" % (name, u)
+    if entry is None:
+        return np.full((n,), fill, np.float32), np.zeros((n,), bool)
+    try:
+        a = np.asarray(entry.detach().cpu().numpy() if hasattr(entry, "detach") else entry, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("%s: expected a scalar or %d numbers (one per phoneme)" % (what, n))
+    if a.ndim == 0:
+        a = np.full((n,), a, np.float32)
+    if a.ndim != 1 or a.shape[0] != n:
+        raise ValueError("%s: expected a scalar or %d values (one per phoneme of utterance %d), got shape %s" % (what, n, u, a.shape))
+    if np.isinf(a).any():
+        raise ValueError("%s: values must be finite (NaN marks a phoneme as not set), got an infinite value at phoneme %d"
+                         % (what, int(np.flatnonzero(np.isinf(a))[0])))
+    has = ~np.isnan(a)
+    return np.where(has, a, np.float32(fill)).astype(np.float32), has
+
+
+class Prosody:
+    """The normalised per-phoneme inputs of a call, per utterance (texts over the phoneme bucket included): `ctl[k][u]` (len_u,) fp32
+    for k = pitch, energy, duration control; `val[k][u]` / `has[k][u]` the explicit pitch, energy and durations and where they are
+    set; `target` (B,) int32, -1 = no frame budget."""
+
+    def __init__(self, lens, ctl, val, has, target):
+        self.lens, self.ctl, self.val, self.has, self.target = lens, ctl, val, has, target
+
+    def plain(self, u):
+        """(p, e, d) scalar controls when utterance u carries nothing the scalar route cannot express, else None."""
+        if self.target[u] >= 0 or any(self.has[k][u].any() for k in range(3)):
+            return None
+        if any(self.lens[u] > 0 and (self.ctl[k][u] != self.ctl[k][u][0]).any() for k in range(3)):
+            return None
+        return tuple(float(self.ctl[k][u][0]) for k in range(3))
+
+    def padded(self, sel, L):
+        """The ten (len(sel), L) / (len(sel),) arrays `FastSpeech2.eval_front_rows` takes, in its order.  Padding is neutral: control
+        1, nothing set (value 0), target -1."""
+        n = len(sel)
+        out = []
+        for k in range(3):
+            c, v, h = np.ones((n, L), np.float32), np.zeros((n, L), np.float32), np.zeros((n, L), np.uint8)
+            for r, u in enumerate(sel):
+                m = self.lens[u]
+                c[r, :m], v[r, :m], h[r, :m] = self.ctl[k][u], self.val[k][u], self.has[k][u]
+            out += [c, v, h]
+        out.append(np.ascontiguousarray(self.target[list(sel)], dtype=np.int32))
+        return out
+
+
+def plan_prosody(lens, p_control=1.0, e_control=1.0, d_control=1.0, pitch=None, energy=None, durations=None, target_frames=None):
+    """Validate and normalise the prosody arguments of a call whose utterances have `lens` phonemes -> Prosody.  Raises ValueError
+    naming the argument and the utterance: a wrong number of entries or phonemes, an infinite value, a negative duration, a frame
+    budget that is no integer >= 0."""
+    lens = [int(n) for n in lens]
+    B = len(lens)
+    ctl, val, has = [], [], []
+    for name, arg in zip(CONTROLS, (p_control, e_control, d_control)):
+        ent = _entries(1.0 if arg is None else arg, B, name)
+        ctl.append([_phoneme_row(ent[u], lens[u], name, u, 1.0)[0] for u in range(B)])
+    for name, arg in zip(VALUES, (pitch, energy, durations)):
+        ent = _entries(arg, B, name)
+        rows = [_phoneme_row(ent[u], lens[u], name, u, 0.0) for u in range(B)]
+        if name == "durations":
+            for u, (a, h) in enumerate(rows):
+                if (a[h] < 0).any():
+                    raise ValueError("durations[%d]: frame counts must be >= 0, got %g at phoneme %d" % (u, a[h].min(), int(np.flatnonzero(h & (a < 0))[0])))
+        val.append([r[0] for r in rows])
+        has.append([r[1].astype(np.uint8) for r in rows])
+    target = np.full((B,), -1, np.int32)
+    for u, t in enumerate(_entries(target_frames, B, "target_frames")):
+        if t is None:
+            continue
+        f = float(t) if _is_scalar(t) else float("nan")
+        if not (f >= 0 and f == int(f) and f < 2 ** 31):
+            raise ValueError("target_frames[%d]: expected None or an integer >= 0, got %r" % (u, t))
+        target[u] = int(f)
+    return Prosody(lens, ctl, val, has, target)

@@ -341,6 +341,132 @@ __global__ __launch_bounds__(256) void duration_round_dev_kernel(const float* __
   if (i < n) out[i] = fmaxf(rintf(expf(logd[i]) - 1.f) * d_control[i / L], 0.f);
 }
 
+// ---------------------------------------------------------------------------------------------- per-phoneme prosody
+// embed_step_kernel with one control per ROW and an optional explicit value per row: where has[row] the value is used as is (the
+// reference's `target` branch, modules.py:92-101,131-140: no control on it), elsewhere pred * control.  Search, NaN rule, sum and
+// the zero rows past lens[u] are embed_step_kernel's: constant control rows and has = 0 give its bits.
+__global__ __launch_bounds__(256) void embed_step_rows_kernel(const float* __restrict__ pred, const float* __restrict__ control,
+                                                              const float* __restrict__ value, const unsigned char* __restrict__ has,
+                                                              const float* __restrict__ bins, int nb, const float* __restrict__ table,
+                                                              const bf16_t* __restrict__ x, const long long* __restrict__ lens, int seg_len,
+                                                              bf16_t* __restrict__ out, float* __restrict__ scaled, int* __restrict__ idx,
+                                                              int rows, int D) {
+  const int cpr = D >> 2;
+  const int64_t n = (int64_t)rows * cpr;
+  for (int64_t c = blockIdx.x * 256 + threadIdx.x; c < n; c += (int64_t)gridDim.x * 256) {
+    const int row = (int)(c / cpr), ch = (int)(c - (int64_t)row * cpr) * 4;
+    const int u = row / seg_len;
+    const float s = has[row] ? value[row] : pred[row] * control[row];
+    const int bi = bucket_of(bins, nb, s);
+    if (ch == 0) { scaled[row] = s; idx[row] = bi; }
+    if (row - u * seg_len >= clamp_len(lens, u, seg_len)) {
+      *(uint2*)(out + (int64_t)row * D + ch) = make_uint2(0u, 0u);
+      continue;
+    }
+    f32x4 v = *(const f32x4*)(table + (int64_t)bi * D + ch);
+    const uint2 w = *(const uint2*)(x + (int64_t)row * D + ch);
+    v[0] += __uint_as_float(w.x << 16); v[1] += __uint_as_float(w.x & 0xFFFF0000u);
+    v[2] += __uint_as_float(w.y << 16); v[3] += __uint_as_float(w.y & 0xFFFF0000u);
+    *(uint2*)(out + (int64_t)row * D + ch) = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
+  }
+}
+
+// duration_round_dev_kernel with one control per row and an optional explicit frame count per row (used as is, modules.py:195-205)
+__global__ __launch_bounds__(256) void duration_rows_kernel(const float* __restrict__ logd, const float* __restrict__ d_control,
+                                                            const float* __restrict__ durations, const unsigned char* __restrict__ has,
+                                                            float* __restrict__ out, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = has[i] ? durations[i] : fmaxf(rintf(expf(logd[i]) - 1.f) * d_control[i], 0.f);
+}
+
+// Sum of one value per thread over the workgroup in a fixed order: LDS tree over the 256 slots.  Every thread gets the result.
+__device__ __forceinline__ double block_sum_256(double x, double* red) {
+  __syncthreads();                      // the previous call's readers are done with `red`
+  red[threadIdx.x] = x;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// Fit the durations of utterance u = blockIdx.x to a frame budget.  Phonemes with has[l] are FIXED and keep
+// trunc(v); the others are FREE and share budget = max(target - F, 0) in proportion to v: q = v * budget / S, dur = floor(q), the
+// frames still missing go one each to the largest fractional parts (ties to the lower l).  target < 0: the row is copied through.
+// Thread t owns l = t, t + 256, t + 512, t + 768 and adds its own four in that order before the tree: the order of every sum is a
+// function of l alone, and positions past lens[u] (or past seg_len) add exact zeros, so neither the row of the batch nor the
+// phoneme bucket changes a bit of the result.  fp64 for S and q: with <= 1024 terms Sum floor(q) cannot pass the budget.
+constexpr int FIT_MAXL = 1024;
+__global__ __launch_bounds__(256) void duration_fit_kernel(const float* __restrict__ v, const unsigned char* __restrict__ has,
+                                                           const int* __restrict__ target, const long long* __restrict__ lens,
+                                                           int seg_len, float* __restrict__ out) {
+  __shared__ double red[256];
+  __shared__ double frac[FIT_MAXL];     // fractional part of q of a free phoneme with v > 0, else -1 (never ranks before anything)
+  const int u = blockIdx.x, t = threadIdx.x;
+  const float* vr = v + (int64_t)u * seg_len;
+  const unsigned char* hr = has + (int64_t)u * seg_len;
+  float* o = out + (int64_t)u * seg_len;
+  const int tgt = target[u];
+  const int len = clamp_len(lens, u, seg_len);
+  if (tgt < 0) {
+    for (int l = t; l < seg_len; l += 256) o[l] = vr[l];
+    return;
+  }
+  float vv[4];
+  bool fixed[4], live[4];
+  double F = 0.0, S = 0.0, nfree = 0.0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int l = t + 256 * k;
+    live[k] = l < len;
+    vv[k] = live[k] ? vr[l] : 0.f;
+    fixed[k] = live[k] && hr[l] != 0;
+    if (fixed[k]) F += (double)truncf(vv[k]);
+    else if (live[k] && vv[k] > 0.f) { S += (double)vv[k]; nfree += 1.0; }
+  }
+  F = block_sum_256(F, red);
+  S = block_sum_256(S, red);
+  const int n = (int)block_sum_256(nfree, red);
+  const double budget = fmax((double)tgt - F, 0.0);
+  double fl[4], got = 0.0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int l = t + 256 * k;
+    const bool elig = live[k] && !fixed[k] && vv[k] > 0.f;
+    fl[k] = 0.0;
+    double fr = -1.0;
+    if (elig) {
+      const double q = (double)vv[k] * budget / S;
+      fl[k] = floor(q);
+      fr = q - fl[k];
+      got += fl[k];
+    }
+    frac[l] = fr;
+  }
+  got = block_sum_256(got, red);          // its barriers also publish frac[]
+  // frames still to hand out; < n by construction, the general split keeps the total exact should rounding ever make it n or more
+  const long long r = n > 0 ? (long long)fmax(budget - got, 0.0) : 0;
+  const long long each = n > 0 ? r / n : 0;
+  const int extra = n > 0 ? (int)(r % n) : 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int l = t + 256 * k;
+    if (l >= seg_len) continue;
+    if (!live[k]) { o[l] = vr[l]; continue; }             // past the utterance's own end: as it came
+    if (fixed[k]) { o[l] = truncf(vv[k]); continue; }
+    if (!(vv[k] > 0.f)) { o[l] = 0.f; continue; }
+    const double mine = frac[l];
+    int rank = 0;
+    if (extra > 0)
+      for (int m = 0; m < len; ++m) {
+        const double f = frac[m];
+        rank += (f > mine || (f == mine && m < l)) ? 1 : 0;
+      }
+    o[l] = (float)(fl[k] + (double)each + (rank < extra ? 1.0 : 0.0));
+  }
+}
+
 // rows (u, t) with t >= lens[u] := 0 (16-byte pieces), the per-utterance form of zero_frames_kernel
 __global__ __launch_bounds__(256) void zero_frames_lens_kernel(uint4* __restrict__ x, int rows, int q_per_row, int seg_len,
                                                                const long long* __restrict__ lens) {
@@ -600,6 +726,38 @@ extern "C" int ttsk_embed_step(const float* pred, const float* control, const fl
 extern "C" int ttsk_duration_round_dev(const float* logd, const float* d_control, int L, float* out, int n, void* stream) {
   TTSK_REQUIRE(logd && d_control && out && n > 0 && L > 0 && n % L == 0, "duration_round_dev: bad arguments");
   hipLaunchKernelGGL(duration_round_dev_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, logd, d_control, L, out, n);
+  TTSK_CHECK_LAUNCH();
+  return TTSK_OK;
+}
+
+extern "C" int ttsk_embed_step_rows(const float* pred, const float* control, const float* value, const uint8_t* has, const float* bins,
+                                    int n_bins, const float* table, const void* x_bf16, const int64_t* lens, int seg_len, void* x_out_bf16,
+                                    float* scaled_out, int32_t* idx_out, int rows, int D, void* stream) {
+  TTSK_REQUIRE(pred && control && value && has && bins && table && x_bf16 && lens && x_out_bf16 && scaled_out && idx_out,
+               "embed_step_rows: null pointer");
+  TTSK_REQUIRE(rows > 0 && seg_len > 0 && rows % seg_len == 0 && D > 0 && (D & 3) == 0 && n_bins > 0, "embed_step_rows: bad sizes");
+  hipLaunchKernelGGL(embed_step_rows_kernel, dim3(grid_for((int64_t)rows * (D >> 2))), dim3(256), 0, (hipStream_t)stream, pred, control, value,
+                     has, bins, n_bins, table, (const bf16_t*)x_bf16, (const long long*)lens, seg_len, (bf16_t*)x_out_bf16, scaled_out, idx_out,
+                     rows, D);
+  TTSK_CHECK_LAUNCH();
+  return TTSK_OK;
+}
+
+extern "C" int ttsk_duration_rows(const float* logd, const float* d_control, const float* durations, const uint8_t* has, float* out, int n,
+                                  void* stream) {
+  TTSK_REQUIRE(logd && d_control && durations && has && out, "duration_rows: null pointer");
+  TTSK_REQUIRE(n > 0, "duration_rows: n must be positive");
+  hipLaunchKernelGGL(duration_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, logd, d_control, durations, has, out, n);
+  TTSK_CHECK_LAUNCH();
+  return TTSK_OK;
+}
+
+extern "C" int ttsk_duration_fit(const float* v, const uint8_t* has, const int32_t* target, const int64_t* lens, int seg_len, float* out,
+                                 int B, void* stream) {
+  TTSK_REQUIRE(v && has && target && lens && out, "duration_fit: null pointer");
+  TTSK_REQUIRE(B > 0 && seg_len > 0 && seg_len <= FIT_MAXL, "duration_fit: B=%d seg_len=%d out of range (seg_len <= %d)", B, seg_len, FIT_MAXL);
+  hipLaunchKernelGGL(duration_fit_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, v, has, (const int*)target, (const long long*)lens,
+                     seg_len, out);
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
 }

@@ -925,6 +925,23 @@ class FastSpeech2(nn.Module):
             raise ops.L.TtskError("eval_front_ragged: %d phonemes exceed max_seq_len %d; longer texts take the single-utterance path" % (Lp, self.max_seq_len))
         return self._eval_front(speakers, texts, src_lens, Lp, p_control, e_control, d_control, ragged=True)
 
+    def eval_front_rows(self, speakers, texts, src_lens, Lp, rows):
+        """`eval_front_ragged` with per-phoneme prosody.  `rows`: ten device tensors, all VALUES of one graph --
+        (p_control, pitch, has_pitch, e_control, energy, has_energy, d_control, durations, has_durations) each (B, Lp), fp32 and uint8
+        flags, and target_frames (B,) int32 (< 0: no budget); `batching.plan_prosody` builds them with neutral padding.  Where a flag is
+        set the value replaces prediction * control (the reference's targets, modules.py:92-101,131-140,195-205); the energy predictor
+        reads the pitch embedding picked that way.  The durations are then fitted to the budget (`ops.duration_fit`).  Neutral inputs
+        give `eval_front_ragged`'s bits.  Returns what it returns; pitch / energy / dur report what was used."""
+        if self.use_cwt:
+            raise ops.L.TtskError("use_cwt: batched synthesis of different-length texts is not defined -- the reference's CWT pitch "
+                                  "standardises over the batch axis and its scalar heads pool over the padded length; synthesize one text per call")
+        if Lp > min(self.max_seq_len, ops.FIT_MAX_L):
+            raise ops.L.TtskError("eval_front_rows: %d phonemes exceed the limit %d (max_seq_len %d, duration_fit %d)"
+                                  % (Lp, min(self.max_seq_len, ops.FIT_MAX_L), self.max_seq_len, ops.FIT_MAX_L))
+        if len(rows) != 10:
+            raise ops.L.TtskError("eval_front_rows: rows must hold 10 tensors (three controls, three values, three flags, the targets), got %d" % len(rows))
+        return self._eval_front(speakers, texts, src_lens, Lp, None, None, None, ragged=True, rows=rows)
+
     def eval_back_ragged(self, x3, dur, Lp, T):
         """`eval_back` for a frame count T that is a bucket (>= every utterance's own count): frames t >= mel_lens[u] of the PostNet's
         input and of its layers' outputs are zero rows, the zero padding each k = 5 conv meets when utterance u runs alone (in the
@@ -934,9 +951,10 @@ class FastSpeech2(nn.Module):
             raise ops.L.TtskError("eval_back_ragged: %d frames exceed max_seq_len %d" % (T, self.max_seq_len))
         return self._eval_back(x3, dur, Lp, T, ragged=True)[:3]
 
-    def _eval_front(self, speakers, texts, src_lens, Lp, p_control, e_control, d_control, ragged):
-        """The body of `eval_front` (`ragged` False: scalar controls, the reference's padded-batch semantics) and of
-        `eval_front_ragged` (True: control tensors, per-utterance limits on everything a predictor conv reads)."""
+    def _eval_front(self, speakers, texts, src_lens, Lp, p_control, e_control, d_control, ragged, rows=None):
+        """The body of `eval_front` (`ragged` False: scalar controls, the reference's padded-batch semantics), of
+        `eval_front_ragged` (True: control tensors, per-utterance limits on everything a predictor conv reads) and of
+        `eval_front_rows` (`rows`: the ragged front with the per-row kernels and the duration fit)."""
         self.sync_shadow()
         d = self.d
         Bn = texts.shape[0]
@@ -957,7 +975,10 @@ class FastSpeech2(nn.Module):
             x1 = ops.gather_add(x, self._m("speaker_emb.weight"), speakers, idx_div=Lp)
         pitch = self._predictor_fwd(va + "pitch_predictor.", x1, Bn, Lp, src_lens, 0.0, 0, None, None, hidden_lens=hl)
         heads = None
-        if ragged:
+        if rows is not None:
+            pc, pv, ph, ec, ev, eh, dc, dv, dh, target = rows
+            x2, pitch, _ = ops.embed_step_rows(pitch, pc, pv, ph, self.get(va + "pitch_bins"), self._m(va + "pitch_embedding.weight"), x1, src_lens, Lp)
+        elif ragged:
             x2, pitch, _ = ops.embed_step(pitch, p_control, self.get(va + "pitch_bins"), self._m(va + "pitch_embedding.weight"), x1, src_lens, Lp)
         else:
             if self.use_cwt:
@@ -966,7 +987,10 @@ class FastSpeech2(nn.Module):
                 pidx, pitch = ops.bucketize(pitch, self.get(va + "pitch_bins"), p_control, want_scaled=True)
             x2 = ops.gather_add(x1, self._m(va + "pitch_embedding.weight"), pidx.view(-1))
         energy = self._predictor_fwd(va + "energy_predictor.", x2, Bn, Lp, src_lens, 0.0, 0, None, None, hidden_lens=hl)
-        if ragged:
+        if rows is not None:
+            x3, energy, _ = ops.embed_step_rows(energy, ec, ev, eh, self.get(va + "energy_bins"), self._m(va + "energy_embedding.weight"), x2, src_lens, Lp)
+            dur = ops.duration_fit(ops.duration_rows(logd, dc, dv, dh), dh, target, src_lens)
+        elif ragged:
             x3, energy, _ = ops.embed_step(energy, e_control, self.get(va + "energy_bins"), self._m(va + "energy_embedding.weight"), x2, src_lens, Lp)
             dur = ops.duration_round_dev(logd, d_control)
         else:

@@ -1230,6 +1230,68 @@ def embed_step(pred, control, bins, table, x, lens, seg_len):
     return out, scaled, idx
 
 
+def _rows_like(name, ref, **arrays):
+    """Per-row inputs of the per-phoneme kernels: contiguous, on the device, `ref.numel()` entries, fp32 (uint8 for the `has` flags)."""
+    for key, (a, dt) in arrays.items():
+        if a.dtype != dt or a.numel() != ref.numel() or not a.is_contiguous():
+            raise L.TtskError("%s: %s must be contiguous %s with %d entries (one per row), got %s %s"
+                              % (name, key, dt, ref.numel(), a.dtype, tuple(a.shape)))
+
+
+def embed_step_rows(pred, control, value, has, bins, table, x, lens, seg_len):
+    """`embed_step` with one control per row and an optional explicit value per row: scaled = value where has else pred * control.
+    pred / control / value (B, L) fp32, has (B, L) uint8, x bf16 (B * L, D), lens (B,) int64 -> (x_out, scaled, idx)."""
+    _dev(pred, control, value, has, bins, table, x, lens)
+    if lens.dtype != torch.int64 or pred.dtype != torch.float32:
+        raise L.TtskError("embed_step_rows: pred must be fp32, lens int64")
+    pred = pred.contiguous()
+    rows, D = x.shape
+    Bn = rows // max(int(seg_len), 1)
+    if seg_len <= 0 or Bn * seg_len != rows or pred.numel() != rows or lens.numel() != Bn or table.shape[0] <= bins.numel() \
+            or not (x.is_contiguous() and lens.is_contiguous()):
+        raise L.TtskError("embed_step_rows: %d rows of seg_len %d need %d predictions, contiguous lens of %d entries and a table of more than "
+                          "%d rows; got %d, %d, %d" % (rows, seg_len, rows, Bn, bins.numel(), pred.numel(), lens.numel(), table.shape[0]))
+    _rows_like("embed_step_rows", pred, control=(control, torch.float32), value=(value, torch.float32), has=(has, torch.uint8))
+    out = torch.empty(rows, D, dtype=bf16, device=x.device)
+    scaled = torch.empty_like(pred)
+    idx = torch.empty(pred.shape, dtype=torch.int32, device=x.device)
+    check(L.load().ttsk_embed_step_rows(_ptr(pred), _ptr(control), _ptr(value), _ptr(has), _ptr(bins), bins.numel(), _ptr(table), _ptr(x),
+                                        _ptr(lens), seg_len, _ptr(out), _ptr(scaled), _ptr(idx), rows, D, _stream()), "ttsk_embed_step_rows")
+    return out, scaled, idx
+
+
+def duration_rows(logd, d_control, durations, has):
+    """v = durations where has else max(rint(exp(logd) - 1) * d_control, 0): logd / d_control / durations (B, L) fp32, has uint8."""
+    _dev(logd, d_control, durations, has)
+    if logd.dtype != torch.float32 or logd.dim() != 2 or not logd.is_contiguous():
+        raise L.TtskError("duration_rows: needs contiguous fp32 logd (B, L), got %s %s" % (logd.dtype, tuple(logd.shape)))
+    _rows_like("duration_rows", logd, d_control=(d_control, torch.float32), durations=(durations, torch.float32), has=(has, torch.uint8))
+    out = torch.empty_like(logd)
+    check(L.load().ttsk_duration_rows(_ptr(logd), _ptr(d_control), _ptr(durations), _ptr(has), _ptr(out), logd.numel(), _stream()),
+          "ttsk_duration_rows")
+    return out
+
+
+FIT_MAX_L = 1024     # duration_fit: one workgroup per utterance keeps the fractional parts in LDS
+
+
+def duration_fit(v, has, target, lens):
+    """Fit each utterance's durations to its frame budget (include/ttsk.h): v (B, L) fp32, has (B, L) uint8 (the
+    fixed phonemes), target (B,) int32 (< 0: none, the row is copied), lens (B,) int64 -> (B, L) fp32 whole frame counts."""
+    _dev(v, has, target, lens)
+    if v.dtype != torch.float32 or v.dim() != 2 or not v.is_contiguous() or not 0 < v.shape[1] <= FIT_MAX_L:
+        raise L.TtskError("duration_fit: needs contiguous fp32 v (B, L) with L <= %d, got %s %s" % (FIT_MAX_L, v.dtype, tuple(v.shape)))
+    _rows_like("duration_fit", v, has=(has, torch.uint8))
+    Bn = v.shape[0]
+    if target.dtype != torch.int32 or lens.dtype != torch.int64 or target.numel() != Bn or lens.numel() != Bn \
+            or not (target.is_contiguous() and lens.is_contiguous()):
+        raise L.TtskError("duration_fit: target must be int32 and lens int64, contiguous with %d entries; got %s (%d) and %s (%d)"
+                          % (Bn, target.dtype, target.numel(), lens.dtype, lens.numel()))
+    out = torch.empty_like(v)
+    check(L.load().ttsk_duration_fit(_ptr(v), _ptr(has), _ptr(target), _ptr(lens), v.shape[1], _ptr(out), Bn, _stream()), "ttsk_duration_fit")
+    return out
+
+
 def scatter_sum(dx, idx, dtable, idx_div=1, skip_row=-1, accumulate=True, defer=None):
     """dtable[v] (+)= sum of the rows of dx whose index is v.  `defer` (the list flush_finalize drains): the embedding-table
     gradients of a backward pass are independent and nothing but the optimiser reads them — queued, they share one launch."""

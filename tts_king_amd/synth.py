@@ -77,7 +77,8 @@ class GraphedSynthesizer:
         return post.clone(), mel_lens.clone()
 
     @torch.no_grad()
-    def mel_ragged(self, speakers, texts, p_control=1.0, e_control=1.0, d_control=1.0, aux=False):
+    def mel_ragged(self, speakers, texts, p_control=1.0, e_control=1.0, d_control=1.0, aux=False, durations=None, pitch=None, energy=None,
+                   target_frames=None):
         """Texts of different lengths in one call, every utterance as the model gives it alone (not as the reference's padded batch
         gives it: DESIGN.md section 12).  speakers: one id or one per utterance; texts: a list of 1-D phoneme-id arrays; each control
         a scalar or one value per utterance.  -> (a list of (T_u, 80) fp32 postnet mels on the device, the frame counts [T_u]).
@@ -87,12 +88,24 @@ class GraphedSynthesizer:
         text or predicted frame count exceeds max_seq_len leaves the batch for `mel`.  An utterance predicted to have no frame at all comes
         back as an empty (0, 80) mel with count 0 (`mel` returns one padding frame there, which is no frame of the utterance either); its
         decoder rows then attend over zero keys in the batched graph, and nothing reads what they produce.  `aux`: also a list of per-utterance dicts
-        (logd, pitch, energy, dur over the utterance's own phonemes, mel = the pre-PostNet mel; None for an utterance that left the batch)."""
+        (logd, pitch, energy, dur over the utterance's own phonemes, mel = the pre-PostNet mel; None for an utterance that left the batch).
+
+        Per-phoneme prosody: a control may also hold, per utterance, an array over its phonemes; `pitch`,
+        `energy`, `durations` set explicit values (per utterance None, a scalar or an array with NaN = not set; a set value is used as
+        is, no control on it) and `target_frames` a frame budget per utterance the durations are fitted to.  A call that uses any of
+        this runs the front with the per-row kernels under ONE more key per shape, ("front", B, L_bucket, "rows"), every input a static
+        device array; a call that uses none of it runs exactly what it ran before.  On that route the aux of an utterance whose frame
+        count passes max_seq_len is filled too; a text of more than max_seq_len phonemes with per-phoneme inputs is refused."""
         m = self.fs2
         m.eval()
         rows = batching.as_id_rows(texts)
         Bn = len(rows)
         spk = batching.per_utterance(speakers.cpu().numpy() if torch.is_tensor(speakers) else speakers, Bn, "speakers", np.int64)
+        if batching.wants_rows(Bn, (p_control, e_control, d_control), (pitch, energy, durations), target_frames):
+            pros = batching.plan_prosody([len(r) for r in rows], p_control, e_control, d_control, pitch, energy, durations, target_frames)
+            mels, lens, extra = [None] * Bn, [0] * Bn, ([None] * Bn if aux else None)
+            self._ragged_rows(rows, spk, pros, list(range(Bn)), mels, lens, extra)
+            return (mels, lens, extra) if aux else (mels, lens)
         ctl = [batching.per_utterance(c, Bn, n) for c, n in ((p_control, "p_control"), (e_control, "e_control"), (d_control, "d_control"))]
         mels, lens, extra = [None] * Bn, [0] * Bn, ([None] * Bn if aux else None)
         self._ragged(rows, spk, ctl, list(range(Bn)), mels, lens, extra)
@@ -134,6 +147,48 @@ class GraphedSynthesizer:
             if extra is not None:
                 extra[i] = {"logd": logd[r, :Lu].clone(), "pitch": pitch[r, :Lu].clone(), "energy": energy[r, :Lu].clone(),
                             "dur": dur.view(Bn, Lp)[r, :Lu].clone(), "mel": mel_pre[r, :n].clone()}
+
+    def _ragged_rows(self, rows, spk, pros, only, mels, lens, extra):
+        """`_ragged` on the per-phoneme front (`FastSpeech2.eval_front_rows`); the back half and its keys are `_ragged`'s."""
+        m, dev = self.fs2, self.fs2.device
+        plan = batching.plan_texts(rows, m.max_seq_len, self.l_bucket, only)
+        for i in plan.solo:
+            ctl = pros.plain(i)
+            if ctl is None:
+                raise ValueError("utterance %d has %d phonemes: per-phoneme prosody (arrays, explicit values, a frame budget) is limited to "
+                                 "texts of at most max_seq_len = %d phonemes" % (i, len(rows[i]), m.max_seq_len))
+            self._solo(rows, spk, [np.full((len(rows),), c, np.float32) for c in ctl], i, mels, lens)
+        if not plan.batch:
+            return
+        Bn, Lp = len(plan.batch), plan.L
+        sel = np.asarray(plan.batch)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+        inputs = (up(spk[sel]), up(plan.ids), up(plan.lens)) + tuple(up(a) for a in pros.padded(plan.batch, Lp))
+        front = lambda s, t, sl, *pr: m.eval_front_rows(s, t, sl, Lp, pr)
+        x3, dur, total, (pitch, energy, logd) = self._get(self._front, batching.rows_key(Bn, Lp), front, inputs)
+        totals = total.cpu().tolist()                        # the path's one host read
+        keep, over, T = batching.plan_frames(totals, m.max_seq_len, self.t_bucket)
+
+        def hand_out(i, r, post, mel_pre, n):
+            Lu = int(plan.lens[r])
+            mels[i], lens[i] = post[:n].clone(), n
+            if extra is not None:
+                extra[i] = {"logd": logd[r, :Lu].clone(), "pitch": pitch[r, :Lu].clone(), "energy": energy[r, :Lu].clone(),
+                            "dur": dur.view(Bn, Lp)[r, :Lu].clone(), "mel": mel_pre[:n].clone()}
+
+        if over:            # past the position table: this utterance's rows of the front, alone through `eval_back` with the exact T and a host-built table
+            d = x3.shape[-1]
+            for r in over:
+                x3_r, dur_r = x3.view(Bn, Lp, d)[r].clone(), dur.view(Bn, Lp)[r:r + 1].clone()
+                mel_pre, post, _, _ = m.eval_back(x3_r, dur_r, Lp, totals[r])
+                hand_out(plan.batch[r], r, post[0], mel_pre[0], totals[r])
+            if keep:        # the others again as their own batch (a smaller B: its own keys)
+                self._ragged_rows(rows, spk, pros, [plan.batch[r] for r in keep], mels, lens, extra)
+            return
+        back = lambda x, dd: m.eval_back_ragged(x, dd, Lp, T)
+        mel_pre, post, _ = self._get(self._back, batching.back_key(Bn, Lp, T), back, (x3, dur))
+        for r, i in enumerate(plan.batch):
+            hand_out(i, r, post[r], mel_pre[r], max(totals[r], 0))
 
     @torch.no_grad()
     def wav(self, mel_bct):
