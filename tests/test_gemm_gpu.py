@@ -313,7 +313,7 @@ def test_grouped_launch_equals_individual_launches(kern):
             res.append(dst)
         if mode == "grouped":
             assert len(q.group) == len(cases)
-        ops.flush_deferred(q)
+        q.flush()
         torch.cuda.synchronize()
         outs[mode] = [r.cpu() for r in res]
     # the same group with its grid capped at 5 workgroups (ttsk_gemm_group_launch_capped: each workgroup walks tiles wg, wg + 5, ...;
@@ -331,10 +331,10 @@ def test_grouped_launch_equals_individual_launches(kern):
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
-        ops.flush_deferred_gemms(q, max_wgs=5, small_too=True)          # small_too: the 128x128 problems go out (uncapped) as well
-    assert not q.group and len(q) > 0                      # the GEMMs went out, their split-K slabs still wait for the reducer
+        q.flush_gemms(max_wgs=5, small_too=True)          # small_too: the 128x128 problems go out (uncapped) as well
+    assert not q.group and len(q.reduce) > 0                      # the GEMMs went out, their split-K slabs still wait for the reducer
     torch.cuda.current_stream().wait_stream(side)
-    ops.flush_deferred(q)
+    q.flush()
     torch.cuda.synchronize()
     for a, r in zip(outs["single"], res):
         assert torch.equal(a, r.cpu())

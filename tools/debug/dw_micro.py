@@ -53,7 +53,7 @@ def run():
         else:
             ops.linear_dw(dy, x, dst, defer=q, accumulate=False)
     n = len(q.group)
-    ops.flush_deferred(q)
+    q.flush()
     return n
 
 

@@ -34,7 +34,7 @@ def grouped():
     q = ops.DeferQueue(group_gemms=True)
     for dy, x, dst in probs:
         ops.conv1d_dw(dy, x, dst, k=9, defer=q, accumulate=False)
-    ops.flush_deferred(q)
+    q.flush()
 
 
 timed(grouped, "grouped GEMM (9 problems per weight)")

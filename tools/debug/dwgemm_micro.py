@@ -45,7 +45,7 @@ def grouped(ps):
             ops.linear_dw(dy.view(B * T, -1), x.view(B * T, -1), dst.view(dst.shape[0], dst.shape[2]), defer=q, accumulate=False)
         else:
             ops.conv1d_dw(dy, x, dst, k=dst.shape[1], defer=q, accumulate=False)
-    ops.flush_deferred(q)
+    q.flush()
 
 
 def dwg(ps, splits):

@@ -79,8 +79,8 @@ class _GroupNotifier:
         self.ready = getattr(getattr(on_bucket, "__self__", None), "ready", None)
         self.pos = 0
         self.flushes = 0
-        # `mark(name)` (the "side" / "late" schedules): instead of flushing and announcing now, the caller records where the queues
-        # stand and does both later, bucket by bucket (FastSpeech2._launch_dw_side_buckets / _flush_param_grads)
+        # `mark(name)` (the "side" / "late" schedules): instead of flushing and announcing now, the caller notes the group and does
+        # both later (FastSpeech2._launch_dw_side_buckets / the end of backward_native)
         self.mark = mark
 
     def done(self, name):
@@ -142,7 +142,7 @@ class FastSpeech2(nn.Module):
         self._shadow_version = -1
         self._anchor = torch.zeros((), requires_grad=True)
         self._ctx = None
-        self._deferred = None           # split-K slabs awaiting the batched reducer (backward only)
+        self._deferred = None           # the step's ops.DeferQueue: weight-gradient problems and split-K slabs awaiting their launches (backward only)
         self._deferred_fin = None       # gradient column-sum partials awaiting the batched finalize
         # The FFT blocks' w_1 forward, q|k|v projection, fc and w_2 input gradients, and the PostNet's 512 -> 512 convs (forward and
         # input gradient) run on the window kernel (csrc/ffn_conv.hip).  It wants the weights in MFMA-fragment order (1 KiB contiguous
@@ -179,8 +179,6 @@ class FastSpeech2(nn.Module):
         # was deleted in round 4; without a second stream, dw_side_wgs = 0, buckets are still flushed one by one as they complete.)
         self.dp_schedule = switches.get("TTSK_DP_SCHEDULE")
         self._fin_side = None
-        self._dp_keep = None
-        self._fin_pending = False
         # Training with targets: the three VariancePredictors' outputs feed nothing but the loss (the embeddings are picked by the TARGET
         # pitch / energy, the length regulator takes the TARGET durations: modules.py:158-205), and their backward needs nothing but the
         # loss's gradients until its last step.  Both run on a stream of their own: the forward beside the decoder's first block, the
@@ -1240,17 +1238,16 @@ class FastSpeech2(nn.Module):
         self._dw_side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self._dw_side):
             ops.stamp("side.start")
-            ops.flush_deferred_gemms(self._deferred, max_wgs=self.dw_side_wgs, frac=1.0 if everything else self.dw_side_frac,
-                                     small_too=everything)
+            self._deferred.flush_gemms(max_wgs=self.dw_side_wgs, frac=1.0 if everything else self.dw_side_frac, small_too=everything)
             ops.stamp("side.end")
         self._dw_side_pending = True
 
     def _mark_bucket(self, name):
         """The notifier's `mark` in the "side" / "late" data-parallel schedules: group `name` is complete once everything queued so far
-        has been flushed — remember where the GEMM and reducer queues stand."""
-        self._dp_marks.append((name, len(self._deferred.group), len(self._deferred), len(self._deferred.dwconv)))
+        has been flushed — remember it for the announcement behind that flush."""
+        self._dp_marks.append(name)
 
-    def _launch_dw_side_buckets(self, on_bucket, ready):
+    def _launch_dw_side_buckets(self, on_bucket):
         """Data-parallel "side" schedule, after the decoder's backward: exactly the single-GPU schedule's second-stream work (`_launch_dw_side`:
         w_1's gradients on dwconv, the other 256-multiple ones on dwgemm with their slab reducer, the few grouped problems, the column
         sums — everything queued so far, so every PostNet / mel_linear / decoder gradient is final when it ends), and behind it, FROM THAT
@@ -1262,15 +1259,15 @@ class FastSpeech2(nn.Module):
         if q.group or q.dwconv or q.dwgemm:
             # a problem still queued would write its gradient (or its split-K slabs) AFTER the reduce / all-reduce below read them
             raise RuntimeError("data-parallel side schedule: %d grouped / %d dwconv / %d dwgemm weight-gradient problems still queued "
-                               "before the buckets are announced" % (len(q.group or ()), len(q.dwconv), len(q.dwgemm)))
+                               "before the buckets are announced" % (len(q.group), len(q.dwconv), len(q.dwgemm)))
         # the split-K slabs of the grouped problems just launched: summed here, not with the final flush (the buckets must be final)
         marks, self._dp_marks = self._dp_marks, []
         with torch.cuda.stream(self._dw_side):
-            ops.flush_deferred_prefix(self._deferred, 0, len(self._deferred))
+            q.reduce_queued()
             if self._deferred_fin:                                  # the column sums queued so far belong to these buckets too
-                self._dp_keep = (self._dp_keep or []) + [k for _, k in self._deferred_fin]
+                q.keep.extend(k for _, k in self._deferred_fin)     # (read on this stream: alive until the queue's final flush)
                 ops.flush_finalize(self._deferred_fin)
-            for name, _, _, _ in marks:
+            for name in marks:
                 on_bucket(name)               # groups in completion order: a bucket goes out when its lowest group has been announced
         self._dw_side_pending = True
 
@@ -1281,7 +1278,7 @@ class FastSpeech2(nn.Module):
             # only activations and gradients the main chain produced: they run now, beside the side stream; the encoder-side dW group
             # queues behind the first one on the side stream; the join comes last, before the split-K reducer.
             cur = torch.cuda.current_stream()
-            launch = ops.upload_deferred_gemms(self._deferred, max_wgs=0, with_dwconv=False, with_dwgemm=False)     # the tables now, on this stream
+            launch = self._deferred.upload_gemms()     # the tables now, on this stream
             # Three branches from here (a replayed graph runs at most three queues side by side): the encoder blocks' w_1 gradients
             # (dwconv, 128 workgroups) and behind them the few grouped problems (80-channel outputs) on one stream; the encoder side's
             # dwgemm problems on the side stream (behind the decoder's work there); the column sums on this one.
@@ -1289,26 +1286,22 @@ class FastSpeech2(nn.Module):
                 self._fin_side = torch.cuda.Stream(device=self.device)
             self._fin_side.wait_stream(cur)
             with torch.cuda.stream(self._fin_side):
-                ops.flush_dwconv(self._deferred)
+                self._deferred.flush_dwconv()
                 ops.stamp("fin.dwconv")
                 launch()
                 ops.stamp("fin.small")
-            self._fin_pending = True
             self._dw_side.wait_stream(cur)
             with torch.cuda.stream(self._dw_side):
-                ops.flush_dwgemm(self._deferred)
+                self._deferred.flush_dwgemm()
                 ops.stamp("fin.dwgemm")
             ops.flush_finalize(self._deferred_fin)
             ops.stamp("fin.colsum")
             self._finalize_loss()       # the two-stream loss's values: behind the column sums, on the branch of the final phase that ends first
             cur.wait_stream(self._dw_side)
-            if getattr(self, "_fin_pending", False):
-                cur.wait_stream(self._fin_side)
-                self._fin_pending = False
+            cur.wait_stream(self._fin_side)
             self._dw_side_pending = False
-        ops.flush_deferred(self._deferred)
+        self._deferred.flush()
         ops.flush_finalize(self._deferred_fin)
-        self._dp_keep = None
 
     @staticmethod
     def _stack3(dlogd, dpitch, denergy):
@@ -1426,7 +1419,7 @@ class FastSpeech2(nn.Module):
         if pred_dxin is not None:
             torch.cuda.current_stream().wait_stream(self._pred_stream)    # long done; its queued dW work joins the second stream's
         if dp_side and self.dp_schedule == "side":
-            self._launch_dw_side_buckets(on_bucket, notifier.ready)
+            self._launch_dw_side_buckets(on_bucket)
         elif self.dw_side_wgs > 0:
             self._launch_dw_side()
         # ---- length regulator: segment sums (the position table has no parameters)
@@ -1465,7 +1458,7 @@ class FastSpeech2(nn.Module):
         self._flush_param_grads()
         ops.stamp("bwd.flushed")
         if dp_side:
-            for name, _, _, _ in self._dp_marks:    # everything is in the buffer now: the remaining buckets, in completion order
+            for name in self._dp_marks:    # everything is in the buffer now: the remaining buckets, in completion order
                 on_bucket(name)
             self._dp_marks = []
         self._finalize_loss()       # (a schedule without the second stream: here, where this stream has seen both halves of the loss)

@@ -42,6 +42,24 @@ GEMM_TRACE = None   # bench.py sets this to a list: every ttsk_gemm launch is th
                     # (and, through `_family`, every launch of the other MFMA kernel families and of the step's HBM-bound passes)
 
 
+def _traced(launch, describe):
+    """launch(), and when GEMM_TRACE is set, between two HIP events on the current stream: (e0, e1, *describe()) joins the trace,
+    describe() -> (algorithmic FLOPs, kind, shape).  The one place that brackets a launch; no cost beyond two closures otherwise."""
+    if GEMM_TRACE is None:
+        return launch()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = launch()
+    e1.record()
+    GEMM_TRACE.append((e0, e1) + tuple(describe()))
+    return out
+
+
+def _count(key):
+    if LAUNCH_COUNTS is not None:
+        LAUNCH_COUNTS[key] = LAUNCH_COUNTS.get(key, 0) + 1
+
+
 def _family(kind, flops):
     """Decorator: when GEMM_TRACE is set, bracket the wrapped launch with HIP events on its stream and record (events, algorithmic
     FLOPs = flops(*args, **kwargs), family name) — bench.py's per-family roofline (`roofline.families`).  No cost otherwise."""
@@ -50,14 +68,8 @@ def _family(kind, flops):
 
         @functools.wraps(fn)
         def wrapped(*a, **kw):
-            if GEMM_TRACE is None:
-                return fn(*a, **kw)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            out = fn(*a, **kw)
-            e1.record()
-            GEMM_TRACE.append((e0, e1, float(flops(*a, **kw)), kind, (0, 0, 0, 1, 1, 0, fn.__name__)))      # (last: the wrapper, for bench.py's per-instance rows)
-            return out
+            return _traced(lambda: fn(*a, **kw),
+                           lambda: (float(flops(*a, **kw)), kind, (0, 0, 0, 1, 1, 0, fn.__name__)))      # (last: the wrapper, for bench.py's per-instance rows)
         return wrapped
     return deco
 
@@ -87,17 +99,6 @@ class Slabs:
         self.ws, self.splits, self.stride = ws, splits, stride
 
 
-class DeferQueue(list):
-    """What `gemm(defer=...)` collects during a backward pass: split-K reduce items (the list itself) and, in `.group`, whole
-    weight-gradient GEMMs that run as grouped launches at `flush_deferred` (nothing but the optimiser reads their results)."""
-
-    def __init__(self, group_gemms=True):
-        super().__init__()
-        self.group = [] if group_gemms else None
-        self.dwconv = []        # weight gradients of convs with taps: (dy, x, dst, lens, accumulate) for dwconv_batch (csrc/dwconv.hip)
-        self.dwgemm = []        # ... of Linear / k = 1 / PostNet layers with 256-multiple channels: (dy, x, dst, lens, accumulate, splits)
-
-
 class GemmGroup:
     """Independent GEMMs (same operand layout per launch) that run as one grouped launch: `gemm(..., group=g)` ... `g.flush()`.
     Problems are launched per (operand layout, tile configuration): at most a handful of grids."""
@@ -110,14 +111,11 @@ class GemmGroup:
         self.keep = []
 
 
-def flush_group(descs, keep, max_wgs=0, upload_only=False):
-    """Grouped launches (ttsk_gemm_group_*) of the queued descriptors, one per operand layout; `keep` holds their tensors.
-    max_wgs > 0 caps the grid of the 256x128 configuration (ttsk_gemm_group_launch_capped).
-    upload_only: only the tables go to the device (current stream); returns a function that issues the launches (on the stream
-    current when it is called, which the caller has ordered behind this one)."""
+def _group_tables(descs, keep):
+    """The queued descriptors as grouped-launch tables, one per (operand layout, tile configuration): yields (host table, device
+    table, FLOPs, trace kind, trace shape).  `keep` holds the descriptors' tensors and receives the device tables."""
     if not descs:
-        return (lambda streams=None: None) if upload_only else None
-    pending = []
+        return
     lib = L.load()
     by_layout = {}
     for d in descs:
@@ -135,86 +133,37 @@ def flush_group(descs, keep, max_wgs=0, upload_only=False):
         total = C.c_int32(0)
         check(lib.ttsk_gemm_group_build(arr, n, host, C.byref(total)), "ttsk_gemm_group_build")
         table = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # filled by group_launch through kernel arguments
-        if upload_only:
-            check(lib.ttsk_gemm_group_upload(host, C.c_void_p(table.data_ptr()), _stream()), "ttsk_gemm_group_upload")
-            fl = sum(2.0 * d.M * d.N * d.K * max(d.taps, 1) * d.nz1 * d.nz2 for d in ds)
-            kind = ("TT" if ds[0].flags & A_TR else ("NT_btr" if ds[0].flags & B_TR else "NT")) + "%dg" % ds[0].kernel
-            pending.append((host, table, fl, kind, (n, 0, 0, 1, 1, int(total.value))))
-            keep.append(table)
-            if LAUNCH_COUNTS is not None:
-                LAUNCH_COUNTS["grouped_gemm"] = LAUNCH_COUNTS.get("grouped_gemm", 0) + 1
-            continue
-        if GEMM_TRACE is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        check(lib.ttsk_gemm_group_launch_capped(host, C.c_void_p(table.data_ptr()), int(max_wgs), _stream()), "ttsk_gemm_group_launch")
-        if LAUNCH_COUNTS is not None:
-            LAUNCH_COUNTS["grouped_gemm"] = LAUNCH_COUNTS.get("grouped_gemm", 0) + 1
-        if GEMM_TRACE is not None:
-            e1.record()
-            fl = sum(2.0 * d.M * d.N * d.K * max(d.taps, 1) * d.nz1 * d.nz2 for d in ds)
-            kind = "TT" if ds[0].flags & A_TR else ("NT_btr" if ds[0].flags & B_TR else "NT")
-            GEMM_TRACE.append((e0, e1, fl, kind + "%dg" % ds[0].kernel, (n, 0, 0, 1, 1, int(total.value))))
         keep.append(table)
+        fl = sum(2.0 * d.M * d.N * d.K * max(d.taps, 1) * d.nz1 * d.nz2 for d in ds)
+        kind = ("TT" if ds[0].flags & A_TR else ("NT_btr" if ds[0].flags & B_TR else "NT")) + "%dg" % ds[0].kernel
+        _count("grouped_gemm")
+        yield host, table, fl, kind, (n, 0, 0, 1, 1, int(total.value))
     descs.clear()
-    if upload_only:
-        def launch(streams=None):
-            """Issue the grouped launches whose tables are uploaded.  `streams`: torch streams (each already ordered behind the
-            uploads by the caller) to spread the launches over, one per launch in turn — they are independent problems."""
-            for i, (host, table, fl, kind, shape) in enumerate(pending):
-                ctx = torch.cuda.stream(streams[i % len(streams)]) if streams else None
-                if ctx is not None:
-                    ctx.__enter__()
-                try:
-                    _launch_uploaded(host, table, fl, kind, shape)
-                finally:
-                    if ctx is not None:
-                        ctx.__exit__(None, None, None)
-
-        def _launch_uploaded(host, table, fl, kind, shape):
-            if GEMM_TRACE is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            check(lib.ttsk_gemm_group_launch_uploaded(host, C.c_void_p(table.data_ptr()), int(max_wgs), _stream()), "ttsk_gemm_group_launch_uploaded")
-            if GEMM_TRACE is not None:
-                e1.record()
-                GEMM_TRACE.append((e0, e1, fl, kind, shape))
-        return launch
 
 
-def upload_deferred_gemms(items, max_wgs=0, with_dwconv=True, with_dwgemm=True):
-    """flush_deferred_gemms in two parts: the tables now (current stream), the launches when the returned function is called (the
-    queued dwconv problems carry their table in the launch's arguments: with_dwconv, they go with the launches)."""
-    group = getattr(items, "group", None)
-    launch = flush_group(group, getattr(items, "_keep"), max_wgs, upload_only=True) if group else (lambda streams=None: None)
-
-    def both(streams=None):
-        if with_dwconv:
-            flush_dwconv(items)
-        if with_dwgemm:
-            flush_dwgemm(items)
-        launch(streams)
-    return both
+def flush_group(descs, keep, max_wgs=0):
+    """Grouped launches (ttsk_gemm_group_*) of the queued descriptors on the current stream, one per operand layout; `keep` holds
+    their tensors.  max_wgs > 0 caps the grid of the 256x128 configuration (ttsk_gemm_group_launch_capped)."""
+    lib = L.load()
+    for host, table, fl, kind, shape in _group_tables(descs, keep):
+        _traced(lambda: check(lib.ttsk_gemm_group_launch_capped(host, C.c_void_p(table.data_ptr()), int(max_wgs), _stream()), "ttsk_gemm_group_launch"),
+                lambda: (fl, kind, shape))
 
 
-def flush_dwconv(items, n=None):
-    """The (first n) queued conv weight gradients as ttsk_dwconv_batch launches (12 problems each, one kernel size each) on the
-    current stream.  Their operands stay alive in the queue's keep list until its final flush."""
-    q = getattr(items, "dwconv", None)
-    if not q:
-        return
-    now = q if n is None else q[:n]
-    rest = [] if n is None else q[n:]
-    if not hasattr(items, "_keep"):
-        items._keep = []
-    by_k = {}
-    for it in now:
-        by_k.setdefault(it[2].shape[1], []).append(it)
-        items._keep.extend(t for t in it[:4] if t is not None)
-    for lst in by_k.values():
-        for i in range(0, len(lst), 12):
-            dwconv_batch(lst[i:i + 12])
-    q[:] = rest
+def upload_group(descs, keep):
+    """flush_group in two parts: only the tables go to the device now (current stream); returns a function that issues the
+    launches (uncapped) on the stream current when it is called, which the caller has ordered behind this one."""
+    lib = L.load()
+    pending = []
+    for host, table, fl, kind, shape in _group_tables(descs, keep):
+        check(lib.ttsk_gemm_group_upload(host, C.c_void_p(table.data_ptr()), _stream()), "ttsk_gemm_group_upload")
+        pending.append((host, table, fl, kind, shape))
+
+    def launch():
+        for host, table, fl, kind, shape in pending:
+            _traced(lambda: check(lib.ttsk_gemm_group_launch_uploaded(host, C.c_void_p(table.data_ptr()), 0, _stream()), "ttsk_gemm_group_launch_uploaded"),
+                    lambda: (fl, kind, shape))
+    return launch
 
 
 DWG_TARGET_STEPS = (72, 72)   # K steps per workgroup: k = 1, taps (3 ranges at B = 16, T = 423: the measured optimum of 2 / 3 / 4)
@@ -235,34 +184,109 @@ def dwgemm_splits(Bsz, S, k=1):
     return max(1, min(Bsz, (steps + target_steps // 2) // target_steps))
 
 
-def flush_dwgemm(items, reduce_now=False, max_wgs=0):
-    """The queued dwgemm problems as ttsk_dwgemm_batch launches on the current stream; the reducer items of the split ones join the
-    queue's split-K items (summed by flush_deferred's batched reducer), or are summed right here (reduce_now)."""
-    q = getattr(items, "dwgemm", None)
-    if not q:
-        return
-    if not hasattr(items, "_keep"):
-        items._keep = []
-    for it in q:
-        items._keep.extend(t for t in it[:4] if t is not None)
-    red = dwgemm_batch(q, max_wgs)
-    q[:] = []
-    if reduce_now and red:
-        arr = (L.ReduceItem * len(red))(*[r for r, _ in red])
-        check(L.load().ttsk_gemm_reduce_batch(arr, len(red), _stream()), "ttsk_gemm_reduce_batch")
-        items._keep.extend(ws for _, ws in red)
-        if LAUNCH_COUNTS is not None:
-            LAUNCH_COUNTS["reduce_batch"] = LAUNCH_COUNTS.get("reduce_batch", 0) + 1
-    else:
-        items.extend(red)
+class DeferQueue:
+    """The weight-gradient work a backward pass puts off (nothing but the optimiser reads its results), in the order it was queued:
+    `group`   whole weight-gradient GEMMs (GemmDesc) for grouped launches — what `gemm(defer=...)` queues;
+              group_gemms=False: it launches them one by one instead and queues only their split-K reduce items;
+    `dwconv`  weight gradients of convs with taps: (dy, x, dst, lens, accumulate) for dwconv_batch (csrc/dwconv.hip);
+    `dwgemm`  ... of Linear / k = 1 / PostNet layers with 256-multiple channels: (dy, x, dst, lens, accumulate, splits) (csrc/dwgemm.hip);
+    `reduce`  (ReduceItem, slabs) of every split-K problem, for the batched reducer;
+    `keep`    every tensor a launch of this queue reads or writes (operands, slabs, tables): alive until `flush`, because the launches
+              may run on other streams than the one that allocated them and the caching allocator would hand them out again.
+    The three kinds of problems stay three lists: each flush below states which it launches, on the stream current at the call."""
+
+    def __init__(self, group_gemms=True):
+        self.group_gemms = group_gemms
+        self.group, self.dwconv, self.dwgemm, self.reduce, self.keep = [], [], [], [], []
+
+    def _reduce(self, items):
+        """One ttsk_gemm_reduce_batch launch over `items` [(ReduceItem, slabs)] on the current stream; the slabs join `keep`."""
+        arr = (L.ReduceItem * len(items))(*[it for it, _ in items])
+        check(L.load().ttsk_gemm_reduce_batch(arr, len(items), _stream()), "ttsk_gemm_reduce_batch")
+        _count("reduce_batch")
+        self.keep.extend(ws for _, ws in items)
+
+    def flush_dwconv(self):
+        """The queued conv weight gradients as ttsk_dwconv_batch launches (12 problems each, one kernel size each) on the current stream."""
+        by_k = {}
+        for it in self.dwconv:
+            by_k.setdefault(it[2].shape[1], []).append(it)
+            self.keep.extend(t for t in it[:4] if t is not None)
+        for lst in by_k.values():
+            for i in range(0, len(lst), 12):
+                dwconv_batch(lst[i:i + 12])
+        self.dwconv.clear()
+
+    def flush_dwgemm(self, reduce_now=False, max_wgs=0):
+        """The queued dwgemm problems as ttsk_dwgemm_batch launches on the current stream (grid capped at max_wgs when > 0); the reduce
+        items of the split ones join `reduce` (summed by a later reduce_queued / flush), or are summed right here (reduce_now)."""
+        if not self.dwgemm:
+            return
+        for it in self.dwgemm:
+            self.keep.extend(t for t in it[:4] if t is not None)
+        red = dwgemm_batch(self.dwgemm, max_wgs)
+        self.dwgemm.clear()
+        if reduce_now and red:
+            self._reduce(red)
+        else:
+            self.reduce.extend(red)
+
+    def flush_gemms(self, max_wgs=0, frac=1.0, small_too=False):
+        """Everything but the reducer, on the current stream: the queued dwconv and dwgemm problems, all of them (dwgemm's grid capped
+        at max_wgs workgroups when > 0, and its slabs then summed right behind it: this is the side stream's launch, which has the
+        time), then the queued grouped GEMMs; their split-K slabs stay queued for reduce_queued / flush.  frac < 1: only about that
+        fraction of the grouped FLOPs (the problems queued first); the rest stays queued for the next flush.
+        A capped launch exists for the 256x128 configuration only: with max_wgs > 0 the few 128x128 problems (80-row / 80-column
+        outputs: mel_linear, the PostNet's first and last conv) go behind it uncapped (small_too: 168 workgroups, two per CU) or
+        stay queued for the final flush."""
+        self.flush_dwconv()
+        stamp("dw.dwconv")
+        self.flush_dwgemm(reduce_now=max_wgs > 0, max_wgs=max_wgs)
+        stamp("dw.dwgemm")
+        now, small, later = list(self.group), [], []
+        if max_wgs > 0:
+            now, small = [d for d in self.group if d.kernel == 2], [d for d in self.group if d.kernel != 2]
+        if frac < 1.0:
+            fl = [2.0 * d.M * d.N * d.K * max(d.taps, 1) * d.nz1 * d.nz2 for d in now]
+            want, acc, n = frac * sum(fl), 0.0, 0
+            while n < len(now) and acc < want:
+                acc += fl[n]
+                n += 1
+            now, later = now[:n], now[n:]
+        flush_group(now, self.keep, max_wgs)
+        if small_too:
+            flush_group(small, self.keep)
+        self.group[:] = later if small_too else later + small
+
+    def upload_gemms(self):
+        """The tables of the queued grouped GEMMs to the device now (current stream); returns the function that launches them, on the
+        stream current when it is called (ordered behind this one by the caller).  The dwconv / dwgemm problems stay queued."""
+        return upload_group(self.group, self.keep)
+
+    def reduce_queued(self):
+        """The batched reducer over every split-K item queued so far, on the current stream: the gradients of the problems launched
+        so far are final behind it (the data-parallel "side" schedule announces its buckets there)."""
+        if self.reduce:
+            self._reduce(self.reduce)
+            self.reduce.clear()
+
+    def flush(self):
+        """Whatever is still queued, on the current stream — dwconv, dwgemm, the grouped GEMMs, then one ttsk_gemm_reduce_batch launch
+        for the split-K slabs — and the end of the queue's keep list: the caller has joined every stream the queue launched on."""
+        self.flush_dwconv()
+        self.flush_dwgemm()
+        flush_group(self.group, self.keep)
+        self.reduce_queued()
+        self.keep = []
 
 
 def queue_dw(defer, dy, x, dst, lens, accumulate, k=1, use_dwgemm=True):
-    """Queue the weight gradient dst (Cout, k, Cin) (+)= dy (B,S,Cout)^T x (B,S,Cin) [taps: "same" padding]: on the 256x256-tile kernel
-    (dwgemm.hip) when the shape allows, else as a grouped GEMM.  `lens`: rows of each utterance that carry a gradient (or None)."""
+    """Queue the weight gradient dst (Cout, k, Cin) (+)= dy (B,S,Cout)^T x (B,S,Cin) [taps: "same" padding] in the DeferQueue `defer`:
+    on the 256x256-tile kernel (dwgemm.hip) when the shape allows, else as a grouped GEMM.  `lens`: rows of each utterance that carry
+    a gradient (or None)."""
     Bsz, S, Cout = dy.shape
     Cin = x.shape[2]
-    if (use_dwgemm and getattr(defer, "group", None) is not None and dy.dtype == bf16 and x.dtype == bf16 and dwgemm_supported(Cout, Cin, k)
+    if (use_dwgemm and defer.group_gemms and dy.dtype == bf16 and x.dtype == bf16 and dwgemm_supported(Cout, Cin, k)
             and dst.is_contiguous()):
         sp = dwgemm_splits(Bsz, S, k)
         if (Bsz + sp - 1) // sp <= 64:
@@ -273,92 +297,6 @@ def queue_dw(defer, dy, x, dst, lens, accumulate, k=1, use_dwgemm=True):
     else:
         conv1d_dw(dy, x, dst, k=k, defer=defer, accumulate=accumulate)
 
-
-def flush_deferred_gemms(items, max_wgs=0, frac=1.0, small_too=False):
-    """Only the grouped weight-gradient GEMMs queued in `items` so far, as grouped launches on the current stream (grid capped at
-    max_wgs workgroups when > 0); their split-K slabs stay queued for `flush_deferred`'s reducer launch.  frac < 1: only about
-    that fraction of the queued FLOPs (the problems queued first); the rest stays queued for the next flush.  The queued dwconv
-    and dwgemm problems go first, all of them (capped likewise; with max_wgs their slabs are summed right behind them: this is the
-    side stream's launch, which has the time)."""
-    flush_dwconv(items)
-    stamp("dw.dwconv")
-    flush_dwgemm(items, reduce_now=max_wgs > 0, max_wgs=max_wgs)
-    stamp("dw.dwgemm")
-    group = getattr(items, "group", None)
-    if not group:
-        return
-    if max_wgs > 0:
-        # a capped launch exists for the 256x128 configuration only; the few 128x128 problems (80-row / 80-column outputs: mel_linear, the
-        # PostNet's first and last conv) go behind it uncapped (small_too: 168 workgroups, two per CU) or stay queued for the final flush
-        small = [d for d in group if d.kernel != 2]
-        if small:
-            group[:] = [d for d in group if d.kernel == 2]
-            try:
-                if group:
-                    flush_deferred_gemms(items, max_wgs, frac)
-            finally:
-                group.extend(small)
-            if small_too:
-                now = [d for d in group if d.kernel != 2]
-                group[:] = [d for d in group if d.kernel == 2]
-                flush_group(now, getattr(items, "_keep"), 0)
-            return
-    if frac < 1.0:
-        fl = [2.0 * d.M * d.N * d.K * max(d.taps, 1) * d.nz1 * d.nz2 for d in group]
-        want, acc, n = frac * sum(fl), 0.0, 0
-        while n < len(group) and acc < want:
-            acc += fl[n]
-            n += 1
-        now, later = group[:n], group[n:]
-        flush_group(now, getattr(items, "_keep"), max_wgs)
-        group[:] = later
-        return
-    flush_group(group, getattr(items, "_keep"), max_wgs)
-
-
-def flush_deferred_prefix(items, n_group, n_reduce, max_wgs=0, n_dwconv=0):
-    """The first `n_dwconv` queued dwconv problems, the first `n_group` queued weight-gradient GEMMs as grouped launches (grid capped at
-    max_wgs when > 0) and then the batched reducer for the first `n_reduce` queued split-K items, on the current stream; all are
-    removed from the queue.  The data-parallel "side" schedule flushes the queue bucket by bucket this way
-    (FastSpeech2._launch_dw_side_buckets)."""
-    if n_dwconv > 0:
-        flush_dwconv(items, n_dwconv)
-    group = getattr(items, "group", None)
-    if group and n_group > 0:
-        now = group[:n_group]
-        del group[:n_group]
-        flush_group(now, getattr(items, "_keep"), max_wgs)
-    if n_reduce > 0:
-        head = items[:n_reduce]
-        del items[:n_reduce]
-        arr = (L.ReduceItem * len(head))(*[it for it, _ in head])
-        check(L.load().ttsk_gemm_reduce_batch(arr, len(head), _stream()), "ttsk_gemm_reduce_batch")
-        if LAUNCH_COUNTS is not None:
-            LAUNCH_COUNTS["reduce_batch"] = LAUNCH_COUNTS.get("reduce_batch", 0) + 1
-        if hasattr(items, "_keep"):
-            items._keep.extend(ws for _, ws in head)       # the slabs stay alive until the queue's final flush
-
-
-def flush_deferred(items):
-    """The queued weight-gradient GEMMs as grouped launches, then one ttsk_gemm_reduce_batch launch (per 64 items) for the
-    split-K slabs collected in `items` (see gemm(defer=...))."""
-    flush_dwconv(items)
-    flush_dwgemm(items)
-    group = getattr(items, "group", None)
-    if group:
-        keep = getattr(items, "_keep")
-        flush_group(group, keep)
-    if not items:
-        if group is not None:
-            items._keep = []
-        return
-    arr = (L.ReduceItem * len(items))(*[it for it, _ in items])
-    check(L.load().ttsk_gemm_reduce_batch(arr, len(items), _stream()), "ttsk_gemm_reduce_batch")
-    if LAUNCH_COUNTS is not None:
-        LAUNCH_COUNTS["reduce_batch"] = LAUNCH_COUNTS.get("reduce_batch", 0) + 1
-    items.clear()
-    if group is not None:
-        items._keep = []
 
 
 def plan(d):
@@ -374,8 +312,9 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, flags=0, alpha=1.0, bias=None, R=No
          in_slope=0.0, out_slope=0.0, defer=None, group=None, s_bias1=0, raw=False):
     """Raw descriptor-level call of ttsk_gemm (see include/ttsk.h).  A/B/Cout may be views: the data pointer of
     the view is the operand origin.  splits / kernel = 0 let the library plan (tile configuration, split-K factor);
-    the split-K workspace is allocated here (the C library never allocates).  `defer`: a list — a split-K weight-
-    gradient GEMM then leaves its slabs un-reduced and appends a reduce item to it (see flush_deferred).  `group`: a
+    the split-K workspace is allocated here (the C library never allocates).  `defer`: a DeferQueue — a plain weight-
+    gradient GEMM is then queued there whole for a grouped launch (group_gemms=False: launched here), and when it splits K it
+    leaves its slabs un-reduced and queues a reduce item (see DeferQueue).  `group`: a
     GemmGroup — independent problems collected there run as ONE grouped launch at `group.flush()`.  `raw`: leave the fp32
     partial tiles [splits][M][N] un-reduced and without epilogue (TTSK_GEMM_RAW_SLABS); returns Slabs(ws, splits, M*N) for
     layernorm_bwd(slabs=...) — `Cout` may be None."""
@@ -413,8 +352,11 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, flags=0, alpha=1.0, bias=None, R=No
         # grouped launches exist for the 128x128 and 256x128 tiles only: plan again with the 128x128 tile
         d.kernel, d.splits = 1, user_splits
         kernel, splits, ws_bytes = plan(d)
-    grouped_dw = (defer is not None and getattr(defer, "group", None) is not None and nz1 == 1 and (flags & C_F32)
-                  and not (flags & ~(A_TR | B_TR | C_F32 | ACCUM_C)) and bias is None and A.dtype != f16)
+    # a plain weight-gradient GEMM: fp32 output (+= or =) and nothing else — no epilogue, no bias, no first batch index, bf16 operands
+    # (an fp16 A sets F16).  Only such a problem is deferred: its split-K slabs wait for the queue's reducer, and the problem itself
+    # for a grouped launch when the queue groups
+    plain_dw = defer is not None and nz1 == 1 and bool(flags & C_F32) and not (flags & ~(A_TR | B_TR | C_F32 | ACCUM_C)) and bias is None
+    grouped_dw = plain_dw and defer.group_gemms
     if grouped_dw and user_splits == 0 and user_kernel == 0:
         # The planner splits K until ONE problem fills the chip (a 256x256 weight gradient over 6768 rows: 36 ways, 36 fp32
         # slabs to write and to reduce).  In a grouped launch the other problems fill it: ~28 (128x128 tiles) / ~36 (256x128) K steps per workgroup keep the
@@ -430,12 +372,12 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, flags=0, alpha=1.0, bias=None, R=No
     if ws_bytes > 0:
         ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=A.device)
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws_bytes
-        if defer is not None and nz1 == 1 and (flags & C_F32) and not (flags & ~(A_TR | B_TR | C_F32 | ACCUM_C)) and bias is None:
+        if plain_dw:
             d.flags = flags | DEFER_REDUCE
             it = L.ReduceItem()
             it.ws, it.C, it.M, it.N, it.ldc, it.nz, it.splits = ws.data_ptr(), Cout.data_ptr(), M, N, ldc, nz2, splits
             it.accumulate, it.sC2, it.alpha = int(bool(flags & ACCUM_C)), sC[1], alpha
-            defer.append((it, ws))
+            defer.reduce.append((it, ws))
     if raw:
         check(L.load().ttsk_gemm(C.byref(d), _stream()), "ttsk_gemm")
         return Slabs(ws, splits, M * N * nz1 * nz2)
@@ -444,21 +386,13 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, flags=0, alpha=1.0, bias=None, R=No
         group.keep.extend(t for t in (A, B, Cout, ws, bias, R, G, C2) if t is not None)
         return Cout
     if grouped_dw:
-        # a weight-gradient GEMM: queued whole, launched with the others at flush_deferred
+        # a weight-gradient GEMM: queued whole, launched with the others by one of the queue's flushes
         defer.group.append(d)
-        if not hasattr(defer, "_keep"):
-            defer._keep = []
-        defer._keep.extend(t for t in (A, B, Cout, ws) if t is not None)
+        defer.keep.extend(t for t in (A, B, Cout, ws) if t is not None)
         return Cout
-    if GEMM_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(L.load().ttsk_gemm(C.byref(d), _stream()), "ttsk_gemm")
-        e1.record()
-        kind = "TT" if flags & A_TR else ("NT_btr" if flags & B_TR else "NT")
-        GEMM_TRACE.append((e0, e1, 2.0 * M * N * K * max(taps, 1) * nz1 * nz2, kind + str(kernel), (M, N, K, max(taps, 1), nz1 * nz2, splits)))
-        return Cout
-    check(L.load().ttsk_gemm(C.byref(d), _stream()), "ttsk_gemm")
+    _traced(lambda: check(L.load().ttsk_gemm(C.byref(d), _stream()), "ttsk_gemm"),
+            lambda: (2.0 * M * N * K * max(taps, 1) * nz1 * nz2, ("TT" if flags & A_TR else ("NT_btr" if flags & B_TR else "NT")) + str(kernel),
+                     (M, N, K, max(taps, 1), nz1 * nz2, splits)))
     return Cout
 
 
@@ -751,18 +685,13 @@ def dwconv_batch(items):
         it = arr[i]
         it.dy, it.x, it.dw, it.lens = dy.data_ptr(), x.data_ptr(), dst.data_ptr(), _ptr(lens)
         it.Cout, it.Cin, it.K, it.ldy, it.ldx, it.B, it.S, it.accumulate = Cout, Cin, dst.shape[1], dy.stride(1), x.stride(1), Bsz, S, int(bool(accumulate))
-    if GEMM_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(L.load().ttsk_dwconv_batch(arr, len(items), _stream()), "ttsk_dwconv_batch")
-    if GEMM_TRACE is not None:
-        e1.record()
+    def describe():
         # algorithmic FLOPs: every row of every utterance (2*B*S*Cout*Cin*k), whatever `lens` lets the kernel skip
         fl = sum(2.0 * it[0].shape[0] * it[0].shape[1] * it[0].shape[2] * it[1].shape[2] * it[2].shape[1] for it in items)
         nwg = sum((it[0].shape[2] // 256) * (it[1].shape[2] // 32) for it in items)
-        GEMM_TRACE.append((e0, e1, fl, "dwconv%d" % items[0][2].shape[1], (len(items), 0, 0, 1, 1, nwg)))
-    if LAUNCH_COUNTS is not None:
-        LAUNCH_COUNTS["dwconv"] = LAUNCH_COUNTS.get("dwconv", 0) + 1
+        return fl, "dwconv%d" % items[0][2].shape[1], (len(items), 0, 0, 1, 1, nwg)
+    _traced(lambda: check(L.load().ttsk_dwconv_batch(arr, len(items), _stream()), "ttsk_dwconv_batch"), describe)
+    _count("dwconv")
 
 
 def dwgemm_supported(Cout, Cin, k):
@@ -799,16 +728,10 @@ def dwgemm_batch(items, max_wgs=0):
                 r.ws, r.C, r.M, r.N, r.ldc, r.nz, r.splits = ws.data_ptr(), dst.data_ptr(), Cout, Cin, k * Cin, k, splits
                 r.accumulate, r.sC2, r.alpha = int(bool(accumulate)), Cin, 1.0
                 reduce.append((r, ws))
-        if GEMM_TRACE is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        check(lib.ttsk_dwgemm_batch(arr, len(chunk), int(max_wgs), _stream()), "ttsk_dwgemm_batch")
-        if GEMM_TRACE is not None:
-            e1.record()
-            fl = sum(2.0 * it[0].shape[0] * it[0].shape[1] * it[0].shape[2] * it[1].shape[2] * (it[2].shape[1] if it[2].dim() == 3 else 1) for it in chunk)
-            GEMM_TRACE.append((e0, e1, fl, "dwgemm", (len(chunk), 0, 0, 1, 1, 0)))
-        if LAUNCH_COUNTS is not None:
-            LAUNCH_COUNTS["dwgemm"] = LAUNCH_COUNTS.get("dwgemm", 0) + 1
+        _traced(lambda: check(lib.ttsk_dwgemm_batch(arr, len(chunk), int(max_wgs), _stream()), "ttsk_dwgemm_batch"),
+                lambda: (sum(2.0 * it[0].shape[0] * it[0].shape[1] * it[0].shape[2] * it[1].shape[2] * (it[2].shape[1] if it[2].dim() == 3 else 1)
+                             for it in chunk), "dwgemm", (len(chunk), 0, 0, 1, 1, 0)))
+        _count("dwgemm")
     return reduce
 
 
