@@ -796,6 +796,24 @@ int ttsk_optim_step_packed(float* params, float* grads, float* exp_avg, float* e
                            const float* anneal_steps_host, int n_anneal, float anneal_rate, int advance_rng,
                            const ttsk_adam_item* dev_items, int n_items, int n_tiles, const int64_t* dev_gaps, int n_gaps,
                            int64_t gap_floats, void* stream);
+/* The optimizer step over a SUBSET of the flat buffers (speaker adaptation: some parameter groups trained, the rest frozen; torch:
+ * requires_grad_(False) on the rest — clip_grad_norm_ and Adam then skip them).  Two launches, like ttsk_optim_step_packed.
+ * dev_ranges [n_ranges][3] (device, int64, ascending, disjoint): {start, end, sum of (end - start) / 4 over the ranges before this one},
+ * every start / end a multiple of 4; range_floats = their total.  Launch 1 sums g^2 over the ranges only (one fixed slot of `partials`
+ * per workgroup, a fixed order: equal inputs give equal bits) and advances sched_step / adam_t / lr / the bias corrections (and the
+ * dropout counter when advance_rng).  Launch 2 derives the clip coefficient from those partials in every workgroup, applies Adam, writes
+ * the bf16 shadow and (zero_grad) zeroes the gradients — over the elements of the ranges only: elements outside them are neither read
+ * nor written in any of the five buffers, and the bytes moved are proportional to range_floats.  state.gnorm is the norm over the ranges.
+ * dev_items / dev_gaps as for ttsk_optim_step_packed, restricted to the ranges: the packed weights among the trainable ones (their
+ * packs are rewritten by launch 2; packs of other weights are not touched) and the rest of the ranges as gaps,
+ * n_tiles * 8192 + gap_floats == range_floats.  n_items == 0 (then dev_items, dev_gaps NULL and n_tiles, n_gaps, gap_floats 0): no
+ * packed weight is trainable, launch 2 walks dev_ranges.  No atomics, no host synchronisation, capturable.  n_ranges == 0 is an error. */
+int ttsk_optim_step_ranges(float* params, float* grads, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t n, void* state,
+                           float* partials, float max_norm, float beta1, float beta2, float eps, int zero_grad, float d_model, float warmup,
+                           const float* anneal_steps_host, int n_anneal, float anneal_rate, int advance_rng,
+                           const int64_t* dev_ranges, int n_ranges, int64_t range_floats,
+                           const ttsk_adam_item* dev_items, int n_items, int n_tiles, const int64_t* dev_gaps, int n_gaps,
+                           int64_t gap_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------- CWT pitch branch
  * model_config.use_cwt: True.  reference: fs_two/model/modules.py:18-141 (get_pitch_embedding_cwt), :358-385 (CNNflat / CNNscalar),

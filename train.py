@@ -111,6 +111,8 @@ def main(cfg, max_steps=None):
     model, optimizer = get_model(cfg, device, train=True)
     Loss = FastSpeech2Loss(cfg.preprocess_config, cfg.model_config)
     reducer = None
+    if world > 1 and model.trainable_units is not None:
+        raise NotImplementedError("mi355x.train_only together with data-parallel training is not supported")
     if world > 1:
         # Every rank builds the same weights from the same seed, but "N independent reference micro-batches" draw N different
         # dropout masks: the Philox key of rank r is (rank 0's key) + r.  A checkpoint stores rank 0's key, so the same rule
@@ -130,6 +132,9 @@ def main(cfg, max_steps=None):
         bucket = (l_bucket, int(mi.get("t_bucket", 32)), int(cfg.model_config["max_seq_len"]))
     if rank == 0:
         print("Number of FastSpeech2 Parameters:", get_param_num(model))
+        if model.trainable_units is not None:
+            print("Training only: %s (%d trainable parameters, the rest frozen)" % (
+                ", ".join(model.trainable_units), sum(p.numel() for p in model.parameters() if p.requires_grad)))
         for p in cfg.train_config["path"].values():
             os.makedirs(p, exist_ok=True)
     step = cfg.tts.restore_step + 1

@@ -282,6 +282,51 @@ __global__ __launch_bounds__(256) void adam_pack_kernel(float* __restrict__ p, f
   }
 }
 
+// ---- the optimizer step over a SUBSET of the flat buffer (speaker adaptation: FastSpeech2.set_trainable).  `ranges` is a device table
+// [n_ranges][3] = {start, end, f32x4 groups in the ranges before this one} (the layout of AdamTables::gaps), starts / ends multiples of
+// four floats: the trainable elements as one compact index space.  This launch sums g^2 over them only — every workgroup writes its
+// partial to its own slot, a thread walks its groups in ascending order: the same bits on every run — and its block 0 advances the
+// counters exactly as sumsq_advance_kernel does.  The Adam launch behind it is adam_pack_kernel with tables that cover the same
+// elements and nothing else: bytes moved are proportional to the trainable set, frozen elements are neither read nor written.
+__global__ __launch_bounds__(256) void sumsq_ranges_advance_kernel(const float* __restrict__ g, int64_t n, const long long* __restrict__ ranges,
+                                                                   int n_ranges, long long total4, float* __restrict__ partials, OptState* st,
+                                                                   const SchedArgs sc) {
+  __shared__ float red[4];
+  float s = 0.f;
+  int cur = 0;
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+    // the compact index only grows: most steps stay in the range of the step before
+    if (!(ranges[cur * 3 + 2] <= i && (cur + 1 == n_ranges || i < ranges[(cur + 1) * 3 + 2]))) {
+      int lo = cur, hi = n_ranges;
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (ranges[mid * 3 + 2] <= i) lo = mid; else hi = mid;
+      }
+      cur = lo;
+    }
+    const int64_t e = ranges[cur * 3] + (i - ranges[cur * 3 + 2]) * 4;
+    if (e < 0 || e + 4 > n) continue;          // a table that does not fit the buffer reads nothing outside it
+    const f32x4 v = *(const f32x4*)(g + e);
+    s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const long long sstep = ++st->sched_step;
+    const long long t = ++st->adam_t;
+    double lr = fmin(pow((double)sstep, -0.5), pow((double)sc.warmup, -1.5) * (double)sstep);
+    const float an[4] = {sc.a0, sc.a1, sc.a2, sc.a3};
+    for (int i = 0; i < sc.n_anneal; ++i)
+      if ((double)sstep > (double)an[i]) lr *= (double)sc.anneal_rate;
+    st->lr = (float)(pow((double)sc.d_model, -0.5) * lr);
+    st->bc1 = (float)(1.0 - pow((double)sc.b1, (double)t));
+    st->bc2 = (float)(1.0 - pow((double)sc.b2, (double)t));
+    if (sc.advance_rng) st->rng_step += 1;
+  }
+}
+
 }  // namespace
 
 extern "C" int ttsk_optim_state_bytes(void) { return (int)sizeof(OptState); }
@@ -367,6 +412,52 @@ extern "C" int ttsk_optim_step_packed(float* params, float* grads, float* exp_av
   hipLaunchKernelGGL(sumsq_advance_kernel, dim3(1024), dim3(256), 0, s, grads, n, partials, (OptState*)state, sc);
   hipLaunchKernelGGL(adam_pack_kernel, dim3(2048), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, (bf16_t*)shadow_bf16, (OptState*)state,
                      partials, 1024, max_norm, beta1, beta2, eps, zero_grad, tb);
+  TTSK_CHECK_LAUNCH();
+  return TTSK_OK;
+}
+
+extern "C" int ttsk_optim_step_ranges(float* params, float* grads, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t n, void* state,
+                                      float* partials /* >= 1024 floats */, float max_norm, float beta1, float beta2, float eps, int zero_grad,
+                                      float d_model, float warmup, const float* anneal_steps_host, int n_anneal, float anneal_rate,
+                                      int advance_rng, const int64_t* dev_ranges, int n_ranges, int64_t range_floats,
+                                      const ttsk_adam_item* dev_items, int n_items, int n_tiles, const int64_t* dev_gaps, int n_gaps,
+                                      int64_t gap_floats, void* stream) {
+  TTSK_REQUIRE(params && grads && exp_avg && exp_avg_sq && shadow_bf16 && state && partials && n > 0, "optim_step_ranges: null pointer");
+  TTSK_REQUIRE((n & 3) == 0, "optim_step_ranges: n must be a multiple of 4 (pad the flat buffer)");
+  TTSK_REQUIRE((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)shadow_bf16) & 15) == 0,
+               "optim_step_ranges: alignment");
+  TTSK_REQUIRE(n_anneal >= 0 && n_anneal <= 4, "optim_step_ranges: at most 4 anneal steps");
+  TTSK_REQUIRE(dev_ranges && n_ranges > 0, "optim_step_ranges: no trainable range (n_ranges = %d)", n_ranges);
+  TTSK_REQUIRE(range_floats > 0 && (range_floats & 3) == 0 && range_floats <= n,
+               "optim_step_ranges: the ranges hold %lld floats (a positive multiple of 4, at most n = %lld)", (long long)range_floats, (long long)n);
+  if (n_items == 0) {
+    // no packed weight among the trainable ones: the Adam launch walks the ranges themselves
+    TTSK_REQUIRE(!dev_items && n_tiles == 0 && !dev_gaps && n_gaps == 0 && gap_floats == 0, "optim_step_ranges: tile / gap tables without items");
+    dev_gaps = dev_ranges;
+    n_gaps = n_ranges;
+    gap_floats = range_floats;
+  } else {
+    TTSK_REQUIRE(dev_items && n_items > 0 && n_tiles > 0 && n_gaps >= 0 && (n_gaps == 0 || dev_gaps) && gap_floats >= 0 && (gap_floats & 3) == 0,
+                 "optim_step_ranges: bad tables");
+    TTSK_REQUIRE((int64_t)n_tiles * 8192 + gap_floats == range_floats, "optim_step_ranges: tiles (%d x 8192) + gaps (%lld) do not cover the ranges (%lld)",
+                 n_tiles, (long long)gap_floats, (long long)range_floats);
+  }
+  float a[4] = {0, 0, 0, 0};
+  for (int i = 0; i < n_anneal; ++i) a[i] = anneal_steps_host[i];
+  const SchedArgs sc{d_model, warmup, a[0], a[1], a[2], a[3], anneal_rate, beta1, beta2, n_anneal, advance_rng};
+  const AdamTables tb{dev_items, n_items, n_tiles, (const long long*)dev_gaps, n_gaps, (long long)(gap_floats / 4)};
+  const int64_t total4 = range_floats / 4;
+  // the grid of sumsq_advance_kernel, whatever the ranges hold: one range over the whole buffer then gives ttsk_optim_step's partials,
+  // bit for bit (a workgroup without elements writes a zero; the Adam launch folds all 1024 slots)
+  const int nblk = 1024;
+  int64_t wgs = (gap_floats / 4 + 255) / 256;
+  if (wgs < n_tiles) wgs = n_tiles;
+  const int grid = (int)(wgs < 1 ? 1 : (wgs > 2048 ? 2048 : wgs));
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(sumsq_ranges_advance_kernel, dim3(nblk), dim3(256), 0, s, grads, n, (const long long*)dev_ranges, n_ranges,
+                     (long long)total4, partials, (OptState*)state, sc);
+  hipLaunchKernelGGL(adam_pack_kernel, dim3(grid), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, (bf16_t*)shadow_bf16, (OptState*)state,
+                     partials, nblk, max_norm, beta1, beta2, eps, zero_grad, tb);
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
 }

@@ -86,6 +86,9 @@ class TrainEngine:
     def __init__(self, model, optimizer, cfg, Loss, reducer=None, hip_graph=None):
         mi = cfg.get("mi355x", {}) if hasattr(cfg, "get") else {}
         self.model, self.optimizer, self.cfg, self.Loss, self.reducer = model, optimizer, cfg, Loss, reducer
+        if reducer is not None and getattr(model, "trainable_units", None) is not None:
+            raise NotImplementedError("train_only (FastSpeech2.set_trainable) together with a gradient reducer is not supported: its "
+                                      "buckets and group announcements assume every group completes")
         self.use_graph = bool(mi.get("hip_graph", True)) if hip_graph is None else bool(hip_graph)
         self.max_graphs = int(mi.get("max_graphs", 64))
         self.grad_acc = int(cfg.train_config["optimizer"]["grad_acc_step"])

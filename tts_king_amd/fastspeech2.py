@@ -152,6 +152,13 @@ class FastSpeech2(nn.Module):
         self.window_ffn = switches.get("TTSK_WINDOW_FFN") != "0"
         self._w1_packed = None
         self._adam_tables = None
+        # Speaker adaptation (set_trainable): the units that are trained, None = all of them; the optimizer's tables over their
+        # ranges of the flat buffer (ops.optim_range_tables) and the pack table of the trainable 80-channel ends
+        self._trainable = None
+        self._optimizer_built = False
+        self._range_tables = None
+        self._range_repack = False
+        self._odd_pack_table_sub = None
         self.flash_attention = True     # attention without the S x S tensors when d_k = 128 (csrc/flash_attn.hip); False / other head sizes: scores GEMM + softmax + P V GEMM
         self.fused_ln = True            # fc / w_2 + dropout + residual + LayerNorm + PAD zeroing in one kernel when d = 256
         self._postnet_ends_win = True       # the PostNet's 80 -> 512 / 512 -> 80 convs and their input gradients on the window kernel too (round 5; property below)
@@ -253,6 +260,82 @@ class FastSpeech2(nn.Module):
                 par.grad = self._view(self._flat_grad, en)
                 mod._parameters[leaf] = par
         self._shadow_version = -1
+        self._apply_trainable_flags()
+
+    # ------------------------------------------------------------------ trainable units (speaker adaptation)
+    def set_trainable(self, units=None):
+        """Train only the parameter groups `units` and freeze the rest (torch: `requires_grad_(False)` on the rest).  Units:
+        `params.unit_names` — postnet, mel_linear, decoder.0 .., variance_adaptor, speaker_emb, encoder.0 .., embedding; the prefixes
+        "decoder" / "encoder" name every block of the stack.  None, or every unit: today's path, unchanged.  A frozen unit gets no
+        parameter-gradient work in backward_native, input gradients stop at the lowest trainable unit, and the optimizer's clip / Adam
+        cover the trainable ranges only.  "Frozen" covers parameters: in train mode BatchNorm still takes batch statistics and moves
+        its running ones, and dropout still runs.  Must be called before a ScheduledOptim is built on the model."""
+        if self._optimizer_built:
+            raise RuntimeError("set_trainable must be called before a ScheduledOptim is built on the model (its Adam state, tables and "
+                               "checkpoint layout follow the trainable units)")
+        tu = P.parse_units(units, self.n_enc, self.n_dec)
+        if tu is not None and self.use_cwt:
+            raise NotImplementedError("train_only together with use_cwt: True is not supported")
+        self._trainable = tu
+        self._apply_trainable_flags()
+        self._build_range_tables()
+
+    @property
+    def trainable_units(self):
+        """The trainable units in backward order, or None when everything is trained."""
+        if self._trainable is None:
+            return None
+        return tuple(u for u in P.unit_names(self.n_enc, self.n_dec) if u in self._trainable)
+
+    def trainable_ranges(self):
+        """Sorted [start, end) ranges of the flat buffers the optimizer updates: cut at entry boundaries (each entry's padding to 8
+        floats included), adjacent ones merged.  Everything trainable: [(0, n_flat)]."""
+        return P.unit_ranges(self._table, self._n_flat, self._trainable)
+
+    def trainable_keys(self):
+        """state_dict keys of the parameters that are trained."""
+        return [k for k, en in self._table.items() if en.kind == P.TRAIN and self._unit_on(P.unit_of(k))]
+
+    def _unit_on(self, unit):
+        return self._trainable is None or unit in self._trainable
+
+    def _apply_trainable_flags(self):
+        """requires_grad / .grad of the parameters as the trainable units say (a frozen parameter has no .grad: its stretch of the
+        flat gradient buffer is never written to a defined value)."""
+        for en in self._table.values():
+            if en.kind == P.TRAIN:
+                par = self.get(en.key)
+                on = self._unit_on(P.unit_of(en.key))
+                par.requires_grad_(on)
+                par.grad = self._view(self._flat_grad, en) if on else None
+
+    def _build_range_tables(self):
+        """The device tables of the subset optimizer step (host -> device copies: at construction, set_trainable and `_apply`, never
+        inside a step).  The trainable packed weights keep the Adam launch's tile walk (their packs are written there, the frozen
+        weights' packs are left alone); the trainable 80-channel ends get a pack table of their own."""
+        self._range_tables, self._range_repack, self._odd_pack_table_sub = None, False, None
+        if self._trainable is None or not self._flat.is_cuda:
+            return
+        dev, items = self._flat.device, []
+        packed = self.window_ffn and bool(self._w1_packed)
+        if packed and self._adam_tables is not None:
+            items = [tuple(v) for k, v in self._adam_items.items() if self._unit_on(P.unit_of(k))]
+        tables = ops.optim_range_tables(self.trainable_ranges(), items, dev)
+        if tables is None or (packed and self._adam_tables is None):
+            # a packed weight that does not tile: Adam over the plain ranges, every pack rewritten from the shadow behind it
+            tables, self._range_repack = ops.optim_range_tables(self.trainable_ranges(), [], dev), True
+        self._range_tables = tables
+        if packed and not self._range_repack:
+            odd = [(W, pk, tr) for key, W, pk, tr in getattr(self, "_odd_items", []) if self._unit_on(P.unit_of(key))]
+            if odd:
+                self._odd_pack_table_sub = ops.win_conv_pack_table(odd, dev)
+
+    def refresh_trainable_packs(self):
+        """Behind the subset optimizer step: the packs that step did not write itself — of trainable weights only."""
+        if self._range_repack:
+            self.refresh_packed()
+        elif self._odd_pack_table_sub is not None:
+            ops.win_conv_pack_run(*self._odd_pack_table_sub)
 
     def mark_dirty(self):
         """Call after writing the fp32 masters through anything torch cannot see (raw pointers): the next forward
@@ -279,6 +362,8 @@ class FastSpeech2(nn.Module):
         self._rebind()
         if self.window_ffn and self._shadow.is_cuda:
             self._build_packs()
+        else:
+            self._build_range_tables()
         return self
 
     def get(self, key):
@@ -439,7 +524,7 @@ class FastSpeech2(nn.Module):
         self._pack_table = ops.win_conv_pack_table([(self._pack_source(key, fr), out, tr) for key, fr, out, tr in self._pack_items],
                                                    self._shadow.device) if self._pack_items else None
         self._odd_pack_table = None
-        odd_items = []
+        odd_items, self._odd_items = [], []
         for tag, key, _, tr in odd:
             if key not in self._table:
                 continue
@@ -451,6 +536,7 @@ class FastSpeech2(nn.Module):
             pk = torch.empty(ops.win_pack_numel(cs, kk, ds, tr), dtype=bf16, device=self._shadow.device)
             self._w1_packed[(tag, key)] = pk
             odd_items.append((W, pk, tr))
+            self._odd_items.append((key, W, pk, tr))
         if odd_items:
             self._odd_pack_table = ops.win_conv_pack_table(odd_items, self._shadow.device)
         # ... and the tables with which the optimizer's Adam launch writes these packs itself (ttsk_optim_step_packed): per weight its
@@ -467,6 +553,8 @@ class FastSpeech2(nn.Module):
                 ent[3 if tr else 2] = out
             if ok:
                 self._adam_tables = ops.adam_pack_tables([tuple(v) for v in by_key.values()], self._n_flat, self._shadow.device)
+                self._adam_items = by_key
+        self._build_range_tables()
 
     def _pack(self, tag, key):
         """The window kernel's pack `(tag, key)` of `_build_packs`, or None: no such pack, or no packs at all (TTSK_WINDOW_FFN=0)."""
@@ -667,9 +755,11 @@ class FastSpeech2(nn.Module):
         Lp, row_limit = saved[9], saved[12]
         return ops.va_combine(dx3, dxin, Lp, row_limit)
 
-    def _predictors_bwd_inputs(self, saved, dstack, rng):
+    def _predictors_bwd_inputs(self, saved, dstack, rng, train=True, need_dur_dx=True):
         """Everything of the predictors' backward that needs only the loss's gradients: (3, rows, d) fp32 input gradients, and the
-        parameter-gradient work queued."""
+        parameter-gradient work queued.  `train` False (the variance adaptor is frozen): no parameter-gradient work, the LayerNorm
+        partials the kernels emit are dropped.  `need_dur_dx` False (nothing of the encoder is trained): the duration predictor's
+        input gradient, which feeds nothing but the encoder, is not computed — slot 0 of the result is not written."""
         (stack, h1, m1, r1, a1, h2, m2, r2, Bn, Lp, lens, p, row_limit) = saved
         d, rows, ps = self.d, Bn * Lp, self._pred_stride
         names = ("duration", "pitch", "energy")
@@ -683,7 +773,7 @@ class FastSpeech2(nn.Module):
                                                     site_post=201, rng=rng, dhead=dstack.view(-1),
                                                     head_w=self._m(pre + "linear_layer.weight").view(-1))
         dh2 = dh2.view(3, rows, Fh)
-        for g, n in enumerate(names):
+        for g, n in enumerate(names if train else ()):
             cg = "variance_adaptor.%s_predictor.conv_layer." % n
             self._finalize_ln(part[g], nblk, 4 * Fh + 1, cg + "conv1d_2.conv.bias")
             ops.queue_dw(self._deferred, dh2[g].view(Bn, Lp, Fh), a1[g * rows:(g + 1) * rows].view(Bn, Lp, Fh), self._g(cg + "conv1d_2.conv.weight"),
@@ -694,13 +784,17 @@ class FastSpeech2(nn.Module):
                                                     self._m(c + "layer_norm_1.bias"), 3, ps, 2, row_limit, Lp if row_limit is not None else 0,
                                                     relu_in=True, p_post=p, site_post=200, rng=rng)
         dh1 = dh1.view(3, rows, Fh)
-        for g, n in enumerate(names):
+        for g, n in enumerate(names if train else ()):
             cg = "variance_adaptor.%s_predictor.conv_layer." % n
             self._finalize_ln(part[g], nblk, 3 * Fh, cg + "conv1d_1.conv.bias")
             ops.queue_dw(self._deferred, dh1[g].view(Bn, Lp, Fh), stack[g].view(Bn, Lp, d), self._g(cg + "conv1d_1.conv.weight"), None,
                          self._acc, k=self.k_var, use_dwgemm=self._use_dwconv)
         dxin = torch.empty(3, rows, d, dtype=torch.float32, device=dev)
-        ops.conv1d_dx(dh1[0].view(Bn, Lp, Fh), W1, out=dxin[0].view(Bn, Lp, d), nz1=3, sA=(rows * Fh, 0), sB=(ps, 0), sC=(rows * d, 0))
+        if need_dur_dx:
+            ops.conv1d_dx(dh1[0].view(Bn, Lp, Fh), W1, out=dxin[0].view(Bn, Lp, d), nz1=3, sA=(rows * Fh, 0), sB=(ps, 0), sC=(rows * d, 0))
+        else:       # the pitch and energy predictors only
+            ops.conv1d_dx(dh1[1].view(Bn, Lp, Fh), self._w("variance_adaptor.pitch_predictor.conv_layer.conv1d_1.conv.weight"),
+                          out=dxin[1].view(Bn, Lp, d), nz1=2, sA=(rows * Fh, 0), sB=(ps, 0), sC=(rows * d, 0))
         return dxin
 
     def _forward(self, train, speakers, texts, src_lens, Lp, mel_lens, max_mel_len, e_targets, d_targets, pitches_raw,
@@ -1075,11 +1169,13 @@ class FastSpeech2(nn.Module):
             return "pre"
         return True
 
-    def _fft_bwd(self, saved, dx2, rng, raw_out=False):
+    def _fft_bwd(self, saved, dx2, rng, raw_out=False, train=True, need_dx=True):
         """Backward of one FFTBlock.  `dx2`: gradient of the block output — a bf16 tensor, or (Slabs, residual) when the dX GEMM
         that produced it left its split-K partial tiles un-reduced (the next block's `raw_out`): the LayerNorm backward sums them
         while it reads its rows, so no reducer launch and no bf16 copy of that gradient exist.  Returns the gradient of the block
-        input in the same two forms."""
+        input in the same two forms.  `train` False (the block is frozen): none of its parameter-gradient work is issued (the
+        LayerNorm / bias partials the fused kernels emit are dropped).  `need_dx` False (nothing in front of the block is trained):
+        the block's input gradient is not computed, the result is None."""
         (pre, x, qkv, probs, o, z1, mean1, rstd1, x1, h, z2, mean2, rstd2, Bn, S, lens, H, p, site, o32) = saved
         d, rows = self.d, Bn * S
         dk = d // H
@@ -1105,8 +1201,9 @@ class FastSpeech2(nn.Module):
             dz2, dy2, part, nblk = ops.layernorm_bwd(dd2, z2, mean2, rstd2, self._m(f + "layer_norm.weight"), self._m(f + "layer_norm.bias"),
                                                      lens, S, p_pre=p, site_pre=site + 1, rng=rng, slabs=sl2, R=r2)
         # ---- w_2 (k=1): dW, dX gated by the ReLU
-        self._finalize_ln(part, nblk, 3 * d, f + "w_2.bias")
-        ops.queue_dw(self._deferred, dy2.view(Bn, S, d), h, self._g(f + "w_2.weight"), lens, self._acc, k=self.k2, use_dwgemm=self._use_dwconv)
+        if train:
+            self._finalize_ln(part, nblk, 3 * d, f + "w_2.bias")
+            ops.queue_dw(self._deferred, dy2.view(Bn, S, d), h, self._g(f + "w_2.weight"), lens, self._acc, k=self.k2, use_dwgemm=self._use_dwconv)
         if dh is not None:
             pass
         elif pk2 is not None and self.k2 == 1:
@@ -1114,13 +1211,14 @@ class FastSpeech2(nn.Module):
         else:
             dh = ops.conv1d_dx(dy2.view(Bn, S, d), self._w(f + "w_2.weight"), G=h)
         # ---- w_1 (k=9): bias, dW, dX + residual gradient; the dX stays in split-K form for the attention LayerNorm's backward
-        ops.colsum_into(dh.view(rows, -1), self._g(f + "w_1.bias"), defer=self._deferred_fin, accumulate=self._acc)
-        if self._use_dwconv and Bn <= 64 and dh.dtype == bf16 and ops.dwconv_supported(dh.shape[-1], d, self.k1):
-            # the taps share one fetch of dh and one window of x1 (csrc/dwconv.hip); dh is zero at PAD rows (the LayerNorm backward
-            # that produced dy2 gives them no gradient), so only the rows of each utterance's own length are walked
-            self._deferred.dwconv.append((dh, x1.view(Bn, S, d), self._g(f + "w_1.weight"), lens, self._acc))
-        else:
-            ops.conv1d_dw(dh, x1.view(Bn, S, d), self._g(f + "w_1.weight"), k=self.k1, defer=self._deferred, accumulate=self._acc)
+        if train:
+            ops.colsum_into(dh.view(rows, -1), self._g(f + "w_1.bias"), defer=self._deferred_fin, accumulate=self._acc)
+            if self._use_dwconv and Bn <= 64 and dh.dtype == bf16 and ops.dwconv_supported(dh.shape[-1], d, self.k1):
+                # the taps share one fetch of dh and one window of x1 (csrc/dwconv.hip); dh is zero at PAD rows (the LayerNorm backward
+                # that produced dy2 gives them no gradient), so only the rows of each utterance's own length are walked
+                self._deferred.dwconv.append((dh, x1.view(Bn, S, d), self._g(f + "w_1.weight"), lens, self._acc))
+            else:
+                ops.conv1d_dw(dh, x1.view(Bn, S, d), self._g(f + "w_1.weight"), k=self.k1, defer=self._deferred, accumulate=self._acc)
         # ---- attention tail
         do = delta = None
         pk1 = self._pack("w1T", f + "w_1.weight")
@@ -1139,8 +1237,9 @@ class FastSpeech2(nn.Module):
         else:
             dz1, dy1, part, nblk = ops.layernorm_bwd(None, z1, mean1, rstd1, self._m(a + "layer_norm.weight"), self._m(a + "layer_norm.bias"),
                                                      lens, S, p_pre=p, site_pre=site, rng=rng, slabs=sl, R=dz2)
-        self._finalize_ln(part, nblk, 3 * d, a + "fc.bias")
-        ops.queue_dw(self._deferred, dy1.view(Bn, S, d), o.view(Bn, S, d), self._g(a + "fc.weight"), lens, self._acc, use_dwgemm=self._use_dwconv)
+        if train:
+            self._finalize_ln(part, nblk, 3 * d, a + "fc.bias")
+            ops.queue_dw(self._deferred, dy1.view(Bn, S, d), o.view(Bn, S, d), self._g(a + "fc.weight"), lens, self._acc, use_dwgemm=self._use_dwconv)
         if do is not None:
             pass
         elif pkf is not None:
@@ -1168,9 +1267,12 @@ class FastSpeech2(nn.Module):
                      sA=(H * S * Sp, S * Sp), sB=(S * d, dk), sC=(S * 3 * d, dk), group=kv)
             kv.flush()
         # ---- q|k|v projections
-        ops.colsum_into(dqkv, self._g(a + "w_qs.bias", 3 * d), defer=self._deferred_fin, accumulate=self._acc)
-        ops.queue_dw(self._deferred, dqkv.view(Bn, S, 3 * d), x.view(Bn, S, d), self._g(a + "w_qs.weight", 3 * d * d).view(3 * d, d), lens,
-                     self._acc, use_dwgemm=self._use_dwconv)
+        if train:
+            ops.colsum_into(dqkv, self._g(a + "w_qs.bias", 3 * d), defer=self._deferred_fin, accumulate=self._acc)
+            ops.queue_dw(self._deferred, dqkv.view(Bn, S, 3 * d), x.view(Bn, S, d), self._g(a + "w_qs.weight", 3 * d * d).view(3 * d, d), lens,
+                         self._acc, use_dwgemm=self._use_dwconv)
+        if not need_dx:
+            return None
         pkq = self._pack("qkvT", a + "w_qs.weight")
         if raw_out:
             if pkq is not None and raw_out == "pre" and d == 256:
@@ -1182,7 +1284,8 @@ class FastSpeech2(nn.Module):
             return ops.qkv_dx(dqkv, pkq, R=dz1)       # the first block of the stack: the same 32-row product as a kernel of its own
         return ops.linear_dx(dqkv, self._w(a + "w_qs.weight", 3 * d), R=dz1)
 
-    def _predictor_bwd(self, pre, saved, dout, rng, R):
+    def _predictor_bwd(self, pre, saved, dout, rng, R, train=True, need_dx=True):
+        """`train` / `need_dx`: as for _fft_bwd."""
         (x, h1, m1, r1, a1, h2, m2, r2, Bn, Lp, lens, p, site) = saved
         d, rows = self.d, Bn * Lp
         c = pre + "conv_layer."
@@ -1197,14 +1300,18 @@ class FastSpeech2(nn.Module):
             dh2, _, part, nblk = ops.layernorm_bwd(None, h2.view(rows, Fh), m2, r2, self._m(c + "layer_norm_2.weight"),
                                                    self._m(c + "layer_norm_2.bias"), lens, Lp, relu_in=True, p_post=p,
                                                    site_post=site + 1, rng=rng, dhead=dout.contiguous().view(-1), head_w=hw.view(-1))
-        self._finalize_ln(part, nblk, (3 + n_out) * Fh + n_out, c + "conv1d_2.conv.bias")
-        ops.conv1d_dw(dh2.view(Bn, Lp, Fh), a1.view(Bn, Lp, Fh), self._g(c + "conv1d_2.conv.weight"), k=self.k_var, defer=self._deferred, accumulate=self._acc)
+        if train:
+            self._finalize_ln(part, nblk, (3 + n_out) * Fh + n_out, c + "conv1d_2.conv.bias")
+            ops.conv1d_dw(dh2.view(Bn, Lp, Fh), a1.view(Bn, Lp, Fh), self._g(c + "conv1d_2.conv.weight"), k=self.k_var, defer=self._deferred, accumulate=self._acc)
         da1 = ops.conv1d_dx(dh2.view(Bn, Lp, Fh), self._w(c + "conv1d_2.conv.weight"))
         dh1, _, part, nblk = ops.layernorm_bwd(da1.view(rows, Fh), h1.view(rows, Fh), m1, r1, self._m(c + "layer_norm_1.weight"),
                                                self._m(c + "layer_norm_1.bias"), None, 0, relu_in=True, p_post=p,
                                                site_post=site, rng=rng)
-        self._finalize_ln(part, nblk, 3 * Fh, c + "conv1d_1.conv.bias")
-        ops.conv1d_dw(dh1.view(Bn, Lp, Fh), x.view(Bn, Lp, d), self._g(c + "conv1d_1.conv.weight"), k=self.k_var, defer=self._deferred, accumulate=self._acc)
+        if train:
+            self._finalize_ln(part, nblk, 3 * Fh, c + "conv1d_1.conv.bias")
+            ops.conv1d_dw(dh1.view(Bn, Lp, Fh), x.view(Bn, Lp, d), self._g(c + "conv1d_1.conv.weight"), k=self.k_var, defer=self._deferred, accumulate=self._acc)
+        if not need_dx:
+            return None
         return ops.conv1d_dx(dh1.view(Bn, Lp, Fh), self._w(c + "conv1d_1.conv.weight"), R=R)
 
     def _finalize_loss(self):
@@ -1273,6 +1380,11 @@ class FastSpeech2(nn.Module):
 
     def _flush_param_grads(self):
         """Run the queued weight-gradient work (grouped dW GEMMs, split-K reducers, column sums, scatter-sums)."""
+        if self._dw_side_pending and self._trainable is not None:
+            # a subset step (set_trainable): what is still queued may be a few problems or none, so the three-way fork below could open
+            # branches with nothing in them — the second stream is joined and the rest runs on this one
+            torch.cuda.current_stream().wait_stream(self._dw_side)
+            self._dw_side_pending = False
         if self._dw_side_pending:
             # The main stream gets here ~0.1 ms before the capped dW group on the side stream ends.  The column sums / scatter-sums read
             # only activations and gradients the main chain produced: they run now, beside the side stream; the encoder-side dW group
@@ -1348,35 +1460,61 @@ class FastSpeech2(nn.Module):
         self._use_dwconv = self.dwconv and (on_bucket is None or dp_side)
         notifier = _GroupNotifier(self.backward_group_order(), on_bucket, self._flush_param_grads, mark=self._mark_bucket if dp_side else None)
         notify = notifier.done
+        # ---- trainable units (set_trainable): which parameter gradients are wanted, and how far down the input gradients must go.
+        # With everything trainable every flag below is True and every stop index 0: the launches are today's.
+        on = self._unit_on
+        subset = self._trainable is not None
+        if subset:
+            if on_bucket is not None:
+                raise NotImplementedError("train_only together with a gradient reducer is not supported (its buckets and group "
+                                          "announcements assume every group completes)")
+            notify = lambda name: None          # noqa: E731  (no reducer listens; groups that are skipped are never announced)
+        dec_on = [on("decoder.%d" % i) for i in range(self.n_dec)]
+        enc_on = [on("encoder.%d" % i) for i in range(self.n_enc)]
+        pn_on, mel_on, va_on, spk_on, emb_on = on("postnet"), on("mel_linear"), on("variance_adaptor"), on("speaker_emb"), on("embedding")
+        need_enc = emb_on or any(enc_on)                           # does anything of the encoder want a gradient?
+        enc_stop = 0 if emb_on else (enc_on.index(True) if need_enc else self.n_enc)
+        need_below = need_enc or va_on or spk_on                   # ... anything below the decoder?
+        dec_stop = 0 if need_below else (dec_on.index(True) if any(dec_on) else self.n_dec)
+        need_dec = need_below or any(dec_on)                       # does the decoder's backward run at all?
+        need_mel = need_dec or mel_on                              # ... mel_linear's?
+        # (arguments beyond today's only where a unit is frozen or a gradient stops: a full step calls the block functions as it always did)
+        pkw = {} if (va_on and need_enc) else {"train": va_on, "need_dur_dx": need_enc}
+
+        def bkw(train, need_dx):
+            return {} if (train and need_dx) else {"train": train, "need_dx": need_dx}
         ops.stamp("bwd.start")
         # ---- the predictors' backward up to their input gradients, on a stream of its own beside the PostNet's (see pred_side); not in
-        # the schedules that flush the deferred queue before the decoder is done
+        # the schedules that flush the deferred queue before the decoder is done; not at all when nothing below the decoder is trained
         pred_dxin = None
-        if self.pred_side in ("1", "b") and "grouped" in ctx.preds and (on_bucket is None or dp_side):
+        if self.pred_side in ("1", "b") and "grouped" in ctx.preds and (on_bucket is None or dp_side) and need_below:
             if self._pred_stream is None:
                 self._pred_stream = torch.cuda.Stream(device=self.device)
             if not self._var_on_pred:             # (the two-stream loss left dlogd / dpitch / denergy ON that stream: nothing of this one is needed)
                 self._pred_stream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self._pred_stream):
-                pred_dxin = self._predictors_bwd_inputs(ctx.preds["grouped"], self._stack3(dlogd, dpitch, denergy), rng)
+                pred_dxin = self._predictors_bwd_inputs(ctx.preds["grouped"], self._stack3(dlogd, dpitch, denergy), rng, **pkw)
         elif self._var_on_pred:                   # the predictors' backward runs on this stream: it needs the two-stream loss's other half
             torch.cuda.current_stream().wait_stream(self._pred_stream)
             self._finalize_loss()
         self._var_on_pred = False
         # ---- PostNet (last layer first)
         dout = dpost.view(rows, nm)
+        dmel_tot = None
         bn_partials = None          # BatchNorm-backward statistics of layer i, when conv i+1's input-gradient kernel emitted them
         for i in range(4, -1, -1):
             pp, xin, yc, mean, rstd, keep = ctx.pn[i]
             C = yc.shape[2]
             dy = ops.bn_bwd(dout, yc.view(rows, C), mean, rstd, self._m(pp + "1.weight"), self._m(pp + "1.bias"), i < 4,
-                            p=self.p_post, site=300 + i, rng=rng, dgamma=self._g(pp + "1.weight"), dbeta=self._g(pp + "1.bias"),
+                            p=self.p_post, site=300 + i, rng=rng, dgamma=self._g(pp + "1.weight") if pn_on else None,
+                            dbeta=self._g(pp + "1.bias") if pn_on else None,
                             frame_limit=ctx.frame_limit, keep=keep, accumulate=self._acc, partials=bn_partials)
             bn_partials = None
-            ops.colsum_into(dy, self._g(pp + "0.conv.bias"), defer=self._deferred_fin, accumulate=self._acc)
-            # (no `lens`: the PostNet's BatchNorm runs over the PAD rows too, Layers.py:133-143 — its gradients there are not zero)
-            ops.queue_dw(self._deferred, dy.view(Bn, T, C), xin, self._g(pp + "0.conv.weight"), None, self._acc, k=5,
-                         use_dwgemm=self._use_dwconv)
+            if pn_on:
+                ops.colsum_into(dy, self._g(pp + "0.conv.bias"), defer=self._deferred_fin, accumulate=self._acc)
+                # (no `lens`: the PostNet's BatchNorm runs over the PAD rows too, Layers.py:133-143 — its gradients there are not zero)
+                ops.queue_dw(self._deferred, dy.view(Bn, T, C), xin, self._g(pp + "0.conv.weight"), None, self._acc, k=5,
+                             use_dwgemm=self._use_dwconv)
             pkt = self._pack("pnT", pp + "0.conv.weight")
             if i > 0 and pkt is not None:
                 cw = self._table[pp + "0.conv.weight"].storage_shape
@@ -1392,7 +1530,7 @@ class FastSpeech2(nn.Module):
                     dout = ops.win_conv(dy.view(Bn, T, C), pkt, cw[2], cw[1]).view(rows, -1)   # dX as a forward conv on the transposed pack
             elif i > 0:
                 dout = ops.conv1d_dx(dy.view(Bn, T, C), self._w(pp + "0.conv.weight")).view(rows, -1)
-            else:
+            elif need_mel:
                 if pkt is not None:          # the first conv's input gradient (512 -> 80) + the mel terms' own gradient, on the window kernel
                     cw = self._table[pp + "0.conv.weight"].storage_shape
                     dmel_tot = ops.win_conv_resid(dy.view(Bn, T, C), pkt, dmel_sum.view(Bn, T, nm), cw[2], cw[1]).view(rows, nm)
@@ -1403,56 +1541,76 @@ class FastSpeech2(nn.Module):
         notify("postnet")
         ops.stamp("bwd.postnet_done")
         # ---- mel_linear
-        ops.colsum_into(dmel_tot, self._g("mel_linear.bias"), defer=self._deferred_fin, accumulate=self._acc)
-        ops.linear_dw(dmel_tot, ctx.dec_out, self._g("mel_linear.weight"), defer=self._deferred, accumulate=self._acc)
-        pkm = self._pack("linT", "mel_linear.weight")
-        if pkm is not None and dmel_tot.dtype == bf16:
-            dx = ops.win_conv(dmel_tot.view(Bn, T, nm), pkm, d, 1).view(rows, d)      # mel_linear's input gradient: a k = 1 conv on the transposed pack
-        else:
-            dx = ops.linear_dx(dmel_tot, self._w("mel_linear.weight"))
+        if mel_on:
+            ops.colsum_into(dmel_tot, self._g("mel_linear.bias"), defer=self._deferred_fin, accumulate=self._acc)
+            ops.linear_dw(dmel_tot, ctx.dec_out, self._g("mel_linear.weight"), defer=self._deferred, accumulate=self._acc)
+        dx = None
+        if need_dec:
+            pkm = self._pack("linT", "mel_linear.weight")
+            if pkm is not None and dmel_tot.dtype == bf16:
+                dx = ops.win_conv(dmel_tot.view(Bn, T, nm), pkm, d, 1).view(rows, d)      # mel_linear's input gradient: a k = 1 conv on the transposed pack
+            else:
+                dx = ops.linear_dx(dmel_tot, self._w("mel_linear.weight"))
         notify("mel_linear")
-        # ---- decoder
-        for i in range(self.n_dec - 1, -1, -1):
-            dx = self._fft_bwd(ctx.blocks[ctx.n_enc_blocks + i], dx, rng, raw_out=self._raw_out_mode() if i > 0 else False)
+        # ---- decoder: down to the lowest block whose gradient anything wants
+        for i in range(self.n_dec - 1, dec_stop - 1, -1):
+            dx = self._fft_bwd(ctx.blocks[ctx.n_enc_blocks + i], dx, rng, raw_out=self._raw_out_mode() if i > 0 else False,
+                               **bkw(dec_on[i], need_below or i > dec_stop))
             notify("decoder.%d" % i)
         ops.stamp("bwd.decoder_done")
         if pred_dxin is not None:
             torch.cuda.current_stream().wait_stream(self._pred_stream)    # long done; its queued dW work joins the second stream's
+        q = self._deferred
         if dp_side and self.dp_schedule == "side":
             self._launch_dw_side_buckets(on_bucket)
-        elif self.dw_side_wgs > 0:
+        elif self.dw_side_wgs > 0 and (not subset or (need_below and (q.group or q.dwconv or q.dwgemm))):
+            # (a subset step opens the second stream only when it has work for it and a chain to run beside: no empty branch)
             self._launch_dw_side()
-        # ---- length regulator: segment sums (the position table has no parameters)
-        dx3 = ops.length_regulator_bwd(dx.view(Bn, T, d), ctx.cs, Lp).view(Bn * Lp, d)
-        # ---- variance adaptor, reverse order of modules.py:158-193
-        va = "variance_adaptor."
-        ops.scatter_sum(dx3, ctx.eidx.view(-1), self._g(va + "energy_embedding.weight"), defer=self._deferred_fin, accumulate=self._acc)
-        if "grouped" in ctx.preds:
-            dx2, dx1, dxe = self._predictors_bwd_grouped(ctx.preds["grouped"], None if pred_dxin is not None else
-                                                         self._stack3(dlogd, dpitch, denergy), rng, dx3, dxin=pred_dxin)
-            ops.scatter_sum(dx2, ctx.pidx.view(-1), self._g(va + "pitch_embedding.weight"), defer=self._deferred_fin, accumulate=self._acc)
-            ops.scatter_sum(dx1, ctx.speakers, self._g("speaker_emb.weight"), idx_div=Lp, defer=self._deferred_fin, accumulate=self._acc)
-        else:
-            dx2 = self._predictor_bwd(va + "energy_predictor.", ctx.preds[va + "energy_predictor."], denergy, rng, dx3.view(Bn, Lp, d))
-            ops.scatter_sum(dx2.view(Bn * Lp, d), ctx.pidx.view(-1), self._g(va + "pitch_embedding.weight"), defer=self._deferred_fin, accumulate=self._acc)
-            dx1 = self._predictor_bwd(va + "pitch_predictor.", ctx.preds[va + "pitch_predictor."], dpitch, rng, dx2)
-            if self.use_cwt:
-                # the heads read detached inputs (modules.py:118-119): parameter gradients only, from their own loss terms; the twenty
-                # tensors are one stretch of the flat buffer, summed over the utterances in order by the deferred finalize
-                if dheads is None:
-                    raise RuntimeError("use_cwt: backward_native needs dheads (the gradients of the pitch_mean / pitch_std predictions)")
-                hk = va + "pitch_mean.flat_one.net.0.weight"
-                hpart = ops.cnnscalar_bwd(dheads, ctx.heads_saved, self._m(hk, 2 * ops.CNNSCALAR_FLOATS))
-                self._finalize_ln(hpart, Bn, 2 * ops.CNNSCALAR_FLOATS, hk)
-            ops.scatter_sum(dx1.view(Bn * Lp, d), ctx.speakers, self._g("speaker_emb.weight"), idx_div=Lp, defer=self._deferred_fin, accumulate=self._acc)
-            dxe = self._predictor_bwd(va + "duration_predictor.", ctx.preds[va + "duration_predictor."], dlogd, rng, dx1)
+        if need_below:
+            # ---- length regulator: segment sums (the position table has no parameters)
+            dx3 = ops.length_regulator_bwd(dx.view(Bn, T, d), ctx.cs, Lp).view(Bn * Lp, d)
+            # ---- variance adaptor, reverse order of modules.py:158-193
+            va = "variance_adaptor."
+            if va_on:
+                ops.scatter_sum(dx3, ctx.eidx.view(-1), self._g(va + "energy_embedding.weight"), defer=self._deferred_fin, accumulate=self._acc)
+            if "grouped" in ctx.preds:
+                if pred_dxin is None and pkw:
+                    pred_dxin = self._predictors_bwd_inputs(ctx.preds["grouped"], self._stack3(dlogd, dpitch, denergy), rng, **pkw)
+                dx2, dx1, dxe = self._predictors_bwd_grouped(ctx.preds["grouped"], None if pred_dxin is not None else
+                                                             self._stack3(dlogd, dpitch, denergy), rng, dx3, dxin=pred_dxin)
+                if va_on:
+                    ops.scatter_sum(dx2, ctx.pidx.view(-1), self._g(va + "pitch_embedding.weight"), defer=self._deferred_fin, accumulate=self._acc)
+                if spk_on:
+                    ops.scatter_sum(dx1, ctx.speakers, self._g("speaker_emb.weight"), idx_div=Lp, defer=self._deferred_fin, accumulate=self._acc)
+            else:
+                dx2 = self._predictor_bwd(va + "energy_predictor.", ctx.preds[va + "energy_predictor."], denergy, rng, dx3.view(Bn, Lp, d), **bkw(va_on, True))
+                if va_on:
+                    ops.scatter_sum(dx2.view(Bn * Lp, d), ctx.pidx.view(-1), self._g(va + "pitch_embedding.weight"), defer=self._deferred_fin, accumulate=self._acc)
+                dx1 = self._predictor_bwd(va + "pitch_predictor.", ctx.preds[va + "pitch_predictor."], dpitch, rng, dx2, **bkw(va_on, True))
+                if self.use_cwt:
+                    # the heads read detached inputs (modules.py:118-119): parameter gradients only, from their own loss terms; the twenty
+                    # tensors are one stretch of the flat buffer, summed over the utterances in order by the deferred finalize
+                    if dheads is None:
+                        raise RuntimeError("use_cwt: backward_native needs dheads (the gradients of the pitch_mean / pitch_std predictions)")
+                    hk = va + "pitch_mean.flat_one.net.0.weight"
+                    hpart = ops.cnnscalar_bwd(dheads, ctx.heads_saved, self._m(hk, 2 * ops.CNNSCALAR_FLOATS))
+                    self._finalize_ln(hpart, Bn, 2 * ops.CNNSCALAR_FLOATS, hk)
+                if spk_on:
+                    ops.scatter_sum(dx1.view(Bn * Lp, d), ctx.speakers, self._g("speaker_emb.weight"), idx_div=Lp, defer=self._deferred_fin, accumulate=self._acc)
+                dxe = None
+                if va_on or need_enc:       # (the duration predictor's input gradient feeds nothing but the encoder)
+                    dxe = self._predictor_bwd(va + "duration_predictor.", ctx.preds[va + "duration_predictor."], dlogd, rng, dx1,
+                                              **bkw(va_on, need_enc))
         notify("variance_adaptor")
-        # ---- encoder
-        dx = dxe.view(Bn * Lp, d)
-        for i in range(self.n_enc - 1, -1, -1):
-            dx = self._fft_bwd(ctx.blocks[i], dx, rng, raw_out=self._raw_out_mode() if i > 0 else False)
-            notify("encoder.%d" % i)
-        ops.scatter_sum(dx, ctx.texts.view(-1), self._g("encoder.src_word_emb.weight"), skip_row=0, defer=self._deferred_fin, accumulate=self._acc)   # padding_idx=0
+        # ---- encoder: down to the lowest block whose gradient anything wants
+        if need_enc:
+            dx = dxe.view(Bn * Lp, d)
+            for i in range(self.n_enc - 1, enc_stop - 1, -1):
+                dx = self._fft_bwd(ctx.blocks[i], dx, rng, raw_out=self._raw_out_mode() if i > 0 else False,
+                                   **bkw(enc_on[i], emb_on or i > enc_stop))
+                notify("encoder.%d" % i)
+            if emb_on:
+                ops.scatter_sum(dx, ctx.texts.view(-1), self._g("encoder.src_word_emb.weight"), skip_row=0, defer=self._deferred_fin, accumulate=self._acc)   # padding_idx=0
         notify("embedding")
         ops.stamp("bwd.chain_done")
         self._flush_param_grads()

@@ -1717,6 +1717,78 @@ def optim_step_packed(params, grads, m, v, shadow, state, partials, max_norm, be
           "ttsk_optim_step_packed")
 
 
+def optim_range_tables(ranges, items, device):
+    """Device tables for optim_step_ranges.  ranges: sorted, disjoint [start, end) element ranges of the flat buffers (multiples of 4):
+    what the step may touch.  items: as for adam_pack_tables, the packed weights INSIDE the ranges whose packs the Adam launch is to
+    write (may be empty).  Returns a dict (the tensors must stay alive and the packs where they are), or None when an item does not
+    tile, the ranges overlap or an item sticks out of them."""
+    ranges = sorted((int(a), int(b)) for a, b in ranges)
+    r, acc, pos = [], 0, 0
+    for a, b in ranges:
+        if a < pos or b <= a or a % 4 or b % 4:
+            return None
+        r += [a, b, acc]
+        acc += (b - a) // 4
+        pos = b
+    out = {"ranges": torch.tensor(r if r else [0, 0, 0], dtype=torch.int64).to(device), "n_ranges": len(ranges), "range_floats": acc * 4, "end": pos,
+           "items": None, "n_items": 0, "n_tiles": 0, "gaps": None, "n_gaps": 0, "gap_floats": 0}
+    items = sorted(items, key=lambda it: it[0])
+    if not items:
+        return out
+    arr = (L.AdamItem * len(items))()
+    tile0, gaps, ri = 0, [], 0
+    cursor = ranges[0][0]
+    for i, (off, (Cs, K, Ds), pk, pkt) in enumerate(items):
+        if Cs % 32 or Ds % 256 or off % 4:
+            return None
+        end = off + Cs * K * Ds
+        while ri < len(ranges) and ranges[ri][1] <= off:          # the rest of the ranges in front of this item are gaps
+            if ranges[ri][1] > cursor:
+                gaps.append((cursor, ranges[ri][1]))
+            ri += 1
+            cursor = ranges[ri][0] if ri < len(ranges) else None
+        if ri == len(ranges) or off < cursor or end > ranges[ri][1]:
+            return None
+        if off > cursor:
+            gaps.append((cursor, off))
+        cursor = end
+        arr[i].off, arr[i].pack, arr[i].pack_t = off, _ptr(pk), _ptr(pkt)
+        arr[i].Cs, arr[i].K, arr[i].Ds, arr[i].tile0 = Cs, K, Ds, tile0
+        tile0 += K * (Cs // 32) * (Ds // 256)
+    while ri < len(ranges):
+        if ranges[ri][1] > cursor:
+            gaps.append((cursor, ranges[ri][1]))
+        ri += 1
+        cursor = ranges[ri][0] if ri < len(ranges) else None
+    g, gacc = [], 0
+    for a, b in gaps:
+        g += [a, b, gacc]
+        gacc += (b - a) // 4
+    if tile0 * 8192 + gacc * 4 != acc * 4:
+        return None
+    out.update(items=torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64).clone().to(device), n_items=len(items), n_tiles=tile0,
+               gaps=torch.tensor(g if g else [0, 0, 0], dtype=torch.int64).to(device), n_gaps=len(gaps), gap_floats=gacc * 4)
+    return out
+
+
+@_family("clip_adam", lambda *a, **kw: 0.0)
+def optim_step_ranges(params, grads, m, v, shadow, state, partials, max_norm, beta1, beta2, eps, d_model, warmup, anneal_steps, anneal_rate,
+                      tables, zero_grad=True, advance_rng=False):
+    """The optimizer step over the element ranges of `tables` (optim_range_tables) only: norm, clip, Adam, bf16 shadow and the packs of
+    the tables' items, in two launches (ttsk_optim_step_ranges).  Elements outside the ranges are neither read nor written."""
+    _dev(params, grads, m, v, shadow, state, partials, tables["ranges"], tables["items"], tables["gaps"])
+    n = params.numel()
+    if tables["end"] > n or min(grads.numel(), m.numel(), v.numel(), shadow.numel()) < n:
+        raise L.TtskError("optim_step_ranges: the ranges end at element %d, the buffers hold %d" % (tables["end"], n))
+    arr = (C.c_float * 4)(*([float(a) for a in anneal_steps] + [0.0] * (4 - len(anneal_steps))))
+    check(L.load().ttsk_optim_step_ranges(_ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(shadow), params.numel(), _ptr(state), _ptr(partials),
+                                          max_norm, beta1, beta2, eps, int(zero_grad), float(d_model), float(warmup), C.cast(arr, C.c_void_p),
+                                          len(anneal_steps), anneal_rate, int(advance_rng), _ptr(tables["ranges"]), tables["n_ranges"],
+                                          tables["range_floats"], _ptr(tables["items"]), tables["n_items"], tables["n_tiles"],
+                                          _ptr(tables["gaps"]), tables["n_gaps"], tables["gap_floats"], _stream()),
+          "ttsk_optim_step_ranges")
+
+
 # ---------------------------------------------------------------------------------------------------- HiFi-GAN helpers
 
 def weight_norm_fold(v, g):

@@ -25,6 +25,11 @@ class ScheduledOptim:
         self.anneal_rate = float(opt["anneal_rate"])
         self.d_model = model_config["transformer"]["encoder_hidden"]
         self.init_lr = np.power(self.d_model, -0.5)
+        # Speaker adaptation (FastSpeech2.set_trainable): clip and Adam cover the trainable ranges of the flat buffer only; from here
+        # on the units are fixed (the Adam state, the device tables and the checkpoint layout follow them)
+        self._subset = getattr(model, "trainable_units", None) is not None
+        if hasattr(model, "_optimizer_built"):
+            model._optimizer_built = True
         flat, grad, _ = model.flat_buffers()
         self.exp_avg = torch.zeros_like(flat)
         self.exp_avg_sq = torch.zeros_like(flat)
@@ -55,7 +60,17 @@ class ScheduledOptim:
         leaves zeros, as the reference's `zero_grad()` right after the step does (train.py:54)."""
         flat, grad, shadow = self.model.flat_buffers()
         tables = getattr(self.model, "_adam_tables", None) if getattr(self.model, "window_ffn", False) else None
-        if tables is not None:
+        if self._subset:
+            # norm, clip, Adam, shadow over the trainable ranges only; the Adam launch writes the packs of the trainable packed weights,
+            # the packs of frozen weights are not rewritten (ttsk_optim_step_ranges)
+            rt = self.model._range_tables
+            if rt is None:
+                raise ops.L.TtskError("the subset optimizer step needs the model on a HIP device (no tables were built)")
+            ops.optim_step_ranges(flat, grad, self.exp_avg, self.exp_avg_sq, shadow, self.state, self._partials, self.grad_clip_thresh,
+                                  self.betas[0], self.betas[1], self.eps, self.d_model, self.n_warmup_steps, self.anneal_steps,
+                                  self.anneal_rate, rt, zero_grad=not keep_grads, advance_rng=advance_rng)
+            self.model.refresh_trainable_packs()   # the trainable 80-channel ends, when there are any
+        elif tables is not None:
             # the Adam launch writes the window kernels' fragment-major weight packs itself (tile by tile, from LDS)
             ops.optim_step_packed(flat, grad, self.exp_avg, self.exp_avg_sq, shadow, self.state, self._partials, self.grad_clip_thresh,
                                   self.betas[0], self.betas[1], self.eps, self.d_model, self.n_warmup_steps, self.anneal_steps,
@@ -74,14 +89,19 @@ class ScheduledOptim:
         """reference: ScheduledOptim.zero_grad (optimizer.py:29-30).  After `step_and_update_lr()` the buffer is already zero; in the
         middle of an accumulation cycle this discards it."""
         if getattr(self.model, "grads_partial", False):
-            self.model.flat_buffers()[1].zero_()
+            grad = self.model.flat_buffers()[1]
+            if self._subset:
+                for a, b in self.model.trainable_ranges():     # (frozen stretches are never read: they may hold anything)
+                    grad[a:b].zero_()
+            else:
+                grad.zero_()
             self.model.grads_partial = False
 
     def lr(self):
         return float(self.init_lr * self._get_lr_scale())
 
     def grad_norm(self):
-        """||g|| of the last step (device read)."""
+        """||g|| of the last step (device read); over the trainable elements when units are frozen."""
         return float(self.state[6:7].view(torch.float32)[0])
 
     # -- checkpointing ----------------------------------------------------------------------------------------
@@ -102,12 +122,15 @@ class ScheduledOptim:
         st = self.state.cpu().clone()
         adam_t = int(st[1])
         keys = self._ref_keys()
+        trained = set(self.model.trainable_keys()) if self._subset else None
         state = {}
         if adam_t > 0:
             for i, k in enumerate(keys):
                 en = table[k]
                 if en.kind != P.TRAIN:
                     continue                 # frozen tables / unused CWT heads never get a gradient: Adam holds no state for them
+                if trained is not None and k not in trained:
+                    continue                 # ... nor do the parameters of frozen units (torch: requires_grad_(False))
                 a = m[en.offset:en.offset + en.numel].view(en.storage_shape)
                 b = v[en.offset:en.offset + en.numel].view(en.storage_shape)
                 if en.conv:
@@ -135,11 +158,14 @@ class ScheduledOptim:
         if len(sd["param_groups"][0]["params"]) != len(keys):
             raise ValueError("optimizer state has %d parameters, the model %d" % (len(sd["param_groups"][0]["params"]), len(keys)))
         m, v = torch.zeros(self.exp_avg.shape), torch.zeros(self.exp_avg_sq.shape)
+        trained = set(self.model.trainable_keys()) if self._subset else None
         adam_t = 0
         for i, ent in sd["state"].items():
             en = table[keys[int(i)]]
             if en.kind != P.TRAIN:
                 continue
+            if trained is not None and keys[int(i)] not in trained:
+                continue                     # state of a parameter that is frozen here: ignored
             a, b = ent["exp_avg"].float(), ent["exp_avg_sq"].float()
             if en.conv:
                 a, b = a.permute(0, 2, 1), b.permute(0, 2, 1)

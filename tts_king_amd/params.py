@@ -189,3 +189,62 @@ def reference_parameter_keys(entries_table):
             r += [0 if parts[-1] == "weight" else 1]
         return r
     return sorted(keys, key=rank)
+
+
+# ------------------------------------------------------------------------------------------- trainable units (speaker adaptation)
+# A unit is trained or frozen as a whole (FastSpeech2.set_trainable): the groups of FastSpeech2.backward_group_order() with the
+# speaker table split out of the variance adaptor.  torch: requires_grad_(False) on everything else.
+def unit_names(n_enc, n_dec):
+    """The units in backward order (the order in which backward_native completes their gradients)."""
+    return (["postnet", "mel_linear"] + ["decoder.%d" % i for i in range(n_dec - 1, -1, -1)] + ["variance_adaptor", "speaker_emb"] +
+            ["encoder.%d" % i for i in range(n_enc - 1, -1, -1)] + ["embedding"])
+
+
+def unit_of(key):
+    """The unit a state_dict key belongs to (None: encoder.position_enc / decoder.position_enc, which belong to none)."""
+    parts = key.split(".")
+    if parts[0] in ("postnet", "mel_linear", "variance_adaptor", "speaker_emb"):
+        return parts[0]
+    if parts[0] in ("encoder", "decoder") and parts[1] == "layer_stack":
+        return "%s.%s" % (parts[0], parts[2])
+    if key == "encoder.src_word_emb.weight":
+        return "embedding"
+    return None
+
+
+def parse_units(units, n_enc, n_dec):
+    """`units` (None = everything, or an iterable of unit names; the prefixes "decoder" / "encoder" name every block of the stack) ->
+    None when every unit is named, else a frozenset of unit names.  Unknown names and an empty selection raise."""
+    if units is None:
+        return None
+    if isinstance(units, str):
+        units = [units]
+    valid = unit_names(n_enc, n_dec)
+    out = set()
+    for u in units:
+        if u in ("decoder", "encoder"):
+            out.update(v for v in valid if v.startswith(u + "."))
+        elif u in valid:
+            out.add(u)
+        else:
+            raise ValueError("unknown trainable unit %r; valid: %s (and the prefixes 'decoder', 'encoder')" % (u, ", ".join(valid)))
+    if not out:
+        raise ValueError("train_only names no unit; valid: %s (and the prefixes 'decoder', 'encoder')" % ", ".join(valid))
+    return None if len(out) == len(valid) else frozenset(out)
+
+
+def unit_ranges(table, total, units, align=8):
+    """Sorted, merged [start, end) ranges of the flat buffer that hold the TRAIN entries of `units` (None: one range over everything),
+    cut at entry boundaries with each entry's alignment padding included."""
+    if units is None:
+        return [(0, total)]
+    out = []
+    for key, en in table.items():
+        if en.kind != TRAIN or unit_of(key) not in units:
+            continue
+        end = en.offset + (en.numel + align - 1) // align * align
+        if out and out[-1][1] == en.offset:
+            out[-1] = (out[-1][0], end)
+        else:
+            out.append((en.offset, end))
+    return out

@@ -35,19 +35,61 @@ def to_device(data, device="cuda:0", non_blocking=False):
     raise ValueError("batch tuple must have 15 (train) or 6 (inference) entries, got %d" % len(data))
 
 
+def grow_speaker_table(emb, n_speakers, init_row=None):
+    """A loaded speaker table (rows, d) for a model with `n_speakers` names.  Equal counts: the table as it is.  Fewer rows than names
+    (new voices were added to speakers.json): the loaded rows keep their indices, every extra row starts as the mean of the loaded
+    rows (fp32, summed in row order: the same bits everywhere) or as a copy of row `init_row`.  More rows than names raises."""
+    rows = int(emb.shape[0])
+    if rows > n_speakers:
+        raise ValueError("the checkpoint's speaker embedding has %d rows, speakers.json names only %d speakers" % (rows, n_speakers))
+    if rows == n_speakers:
+        return emb
+    if init_row is not None and not 0 <= int(init_row) < rows:
+        raise ValueError("new_speaker_init: speaker index %d is not among the %d loaded rows" % (int(init_row), rows))
+    e32 = emb.detach().float().cpu()
+    if init_row is None:
+        acc = torch.zeros(e32.shape[1], dtype=torch.float32)
+        for r in range(rows):
+            acc += e32[r]
+        new = acc / float(rows)
+    else:
+        new = e32[int(init_row)]
+    return torch.cat([e32, new.view(1, -1).repeat(n_speakers - rows, 1)], 0).to(emb.dtype)
+
+
+def _speaker_index(cfg, name):
+    import json
+    with open(os.path.join(cfg.preprocess_config["path"]["preprocessed_path"], "speakers.json")) as f:
+        speakers = json.load(f)
+    if name not in speakers:
+        raise ValueError("mi355x.new_speaker_init: speaker %r is not in speakers.json" % (name,))
+    return int(speakers[name]) if isinstance(speakers, dict) else list(speakers).index(name)
+
+
 def get_model(cfg, device, train=False):
     """reference: fs_two/utils/model.py:12-38.  `cfg.tts.load_path` (absent from the shipped config) is optional;
     the speaker embedding is re-inserted with the rule of fsapi.py:28-30 (the reference's training-resume path
-    silently drops it)."""
-    model = FastSpeech2(cfg.preprocess_config, cfg.model_config, device=device,
-                        seed=int(cfg.get("mi355x", {}).get("seed", 1234)) if hasattr(cfg, "get") else 1234)
+    silently drops it).  `mi355x.train_only: [unit, ...]` trains those parameter groups only
+    (FastSpeech2.set_trainable); a loaded speaker table with fewer rows than speakers.json has names is grown (grow_speaker_table,
+    `mi355x.new_speaker_init`: the name of the speaker whose row the new ones copy; default: the mean row)."""
+    mi = (cfg.get("mi355x", {}) or {}) if hasattr(cfg, "get") else {}
+    train_only = mi.get("train_only")
+    if train_only is not None and int(mi.get("gpus", 1)) > 1:
+        raise NotImplementedError("mi355x.train_only together with mi355x.gpus > 1 is not supported (the gradient reducer's buckets and "
+                                  "group announcements assume every group completes)")
+    model = FastSpeech2(cfg.preprocess_config, cfg.model_config, device=device, seed=int(mi.get("seed", 1234)))
+    if train_only is not None:
+        model.set_trainable(list(train_only))
     load_path = cfg.tts.get("load_path") if hasattr(cfg.tts, "get") else None
     ckpt = None
     if load_path:
         ckpt = torch.load(load_path, map_location="cpu")
         state = dict(ckpt["model"])
         if "embedding" in ckpt:
-            state["speaker_emb.weight"] = ckpt["embedding"]
+            init = mi.get("new_speaker_init")
+            rows = int(ckpt["embedding"].shape[0])
+            state["speaker_emb.weight"] = grow_speaker_table(ckpt["embedding"], model.n_speakers,
+                                                             _speaker_index(cfg, init) if (init is not None and rows < model.n_speakers) else None)
         model.load_state_dict(state, strict=False)
     if train:
         model.train()
@@ -76,6 +118,8 @@ def main_train_step(model, batch, step, optimizer, cfg, Loss, reducer=None):
     Everything up to the final read of the loss values is enqueued without host synchronisation; `reducer`
     (tts_king_amd.parallel.GradReducer) all-reduces gradient buckets on a side stream while backward runs."""
     grad_acc_step = cfg.train_config["optimizer"]["grad_acc_step"]
+    if reducer is not None and getattr(model, "trainable_units", None) is not None:
+        raise NotImplementedError("train_only together with a gradient reducer is not supported")
     if not model.training:
         model.train()
     dev = model.device
