@@ -406,7 +406,11 @@ int ttsk_softmax_bwd(const void* probs_bf16, const float* dprobs, void* dscores_
  * bwd: delta_ws [B*H][S] fp32 scratch; writes ALL of dqkv [B*S][3*d] (dQ | dK | dV, head h at columns h*128 of each part),
  * two launches (delta = rowsum(dO o O); then the query side (dQ) and the key side (dK, dV) as one grid), no atomics.
  * o_f32 [B*S][d] (may be NULL): O before its rounding to bf16.  The backward's delta = rowsum(dO o O) is what dP is cancelled
- * against; taken from the bf16 O its 2^-9 error dominates small dQ / dK gradients, so a training forward keeps the fp32 copy. */
+ * against; taken from the bf16 O its 2^-9 error dominates small dQ / dK gradients, so a training forward keeps the fp32 copy.
+ * Contracts at the edges (pinned by tests/test_flash_edges_gpu.py):
+ *   - lens[b] is clamped to S; an utterance with lens[b] <= 0 has no keys and yields O = 0, o_f32 = 0, lse = 0 and zero dQ, dK, dV;
+ *   - K and V rows at keys >= lens[b] (and < S) are read and multiplied by an exact 0: they must be FINITE (0 * Inf is NaN inside the
+ *     MFMA), and whatever finite values they hold changes no output bit; their dK / dV rows are written as exact zeros. */
 int ttsk_flash_attention_fwd(const void* qkv_bf16, void* o_bf16, float* o_f32 /* may be NULL */, float* lse /* may be NULL */,
                              const int64_t* lens, int B, int H, int S, int d, float scale, void* stream);
 /* delta_ready = 1: delta_ws already holds delta (the producer of dout wrote it: ttsk_win_conv with delta_out), no delta launch. */

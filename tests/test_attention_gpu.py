@@ -2,26 +2,20 @@
 general scores-GEMM + softmax path inside a train step.
 reference: fs_two/transformer/Modules.py:14-24, SubLayers.py:44-60.  Tolerances: O is rounded to bf16 once (2^-8 relative), the
 gradients additionally see the bf16 rounding of P and dS (stated at the assertions).  Ragged key lengths, a sequence shorter
-than one tile, one that is not a tile multiple and one past max_seq_len are covered."""
+than one tile, one that is not a tile multiple and one past max_seq_len are covered.
+
+These cases have near-uniform scores (random weights), key lengths in [S/2, S], B*H no multiple of 8 and a whole-tensor max-abs
+metric.  tests/test_flash_edges_gpu.py holds the same kernels to the same bars per (batch, head) slab and per query row on peaked
+scores, key lengths 0, 1, 2 and around the 64- / 128-key seams, S = 1, 63, 65, 128, 129, the XCD workgroup remap (B*H % 8 == 0) and
+the delta-given entry; tests/flash_ref.py is the reference both files share."""
 import pytest
 import torch
+
+from tests.flash_ref import ref_attention
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 BF = torch.bfloat16
-
-
-def ref_attention(qkv, lens, B, H, S):
-    d = qkv.shape[1] // 3
-    dk = d // H
-    x = qkv.double().view(B, S, 3, H, dk)
-    q, k, v = x[:, :, 0].permute(0, 2, 1, 3), x[:, :, 1].permute(0, 2, 1, 3), x[:, :, 2].permute(0, 2, 1, 3)   # (B,H,S,dk)
-    s = q @ k.transpose(-1, -2) / dk ** 0.5
-    mask = torch.arange(S)[None, :] >= lens[:, None]
-    s = s.masked_fill(mask[:, None, None, :], float("-inf"))
-    p = torch.softmax(s, dim=-1)
-    o = (p @ v).permute(0, 2, 1, 3).reshape(B * S, d)
-    return p.reshape(B * H, S, S), o, (q, k, v)
 
 
 def test_flash_and_gemm_softmax_paths_agree(cfg):
