@@ -27,25 +27,43 @@ from tts_king_amd.synthetic import make_mel, seeded_fill
 SPF = 256
 
 
-def generator_any(sd, h, mel):
-    """hifi/models.py:185-201 with ResBlock1 (:88-95) or ResBlock2 (:134-140), folded weights, any dtype."""
-    lr = lambda t: F.leaky_relu(t, 0.1)
-    x = F.conv1d(mel, sd["conv_pre.weight"], sd["conv_pre.bias"], padding=3)
+def generator_any(sd, h, mel, q=None, mutation=None):
+    """hifi/models.py:185-201 with ResBlock1 (:88-95) or ResBlock2 (:134-140), folded weights, any dtype.
+
+    `q`: a rounding applied to every tensor the HIP path stores between layers (conv outputs, residual sums, activated copies, the
+    MRF average): the calibration of a storage type's error (tests/test_hifigan_generic_gpu.py).  `mutation`: one deliberate defect
+    of the conv-by-conv route, for the negative controls (tests/test_hifigan_v2_cpu.py): "drop_tap" (the last tap of phase 0 of the
+    third upsampler is lost), "zero_cols" (output channels 8..15 of the first conv of the first C = 16 block stay zero) or
+    "c2_before_residual" (a ResBlock1 pair hands on lrelu(conv) in place of lrelu(conv + x) at the C = 16 and C = 8 stages)."""
+    assert mutation in (None, "drop_tap", "zero_cols", "c2_before_residual")
+    q = q or (lambda t: t)
+    lr = lambda t: q(F.leaky_relu(t, 0.1))
+    x = q(F.conv1d(mel, sd["conv_pre.weight"], sd["conv_pre.bias"], padding=3))
     nk = len(h["resblock_kernel_sizes"])
     for i, (u, k) in enumerate(zip(h["upsample_rates"], h["upsample_kernel_sizes"])):
-        x = F.conv_transpose1d(lr(x), sd["ups.%d.weight" % i], sd["ups.%d.bias" % i], stride=u, padding=(k - u) // 2)
+        wu = sd["ups.%d.weight" % i]
+        if mutation == "drop_tap" and i == 2:
+            wu = wu.clone()
+            wu[:, :, (k - u) // 2 + (k // u - 1) * u] = 0              # phase 0 = taps p, p + u, ...: its last one
+        x = q(F.conv_transpose1d(lr(x), wu, sd["ups.%d.bias" % i], stride=u, padding=(k - u) // 2))
         xs = 0
         for j, (rk, rd) in enumerate(zip(h["resblock_kernel_sizes"], h["resblock_dilation_sizes"])):
             p, y = "resblocks.%d." % (i * nk + j), x
+            yl = lr(y)
             for m, d in enumerate(rd):
                 if str(h["resblock"]) == "1":
-                    t = F.conv1d(lr(y), sd[p + "convs1.%d.weight" % m], sd[p + "convs1.%d.bias" % m], dilation=d, padding=(rk * d - d) // 2)
-                    y = F.conv1d(lr(t), sd[p + "convs2.%d.weight" % m], sd[p + "convs2.%d.bias" % m], padding=(rk - 1) // 2) + y
+                    t = F.conv1d(yl, sd[p + "convs1.%d.weight" % m], sd[p + "convs1.%d.bias" % m], dilation=d, padding=(rk * d - d) // 2)
+                    if mutation == "zero_cols" and (i, j, m) == (2, 0, 0):
+                        t = t.clone()
+                        t[:, 8:16] = 0
+                    c = F.conv1d(lr(q(t)), sd[p + "convs2.%d.weight" % m], sd[p + "convs2.%d.bias" % m], padding=(rk - 1) // 2)
                 else:
-                    y = F.conv1d(lr(y), sd[p + "convs.%d.weight" % m], sd[p + "convs.%d.bias" % m], dilation=d, padding=(rk * d - d) // 2) + y
+                    c = F.conv1d(yl, sd[p + "convs.%d.weight" % m], sd[p + "convs.%d.bias" % m], dilation=d, padding=(rk * d - d) // 2)
+                y = q(c + y)
+                yl = lr(c) if mutation == "c2_before_residual" and i >= 2 else lr(y)
             xs = xs + y
-        x = xs / nk
-    return torch.tanh(F.conv1d(F.leaky_relu(x), sd["conv_post.weight"], sd["conv_post.bias"], padding=3))
+        x = q(xs / nk)
+    return torch.tanh(F.conv1d(q(F.leaky_relu(x)), sd["conv_post.weight"], sd["conv_post.bias"], padding=3))
 
 
 def v3_hifi(cfg):

@@ -252,6 +252,38 @@ def g12_hifigan_v3():
           "keys", len(wn_keys), len(folded))
 
 
+# the published HiFi-GAN V2 generator (config_v2): V1's ResBlock1s and upsamplers from 128 channels (128 -> 64 -> 32 -> 16 -> 8)
+HIFI_V2 = dict(resblock="1", upsample_rates=[8, 8, 2, 2], upsample_kernel_sizes=[16, 16, 4, 4], upsample_initial_channel=128,
+               resblock_kernel_sizes=[3, 7, 11], resblock_dilation_sizes=[[1, 3, 5], [1, 3, 5], [1, 3, 5]])
+
+
+def g13_hifigan_v2():
+    """g12_hifigan_v3 for the V2 generator: the mel, the waveform, both key / shape lists and the configuration values in one file
+    (the two narrow stages, C = 16 and C = 8, are what no other fixture has)."""
+    h = AD(dict(cfg.hifi, **HIFI_V2))
+    torch.manual_seed(0)
+    gen = Generator(h)
+    sd_wn = gen.state_dict()
+    seeded_fill(sd_wn, WEIGHT_SEED)
+    wn_keys, wn_shapes = list(sd_wn.keys()), [";".join(map(str, v.shape)) for v in sd_wn.values()]
+    gen.remove_weight_norm()
+    gen.eval()
+    folded = gen.state_dict()
+    mel = make_mel(2, 32, seed=21)
+    with torch.no_grad():
+        wav = gen(mel)
+    probe = ["ups.0.weight", "ups.3.weight", "conv_pre.weight", "resblocks.11.convs1.2.weight", "conv_post.weight"]
+    np.savez_compressed(os.path.join(OUT, "hifi_v2_b2_t32.npz"), B=2, T=32, seed=21, weight_seed=WEIGHT_SEED,
+                        mel=npy(mel), wav=npy(wav), n_wn_keys=len(wn_keys), n_folded_keys=len(folded),
+                        wn_keys=np.array(wn_keys), wn_shapes=np.array(wn_shapes), keys=np.array(list(folded.keys())),
+                        shapes=np.array([";".join(map(str, v.shape)) for v in folded.values()]),
+                        **{("cfg/" + k): np.array(v) for k, v in HIFI_V2.items()},
+                        **{("fold/" + k): npy(folded[k]).ravel()[:64] for k in probe},
+                        **{("foldnorm/" + k): float(folded[k].norm()) for k in probe})
+    print("G13 V2 wav", tuple(wav.shape), "absmax", float(wav.abs().max()), "rms", float(wav.pow(2).mean().sqrt()),
+          "keys", len(wn_keys), len(folded))
+
+
 def g9_text():
     """Symbol inventory (data asset pretrained/symbols.json: the id of a symbol is its position + the model's vocabulary
     is len + 1, Models.py:40) and known-answer vectors of `text_to_sequence` (examples.ipynb cell 2 plus a few more)."""
@@ -355,6 +387,9 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "hifi_v3":
         g12_hifigan_v3()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "hifi_v2":
+        g13_hifigan_v2()
+        sys.exit(0)
     g1_eval_teacher_forced()
     g2_eval_free_running()
     g3_train_no_dropout()
@@ -366,3 +401,4 @@ if __name__ == "__main__":
     g10_collate()
     g11_mel()
     g12_hifigan_v3()
+    g13_hifigan_v2()

@@ -83,6 +83,8 @@ class Generator(nn.Module):
         self.h = h
         self.num_kernels = len(h.resblock_kernel_sizes)
         self.num_upsamples = len(h.upsample_rates)
+        for i, (u, k) in enumerate(zip(h.upsample_rates, h.upsample_kernel_sizes)):
+            ops.check_upsampler(int(k), int(u), "HiFi-GAN upsampler %d" % i)
         c0 = h.upsample_initial_channel
         self.conv_pre = _WNConv((c0, 80, 7), c0)                       # 80 is hard-coded in the reference (:152)
         self.ups = nn.ModuleList()
@@ -148,6 +150,7 @@ class Generator(nn.Module):
         key = self._weights_key() + (dt,)
         if self._packed is not None and self._packed_key == key:
             return self._packed
+        self._check_mrf()
         pk = {}
         pk["pre"] = (ops.pack_conv_weight(self.conv_pre.folded_weight(), dtype=dt), self.conv_pre.bias.data)
         cpre, kpre = pk["pre"][0].shape[0], pk["pre"][0].shape[1]
@@ -443,21 +446,37 @@ class Generator(nn.Module):
 
     _short_rows_memo = None
 
-    def _short_rows_walk(self):
-        pk, nk = self._prepare(), self.num_kernels
+    def stage_routes(self):
+        """Per MRF stage, the kernel family `forward_ntc` runs it on: "resblock2" (fused ResBlock2), "pair" (conv pairs), "fused" (the
+        six-conv ResBlock1 kernel / the fused last stage) or "gemm" (conv by conv on the implicit-GEMM kernel).  From the configuration
+        and the toggles on this object alone — the same conditions as `_prepare`'s packs and `forward_ntc`'s route choice."""
+        nk, routes = self.num_kernels, []
         for i in range(self.num_upsamples):
-            idx = range(i * nk, (i + 1) * nk)
-            rbs = [self.resblocks[j] for j in idx]
-            C_out = pk["ups"][i][0].shape[1]
-            if self.resblock2_fused and nk >= 2 and all(pk["rb2"][j] is not None for j in idx):
-                continue
+            rbs = [self.resblocks[j] for j in range(i * nk, (i + 1) * nk)]
+            C_out = self.ups[i].bias.shape[0]
             want_pair = (self.conv_pair and self.window_conv) if C_out >= 128 else (self.conv_pair_small and self.fused and C_out == 64)
-            if want_pair and self._pair_packs(pk, i, nk, rbs, C_out) is not None:
-                continue
-            if self.fused and nk >= 2 and all(pk["rbf"][j] is not None for j in idx):
-                continue
-            return False
-        return True
+            if self.resblock2_fused and nk >= 2 and all(rb.kind == "2" and len(rb.dilation) == 2 and
+                                                        ops.hifi_resblock2_supported(C_out, rb.k, *rb.dilation) for rb in rbs):
+                routes.append("resblock2")
+            elif want_pair and nk >= 2 and all(rb.kind == "1" and all(ops.hifi_conv_pair_supported(C_out, rb.k, d) for d in rb.dilation) for rb in rbs):
+                routes.append("pair")
+            elif self.fused and nk >= 2 and all(rb.kind == "1" and ops.hifi_resblock1_supported(C_out, rb.k) for rb in rbs):
+                routes.append("fused")
+            else:
+                routes.append("gemm")
+        return routes
+
+    def _check_mrf(self):
+        """The conv-by-conv route averages exactly three ResBlocks per stage (ttsk_avg3): any other count is refused before a launch."""
+        if self.num_kernels != 3:
+            for i, r in enumerate(self.stage_routes()):
+                if r == "gemm":
+                    raise NotImplementedError("HiFi-GAN stage %d runs conv by conv, where the MRF average is written for 3 resblock kernels "
+                                              "per stage (got %d)" % (i, self.num_kernels))
+
+    def _short_rows_walk(self):
+        self._prepare()
+        return "gemm" not in self.stage_routes()
 
     def plan(self, lens):
         """The window plan of a call on this generator: short utterances as rows of the batch where `short_rows()` allows."""

@@ -735,12 +735,22 @@ def dwgemm_batch(items, max_wgs=0):
     return reduce
 
 
+def check_upsampler(k, stride, what):
+    """Every upsampler kernel here computes ConvTranspose1d(k, stride, padding=(k - stride) // 2) as `stride` phases of k // stride
+    taps each, T * stride samples out.  That is torch's layer only when stride divides k (else the low phases own one tap more, which
+    would be dropped) and k - stride is even (else torch's output is one sample longer): anything else is refused, by name."""
+    if k < stride or k % stride != 0 or (k - stride) % 2 != 0:
+        raise L.TtskError("%s: kernel size %d with stride %d is not supported (the stride must divide the kernel size and their "
+                          "difference must be even)" % (what, k, stride))
+
+
 def conv_transpose1d(x, Wp, bias, stride, k, out=None, in_slope=0.0, flags=0, C2=None, out_slope=0.0, **kw):
     """ConvTranspose1d(padding=(k-stride)//2) as `stride` polyphase implicit GEMMs.
     x (B,T,Cin) bf16, Wp (k, Cout, Cin) bf16 (tap-major repack of torch's (Cin,Cout,k)) -> (B,T*stride,Cout).
     reference: hifi/models.py:166-176,189."""
     Bsz, T, Cin = x.shape
     Cout = Wp.shape[1]
+    check_upsampler(k, stride, "conv_transpose1d")
     p = (k - stride) // 2
     if out is None:
         out = torch.empty(Bsz, T * stride, Cout, dtype=x.dtype, device=x.device)
