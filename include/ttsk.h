@@ -506,6 +506,29 @@ int ttsk_mel_windows(const float* src, int64_t stride_t, int64_t stride_c, int64
 int ttsk_wav_stitch(const float* src, const int32_t* plan, void* dst, int64_t n_dst_frames, int to_i16, float scale, int N, int W,
                     int spf, void* stream);
 
+/* ------------------------------------------------------------------------------------ sample-rate conversion
+ * The flat waveform buffer (utterances back to back, what ttsk_wav_stitch writes with to_i16 = 0) resampled by the rational factor
+ * L / M with a polyphase FIR (tts_king_amd/resample.py designs it).  Driven by the device-resident segment
+ * table, TTSK_SEG_ROW int32 per utterance, 16-byte aligned:
+ *   [0] src_off   first sample of the utterance in src        [1] src_len   its samples; 0 = an empty padding row
+ *   [2] dst_off   first sample of the utterance in dst        [3] dst_len   samples to write (the planner: ceil(src_len * L / M))
+ * so lengths are data and a captured graph holds for every call with the same n_segs and n_dst.
+ * Coefficient table: fp32, tap-major: P rows (taps) of L phases, T[p][q] at table[q * L + p] (a wave reads one row per tap); C is
+ * the tap that meets x[j0].  The table and C are arguments: any table runs.  Output sample m of a segment:
+ *   y[m] = sum_{q = 0 .. P-1} T[p][q] * x[j0 + C - q],   u = m * M (64-bit), p = u mod L, j0 = u div L,
+ * with x[j] = 0 outside [0, src_len) of its own segment (a neighbour's samples are never read as signal), accumulated in fp32 by
+ * one thread in the order of q: the value depends on the segment's samples, the table and m only.
+ * Exactly dst_len samples per segment are written and nothing else (gaps and the tail of dst keep their bytes); segments may start
+ * anywhere.  A row that does not fit n_src / n_dst is skipped.  to_i16 = 0: fp32; 1: int16 = (int)clamp(y * scale, -32768, 32767),
+ * truncated toward zero: ttsk_to_int16's arithmetic in range, saturating out of it (a resampler overshoots a near-full-scale
+ * signal; the low 16 bits would wrap that into a click).
+ * resample_tile (host only): samples of dst one workgroup serves for this filter, 0 for a filter ttsk_resample refuses.  Tiles may
+ * straddle segments, so no planner needs it; it tells a test where the tile edges lie. */
+#define TTSK_SEG_ROW 4
+int ttsk_resample_tile(int L, int M, int P);
+int ttsk_resample(const float* src, int64_t n_src, const int32_t* segs, int n_segs, const float* table, int L, int M, int P, int C,
+                  void* dst, int64_t n_dst, int to_i16, float scale, void* stream);
+
 /* ------------------------------------------------------------------------------------ HiFi-GAN generator
  * reference: hifi/models.py:146-210 (Generator), :12-95 (ResBlock1), hifi/vocoder/utils.py:24-37.
  * 16-bit tensors of this family are bf16 (f16 = 0) or IEEE fp16 (f16 = 1; what hifigan.py uses: the generator is

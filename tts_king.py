@@ -48,26 +48,28 @@ class TTSKing:
             speaker = self.speakers[speaker]
         return self.tts.generate(phonemes, duration_control, pitch_control, energy_control, speaker_name=speaker)
 
-    def mel_to_wav(self, mel_spec):
+    def mel_to_wav(self, mel_spec, sample_rate=None):
         """(1, T, 80) mel -> int16 ndarray (1, 1, 256 T).  reference: tts_king.py:47-49.
         A list of (1, T_i, 80) mels of any lengths -> a list of such arrays, vocoded together as fixed-size windows
-        (`HIFIapi.generate_ragged`); a one-element list is how a single long utterance gets onto the bounded graph set."""
+        (`HIFIapi.generate_ragged`); a one-element list is how a single long utterance gets onto the bounded graph set.
+        `sample_rate` (Hz): the waveform at that rate, ceil(256 T L / M) samples, resampled on the device (`HIFIapi.generate`)."""
         if isinstance(mel_spec, (list, tuple)):
-            return self.vocoder.generate_ragged(mel_spec, frames_first=True)
-        return self.vocoder.generate(mel_spec.transpose(1, 2))
+            return self.vocoder.generate_ragged(mel_spec, frames_first=True, sample_rate=sample_rate)
+        return self.vocoder.generate(mel_spec.transpose(1, 2), sample_rate=sample_rate)
 
     def speak(self, text, duration_control=1.0, pitch_control=1.0, energy_control=1.0, speaker=0, durations=None, pitch=None, energy=None,
-              target_frames=None, return_prosody=False):
+              target_frames=None, return_prosody=False, sample_rate=None):
         """reference: tts_king.py:51-57 calls a missing `generate_mel_batch`; here: mel -> float waveform.  A list of texts -> a list
         of float waveforms (1, 1, 256 T_i) on the device: the batched mels go straight into the vocoder's ragged route.  The prosody
-        arguments are `generate_mel`'s (`target_frames` frames are 256 * target_frames samples); `return_prosody`: (waveforms, prosody)."""
+        arguments are `generate_mel`'s (`target_frames` frames are 256 * target_frames samples); `return_prosody`: (waveforms, prosody).
+        `sample_rate` (Hz): the waveforms at that rate (`HIFIapi.__call__` / `call_ragged`)."""
         out = self.generate_mel(text, duration_control, pitch_control, energy_control, speaker, durations=durations, pitch=pitch, energy=energy,
                                 target_frames=target_frames, return_prosody=return_prosody)
         mels, prosody = out if return_prosody else (out, None)
         if isinstance(text, (list, tuple)):
-            wav = self.vocoder.call_ragged(mels, frames_first=True)
+            wav = self.vocoder.call_ragged(mels, frames_first=True, sample_rate=sample_rate)
         else:
-            wav = self.vocoder(mels.transpose(1, 2))
+            wav = self.vocoder(mels.transpose(1, 2), sample_rate=sample_rate)
         return (wav, prosody) if return_prosody else wav
 
     def text_preprocess(self, text):

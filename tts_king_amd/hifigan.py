@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from . import resample
 from . import switches
 from . import windows
 from .ops import bf16, f16
@@ -496,15 +497,59 @@ class Generator(nn.Module):
             (v[o:o + T] if frames_first else v[:, o:o + T]).copy_(mels[i], non_blocking=True)
         return stage
 
-    def forward_windows(self, stage, table, frames_first=False, int16_scale=None, row_lengths=False):
+    def resampler(self, sample_rate):
+        """None for `sample_rate` None or the generator's own rate (the native route: no launch is added), otherwise the filter from
+        `h.sampling_rate` to `sample_rate` on the generator's device (`resample.Filter`; ValueError for a rate it refuses)."""
+        if sample_rate is None:
+            return None
+        native = int(windows._get(self.h, "sampling_rate"))
+        if resample.check_rate(sample_rate) == native:
+            return None
+        return resample.filter_for(native, int(sample_rate), self.conv_pre.bias.device)
+
+    def row_segments(self, Bn, n, sample_rate):
+        """The segment table of B rows of n samples each for `sample_rate`, (B, 4) int32 on the generator's device."""
+        filt = self.resampler(sample_rate)
+        return torch.from_numpy(resample.row_segments(Bn, n, filt.L, filt.M).table).to(self.conv_pre.bias.device)
+
+    def resample_rows(self, y, sample_rate, int16_scale=None, segs=None):
+        """y (B, 1, n) fp32 waveforms at the generator's rate -> (B, 1, ceil(n L / M)) at `sample_rate` (a rate `resampler` has a
+        filter for), every row resampled as an utterance of its own: fp32, or with `int16_scale` saturated int16.  `segs`: the
+        table `row_segments(B, n, sample_rate)` gave (a caller that repeats a shape, or captures the call, keeps it)."""
+        filt = self.resampler(sample_rate)
+        Bn, n = int(y.shape[0]), int(y.shape[-1])
+        if segs is None:
+            segs = self.row_segments(Bn, n, sample_rate)
+        n_dst = Bn * resample.out_len(n, filt.L, filt.M)
+        out = torch.empty(n_dst, dtype=torch.float32 if int16_scale is None else torch.int16, device=y.device)
+        ops.resample(y.contiguous().view(-1), segs, filt, out=out, int16_scale=int16_scale)
+        return out.view(Bn, 1, n_dst // Bn)
+
+    def forward_windows(self, stage, table, frames_first=False, int16_scale=None, row_lengths=False, sample_rate=None, segs=None):
         """Gather -> generator -> stitch on device-resident inputs (capturable: nothing here depends on a length): the staging buffer
         and the plan table (N, 8) int32 -> one flat buffer of N * W * 256 samples, the kept samples of every utterance back to back.
         `row_lengths` (a plan with `has_short_rows`): the generator reads every row's valid frames from the table's column VALID, on
-        the kernels that take a per-row length; without it the launches are those of a batch of full windows."""
+        the kernels that take a per-row length; without it the launches are those of a batch of full windows.
+        `sample_rate` (other than the generator's) with `segs`, the plan's segment table (N, 4) int32 on the device (`plan_resample`):
+        the stitch writes fp32 at the generator's rate and one more launch resamples that buffer by the table (and converts to int16
+        when asked, saturating): the flat buffer, ceil(N W 256 L / M) + N samples, holds the utterances where the table's dst_off put them."""
         with torch.no_grad():
             a0 = ops.mel_windows(stage, table, windows.W, self.act_dtype, frames_first)
             y = self.forward_ntc(a0, row_frames=table[:, windows.VALID] if row_lengths else None)
-            return ops.wav_stitch(y, table, windows.W, int16_scale=int16_scale)
+            filt = self.resampler(sample_rate)
+            if filt is None:
+                return ops.wav_stitch(y, table, windows.W, int16_scale=int16_scale)
+            if segs is None or tuple(segs.shape) != (table.shape[0], resample.ROW):
+                raise ops.L.TtskError("forward_windows: sample_rate needs `segs`, the plan's (N, 4) segment table on the device")
+            flat = ops.wav_stitch(y, table, windows.W)
+            n_dst = resample.out_bound(flat.numel(), table.shape[0], filt.L, filt.M)
+            out = torch.empty(n_dst, dtype=torch.float32 if int16_scale is None else torch.int16, device=flat.device)
+            return ops.resample(flat, segs, filt, out=out, int16_scale=int16_scale)
+
+    def plan_resample(self, plan, filt):
+        """The segment table of `plan` for `filt` (kept on the plan as `plan.segs`, where `resample.split` finds it)."""
+        plan.segs = resample.plan_segments(plan, self.samples_per_frame(), filt.L, filt.M)
+        return plan.segs
 
     @staticmethod
     def ragged_mels(mels, frames_first=False):
@@ -518,39 +563,53 @@ class Generator(nn.Module):
             out.append(m)
         return out, [int(m.shape[0 if frames_first else 1]) for m in out]
 
-    def forward_ragged_flat(self, mels, frames_first=False, int16_scale=None):
+    def forward_ragged_flat(self, mels, frames_first=False, int16_scale=None, sample_rate=None):
         """The windowed part of `forward_ragged`: (flat buffer of the planned utterances' samples, back to back, or None when no
-        utterance fills a window; the plan; samples per frame).  `int16_scale`: the buffer is int16, truncation of waveform * scale."""
+        utterance fills a window; the plan; samples per frame).  `int16_scale`: the buffer is int16, truncation of waveform * scale.
+        `sample_rate` (other than the generator's): the buffer holds the resampled utterances as `plan.segs` lays them out (cut it
+        with `resample.split`), int16 saturated."""
         mels, lens = self.ragged_mels(mels, frames_first)
         dev = self.conv_pre.bias.device
         if dev.type != "cuda":
             raise ops.L.TtskError("HiFi-GAN ragged vocoding needs the generator's weights on a HIP device; there is no CPU path")
+        filt = self.resampler(sample_rate)                  # a rate the resampler refuses fails before any launch
         plan = self.plan(lens)
         if not plan.planned:
             return None, plan, self.samples_per_frame()
         stage = self.stage_mels(mels, plan, frames_first)
         table = torch.from_numpy(plan.table).to(dev)
-        return self.forward_windows(stage, table, frames_first, int16_scale, plan.has_short_rows), plan, self.samples_per_frame()
+        segs = None
+        if filt is not None:
+            segs = torch.from_numpy(self.plan_resample(plan, filt).table).to(dev)
+        return self.forward_windows(stage, table, frames_first, int16_scale, plan.has_short_rows, sample_rate, segs), plan, self.samples_per_frame()
 
-    def forward_short(self, mels, plan, frames_first=False, int16_scale=None, forward=None):
+    def forward_short(self, mels, plan, frames_first=False, int16_scale=None, forward=None, sample_rate=None):
         """The utterances the plan left out (`plan.short`: those shorter than a window on a generator without `short_rows()`), each
-        through `forward` (or the caller's `forward`) on its own: {index: waveform}."""
+        through `forward` (or the caller's `forward`) on its own: {index: waveform}.  `sample_rate`: each is then resampled alone, with
+        a one-row segment table."""
         mels, _ = self.ragged_mels(mels, frames_first)
+        filt = self.resampler(sample_rate)
         out = {}
         for i in plan.short:
             m = mels[i].to(self.conv_pre.bias.device).float()
             y = (forward or self.forward)((m.t() if frames_first else m).unsqueeze(0))
-            out[i] = y if int16_scale is None else ops.to_int16(y, float(int16_scale))
+            if filt is not None:
+                out[i] = self.resample_rows(y, sample_rate, int16_scale)
+            else:
+                out[i] = y if int16_scale is None else ops.to_int16(y, float(int16_scale))
         return out
 
-    def forward_ragged(self, mels, frames_first=False):
+    def forward_ragged(self, mels, frames_first=False, sample_rate=None):
         """mels: a list of (80, T_i) or (1, 80, T_i) tensors of any lengths (`frames_first`: (T_i, 80) / (1, T_i, 80), FastSpeech2's
         layout) -> a list of (1, 1, 256 T_i) fp32 waveforms, each what `forward` gives for that mel alone (tts_king_amd/windows.py).
 
         The utterances run together as fixed-size windows: one gather launch, the generator on (N, W, 80), one stitch launch.  An
         utterance shorter than a window is one row of that batch with its own length (a padded mel is not a solo run: the kernels
         treat what lies past the row's end as the zero padding of every layer).  On a generator configuration whose
-        kernels take no row length (`short_rows()` False) it goes through `forward` on its own instead, one utterance per call."""
+        kernels take no row length (`short_rows()` False) it goes through `forward` on its own instead, one utterance per call.
+
+        `sample_rate` (Hz; None or `h.sampling_rate`: the route above, unchanged): the waveforms at that rate, (1, 1, ceil(256 T_i L / M)),
+        each resampled as an utterance of its own by one more launch on the flat buffer (tts_king_amd/resample.py)."""
         mels = list(mels)
-        flat, plan, spf = self.forward_ragged_flat(mels, frames_first)
-        return windows.split(flat, plan, spf, self.forward_short(mels, plan, frames_first))
+        flat, plan, spf = self.forward_ragged_flat(mels, frames_first, sample_rate=sample_rate)
+        return resample.split(flat, plan, spf, self.forward_short(mels, plan, frames_first, sample_rate=sample_rate))

@@ -1297,6 +1297,34 @@ def wav_stitch(y, plan, W, out=None, int16_scale=None):
     return out
 
 
+def resample(x_flat, segs, filt, out=None, int16_scale=None):
+    """x_flat: contiguous fp32 utterances back to back (what `wav_stitch` writes); segs: (rows, 4) int32 device table {src_off, src_len,
+    dst_off, dst_len} (tts_king_amd/resample.py); filt: a `resample.Filter` on the same device (table (P, L)) -> every utterance resampled by
+    filt.L / filt.M at its dst_off in `out`: fp32, or int16 = clamp(y * int16_scale, -32768, 32767) truncated toward zero.  Without
+    `out` the buffer is sized to the end of the last segment, which costs a host read of the table: a capturable call passes `out`.
+    Samples of `out` that belong to no segment are not written."""
+    _dev(x_flat, segs, filt.table)
+    if (x_flat.dtype != torch.float32 or not x_flat.is_contiguous() or segs.dtype != torch.int32 or not segs.is_contiguous() or segs.dim() != 2 or
+            segs.shape[1] != 4 or filt.table.dtype != torch.float32 or not filt.table.is_contiguous() or filt.table.numel() != filt.L * filt.P):
+        raise L.TtskError("resample: needs a contiguous fp32 source, a contiguous (rows, 4) int32 segment table and a (P, L) fp32 filter table")
+    i16 = int16_scale is not None
+    dt = torch.int16 if i16 else torch.float32
+    if out is None:
+        s = segs.cpu()
+        out = torch.empty(int((s[:, 2].long() + s[:, 3].long()).max()) if s.shape[0] else 0, dtype=dt, device=x_flat.device)
+    elif out.dtype != dt or not out.is_contiguous() or not out.is_cuda:
+        raise L.TtskError("resample: `out` must be a contiguous %s device tensor" % dt)
+    _count("resample")
+    check(L.load().ttsk_resample(_ptr(x_flat), x_flat.numel(), _ptr(segs), segs.shape[0], _ptr(filt.table), filt.L, filt.M, filt.P, filt.C,
+                                 _ptr(out), out.numel(), int(i16), float(int16_scale or 0.0), _stream()), "ttsk_resample")
+    return out
+
+
+def resample_tile(filt):
+    """Samples of the destination one workgroup of `resample` serves for this filter (host only; segments need no alignment to it)."""
+    return int(L.load().ttsk_resample_tile(filt.L, filt.M, filt.P))
+
+
 def _row_args(what, rows, Bn):
     """(pointer, element stride, samples per frame) of a per-row length for the *_rowlen entry points (include/ttsk.h): `rows` =
     (frames, spf) with `frames` a 1-D int32 device tensor or view of Bn entries (column `windows.VALID` of a plan table, or a compact

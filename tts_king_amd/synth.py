@@ -14,6 +14,7 @@ import numpy as np
 
 from . import batching
 from . import ops
+from . import resample
 from . import windows
 
 
@@ -191,28 +192,46 @@ class GraphedSynthesizer:
             hand_out(i, r, post[r], mel_pre[r], max(totals[r], 0))
 
     @torch.no_grad()
-    def wav(self, mel_bct):
-        """mel (B, 80, T) fp32 on the device -> waveform (B, 1, 256 T) fp32."""
+    def wav(self, mel_bct, sample_rate=None, int16_scale=None):
+        """mel (B, 80, T) fp32 on the device -> waveform (B, 1, 256 T) fp32.  `sample_rate` (other than the vocoder's): every row
+        resampled as an utterance of its own, (B, 1, ceil(256 T L / M)), by one more launch in the graph, whose key the rate joins;
+        `int16_scale` (with such a rate only): that launch writes saturated int16."""
         Bn, _, T = mel_bct.shape
-        return self._get(self._voc, ("voc", Bn, T), lambda x: self.vocoder(x), (mel_bct.contiguous(),)).clone()
+        gen = self.vocoder
+        if gen.resampler(sample_rate) is None:
+            if int16_scale is not None:
+                raise ValueError("wav: int16_scale belongs to the resampling launch; at the vocoder's own rate convert with ops.to_int16")
+            return self._get(self._voc, ("voc", Bn, T), lambda x: gen(x), (mel_bct.contiguous(),)).clone()
+        sc = None if int16_scale is None else float(int16_scale)
+        key = ("voc", Bn, T, int(sample_rate), sc)
+        g = self._voc.get(key)
+        # the B-row segment table is a constant of the key: uploaded until the graph exists, the graph's own copy afterwards
+        segs = g.static[1] if g is not None else gen.row_segments(Bn, T * gen.samples_per_frame(), sample_rate)
+        fn = lambda x, sgt: gen.resample_rows(gen(x), sample_rate, sc, sgt)
+        return self._get(self._voc, key, fn, (mel_bct.contiguous(), segs)).clone()
 
     @torch.no_grad()
-    def wav_ragged(self, mels, frames_first=False, int16_scale=None):
+    def wav_ragged(self, mels, frames_first=False, int16_scale=None, sample_rate=None):
         """mels: a list of (80, T_i) mels of any lengths (`frames_first`: (T_i, 80)) -> a list of (1, 1, 256 T_i) waveforms on the device,
         fp32, or int16 = truncation of waveform * `int16_scale`.  The utterances of at least `windows.W` frames run as N fixed-size
         windows (tts_king_amd/windows.py) on ONE graph per ladder value of N: gather -> generator -> stitch, with the mel staging buffer
         and the plan table as its static inputs, so calls with different lengths and the same N replay the same graph.  An utterance
         shorter than a window is a row of the same batch (its length is one more number in the table; such calls share one graph per
-        N of their own); only on a generator without `short_rows()` does it go through `wav`, alone."""
+        N of their own); only on a generator without `short_rows()` does it go through `wav`, alone.
+        `sample_rate` (other than the vocoder's): waveforms of ceil(256 T_i L / M) samples; the resampling launch and its segment table
+        join the graph, still one per (N, rate) whatever the lengths; int16 is then saturated."""
         mels = list(mels)
-        flat, plan, spf = self.wav_ragged_flat(mels, frames_first, int16_scale)
+        flat, plan, spf = self.wav_ragged_flat(mels, frames_first, int16_scale, sample_rate)
         flat = None if flat is None else flat.clone()          # the graph's private output buffer: hand out a copy, as `wav` does
-        return windows.split(flat, plan, spf, self.vocoder.forward_short(mels, plan, frames_first, int16_scale, forward=self.wav))
+        short = self.vocoder.forward_short(mels, plan, frames_first, int16_scale, forward=self.wav, sample_rate=sample_rate)
+        return resample.split(flat, plan, spf, short)
 
     @torch.no_grad()
-    def wav_ragged_flat(self, mels, frames_first=False, int16_scale=None):
+    def wav_ragged_flat(self, mels, frames_first=False, int16_scale=None, sample_rate=None):
         """The windowed part of `wav_ragged`: (flat buffer of N * W * 256 samples or None when no utterance fills a window, plan, samples
-        per frame).  After a replay the buffer is the graph's own: valid until the next call with the same N."""
+        per frame).  After a replay the buffer is the graph's own: valid until the next call with the same N.
+        `sample_rate` (other than the vocoder's): the buffer holds ceil(N W 256 L / M) + N samples, the resampled utterances where
+        `plan.segs` puts them (`resample.split`); the segment table is the graph's third static input, refreshed like the plan table."""
         gen = self.vocoder
         mels, lens = gen.ragged_mels(mels, frames_first)
         plan = gen.plan(lens)
@@ -223,20 +242,31 @@ class GraphedSynthesizer:
         rl = plan.has_short_rows
         key = ("rag", plan.N, plan.W, bool(frames_first), None if int16_scale is None else float(int16_scale)) + (("rows",) if rl else ())
         table = torch.from_numpy(plan.table)
+        filt = gen.resampler(sample_rate)
+        if filt is not None:
+            key += ("rate", int(sample_rate))
+            sg = gen.plan_resample(plan, filt)
+            segs = torch.from_numpy(sg.table)
         g = self._rag.get(key)
         if g is None:
             stage = gen.stage_mels(mels, plan, frames_first)
             table = table.to(stage.device)
-            fn = lambda st, tb: gen.forward_windows(st, tb, frames_first, int16_scale, rl)
+            if filt is None:
+                fn, inputs = (lambda st, tb: gen.forward_windows(st, tb, frames_first, int16_scale, rl)), [stage, table]
+            else:
+                fn = lambda st, tb, sgt: gen.forward_windows(st, tb, frames_first, int16_scale, rl, sample_rate, sgt)
+                inputs = [stage, table, segs.to(stage.device)]
             if key not in self._seen:                      # first sight: eager (lazy allocations, weight packing)
                 self._seen.add(key)
-                return fn(stage, table), plan, spf
+                return fn(*inputs), plan, spf
             if len(self._rag) >= self.max_graphs:
                 self._rag.pop(next(iter(self._rag)))
             torch.cuda.synchronize()
-            g = self._rag[key] = _Graph(fn, [stage, table])
+            g = self._rag[key] = _Graph(fn, inputs)
         else:
             gen.stage_mels(mels, plan, frames_first, g.static[0])
             g.static[1].copy_(table, non_blocking=True)
+            if filt is not None:
+                g.static[2].copy_(segs, non_blocking=True)
         g.graph.replay()
         return g.out, plan, spf

@@ -79,12 +79,14 @@ class Plan:
                   short = the others
        offsets    planned utterance -> its first frame in the staging buffer and in the flat output (both hold the planned utterances
                   back to back); frames = their total, never more than N * W
-       has_short_rows  some row holds an utterance shorter than the window (0 < column VALID < W): the generator needs the row lengths"""
+       has_short_rows  some row holds an utterance shorter than the window (0 < column VALID < W): the generator needs the row lengths
+       segs       None, or, set by a route that resampled the flat output, its layout (`resample.Segments`; `resample.split` reads it)"""
 
     def __init__(self, table, n_windows, planned, short, offsets, frames, lens, Wn, H):
         self.table, self.n_windows, self.planned, self.short = table, n_windows, planned, short
         self.offsets, self.frames, self.lens, self.W, self.H = offsets, frames, lens, Wn, H
         self.N = int(table.shape[0])
+        self.segs = None
         self.has_short_rows = bool(self.N) and bool(((table[:, VALID] > 0) & (table[:, VALID] < Wn)).any())
 
 
