@@ -906,6 +906,30 @@ int ttsk_mel_from_spec(const float* spec, int ld, const float* basis_vals, const
                        const int32_t* basis_off, int nnz, float* mel, float* energy, int B, int rows, int T, int nbins,
                        int n_mels, float eps, float clip, void* stream);
 
+/* ------------------------------------------------------------------------------- pitch and phoneme-level prosody
+ * Data preparation for the FS2 trainer.  reference: fs_two/preprocessor/preprocessor.py:206-266.
+ * pitch_yin: F0 per frame by YIN (de Cheveigne & Kawahara 2002, steps 1-5).  NOT DIO: the values differ from pyworld's.
+ *   wav (B, ld) fp32; lens int32[B] or null (every row has ld samples); samples at or past a row's len are never read.
+ *   f0 (B, T_max) fp32 with T_max = 1 + ld / hop; row b has T = 1 + len / hop frames, the others are written as 0.
+ *   Frame t, S = W + tau_max: s0 = clamp(t * hop - S / 2, 0, max(len - S, 0)), x[j] = wav[s0 + j] (0 from len on), j < S;
+ *   d(tau) = sum_{j < W} (x[j] - x[j + tau])^2 in fp32, direct form, in an order that depends on (W, tau_max) only;
+ *   d'(tau) = d(tau) * tau / sum_{k = 1 .. tau} d(k), 1 where that sum is 0; the first tau in [tau_min, tau_max) with
+ *   d'(tau) < thr, walked on while tau + 1 < tau_max and d'(tau + 1) < d'(tau); none: f0 = 0 (unvoiced);
+ *   off = 0.5 (a - c) / (a - 2 b + c) over d'(tau - 1 .. tau + 1), 0 when the denominator is 0 or |off| > 1; f0 = sr / (tau + off).
+ *   Needs W % 4 == 0, 2 <= tau_min, tau_min + 1 < tau_max <= 1023, W + tau_max <= 8192.
+ * phoneme_prosody: one row per utterance: f0, energy (B, ldT) fp32, dur (B, ldL) int32, T[B] frames and Lp[B] phonemes.
+ *   n = sum dur.  status (int32): 2 when n > T (or a duration is negative), 1 when at most one of the first n frames of f0 is
+ *   non-zero, 3 when the standard deviation below is 0, else 0; a row with a non-zero status writes zeros.
+ *   Unvoiced (zero) frames are interpolated linearly between their voiced neighbours; before the first voiced frame its value is
+ *   held, after the last likewise.  pitch[i] = (log(mean of f0 over phoneme i's frames) - pitch_mean) / pitch_std with the mean
+ *   and population standard deviation of those logs over the utterance; energy_ph[i] = mean of energy over the frames.  A phoneme
+ *   with dur = 0 stores 0 for both and is left out of the statistics (the reference takes log 0 there).  Entries from Lp[b] to
+ *   ldL are written as 0.  ldT <= 8192, ldL <= 1024. */
+int ttsk_pitch_yin(const float* wav, const int32_t* lens, int B, int ld, int hop, int W, int tau_min, int tau_max, float sr, float thr,
+                   float* f0, int T_max, void* stream);
+int ttsk_phoneme_prosody(const float* f0, const float* energy, int ldT, const int32_t* dur, int ldL, const int32_t* T, const int32_t* Lp,
+                         int B, float* pitch, float* energy_ph, float* pitch_mean, float* pitch_std, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

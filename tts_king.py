@@ -72,6 +72,38 @@ class TTSKing:
             wav = self.vocoder(mels.transpose(1, 2), sample_rate=sample_rate)
         return (wav, prosody) if return_prosody else wav
 
+    def extract_prosody(self, wav, durations, sample_rate=22050):
+        """A recording's per-phoneme prosody in the form `speak` / `generate_mel` take: {"durations", "pitch", "energy"}, one
+        value per phoneme.  `wav`: 1-D samples (numpy or torch, any scale) at `sample_rate` Hz covering exactly the aligned speech;
+        `durations`: frames per phoneme (e.g. `textgrid.get_alignment`).  The recording goes through the data-preparation stages
+        (tts_king_amd/preprocess.py: resample to the model's rate, peak-normalise, energy from `TacotronSTFT`, F0 from
+        `PitchExtractor` (YIN), the phoneme-level reduction on the device), then `(x - mean) / std` with the pitch and energy mean
+        and std of the model's stats.json: exactly what the normalisation pass writes into the training targets.  Those are the
+        units of `pitch=` and `energy=` (a set value is used as is, `scaled[l] = value[l]`, and bucketed
+        against the stats.json range), so `speak(text, **tts.extract_prosody(wav, durations))` reproduces the recording's prosody.
+        Raises ValueError when the recording has no usable pitch (fewer than two voiced frames, constant pitch) or fewer frames
+        than the durations ask for."""
+        import json
+        import os
+        from tts_king_amd import preprocess
+        if not hasattr(self, "_features"):
+            self._features = preprocess.Features(self.cfg.preprocess_config, self.cfg.gpu)
+            with open(os.path.join(self.cfg.preprocess_config.path.preprocessed_path, "stats.json")) as f:
+                self._stats = json.load(f)
+        if torch.is_tensor(wav):
+            wav = wav.detach().cpu().numpy()
+        wav = np.asarray(wav).reshape(-1)
+        durations = np.asarray(durations).reshape(-1).astype(np.int64)
+        y = self._features.prepare(wav, int(sample_rate), "extract_prosody")
+        _, energy, f0 = self._features.frame_level(y)
+        status, pitch, energy_ph, _, _ = self._features.phoneme_level(f0, energy, durations.tolist())
+        if status:
+            raise ValueError("extract_prosody: %s (%d samples, %d frames of durations)" % (preprocess.STATUS_TEXT[status], len(y), int(durations.sum())))
+        pm, ps = self._stats["pitch"][2:4]
+        em, es = self._stats["energy"][2:4]
+        return {"durations": durations, "pitch": ((pitch.astype(np.float64) - pm) / ps).astype(np.float32),
+                "energy": ((energy_ph.astype(np.float64) - em) / es).astype(np.float32)}
+
     def text_preprocess(self, text):
         """reference: tts_king.py:59-60 -> input_process.preprocess_rus (needs russian_g2p).  A string that already is in
         the phoneme notation of the reference's frontend, "{R A B O0 T ...}", is converted directly."""

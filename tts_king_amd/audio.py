@@ -127,3 +127,23 @@ class TacotronSTFT:
         if float(y.min()) < -1.0 or float(y.max()) > 1.0:      # stft.py:185-186
             raise AssertionError("TacotronSTFT.mel_spectrogram: input outside [-1, 1]")
         return self._ex(y)
+
+
+class PitchExtractor:
+    """F0 per frame on the device by YIN (`ops.pitch_yin`): frame t is centred on sample t * hop_length, the
+    frame grid of `TacotronSTFT` and of DIO at that frame period.  The method is not DIO: values differ from pyworld's."""
+
+    def __init__(self, sampling_rate, hop_length, window=1024, f0_floor=71.0, f0_ceil=800.0, threshold=0.15):
+        self.sampling_rate, self.hop_length, self.window = int(sampling_rate), int(hop_length), int(window)
+        self.f0_floor, self.f0_ceil, self.threshold = float(f0_floor), float(f0_ceil), float(threshold)
+        self.tau_min, self.tau_max = ops.yin_lags(self.sampling_rate, self.f0_floor, self.f0_ceil)
+
+    def frames(self, n_samples):
+        return 1 + int(n_samples) // self.hop_length
+
+    def __call__(self, y, lens=None):
+        """y (B, L) fp32 on the device, lens (B,) int32 on the device or None -> f0 (B, 1 + L // hop_length), 0 = unvoiced."""
+        if y.dim() != 2 or y.dtype != torch.float32:
+            raise ValueError("PitchExtractor: y must be (B, L) fp32")
+        return ops.pitch_yin(y.contiguous(), lens, sr=self.sampling_rate, hop=self.hop_length, window=self.window,
+                             f0_floor=self.f0_floor, f0_ceil=self.f0_ceil, threshold=self.threshold)

@@ -2140,3 +2140,55 @@ def mel_from_spec(spec, Bsz, rows, T, nbins, vals, start, off, nnz, n_mels, eps,
     check(L.load().ttsk_mel_from_spec(_ptr(spec), spec.stride(0), _ptr(vals), _ptr(start), _ptr(off), nnz, _ptr(mel),
                                       _ptr(energy), Bsz, rows, T, nbins, n_mels, eps, clip, _stream()), "ttsk_mel_from_spec")
     return mel, energy
+
+
+def yin_lags(sr, f0_floor, f0_ceil):
+    """(tau_min, tau_max) = (ceil(sr / f0_ceil), floor(sr / f0_floor)): the lags `pitch_yin` scans."""
+    import math
+    if not (0.0 < f0_floor < f0_ceil):
+        raise L.TtskError("pitch_yin: needs 0 < f0_floor < f0_ceil, got %r, %r" % (f0_floor, f0_ceil))
+    return int(math.ceil(sr / f0_ceil)), int(math.floor(sr / f0_floor))
+
+
+def pitch_yin(wav, lens=None, *, sr=22050, hop=256, window=1024, f0_floor=71.0, f0_ceil=800.0, threshold=0.15):
+    """wav (B, ld) fp32, lens int32 (B,) device tensor or None -> f0 (B, 1 + ld // hop) fp32 by YIN (include/ttsk.h): row b has
+    1 + lens[b] // hop frames, later ones are 0; 0 = unvoiced.  Samples from lens[b] on are never read."""
+    _dev(wav, lens)
+    if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_contiguous():
+        raise L.TtskError("pitch_yin: wav must be a contiguous (B, ld) fp32 tensor")
+    Bsz, ld = wav.shape
+    if lens is not None and (lens.dtype != torch.int32 or lens.dim() != 1 or lens.numel() != Bsz or not lens.is_contiguous()):
+        raise L.TtskError("pitch_yin: lens must be a contiguous int32 tensor of %d entries" % Bsz)
+    tau_min, tau_max = yin_lags(sr, f0_floor, f0_ceil)
+    T_max = 1 + ld // int(hop) if hop > 0 else 0
+    f0 = torch.empty(Bsz, max(T_max, 0), dtype=torch.float32, device=wav.device)
+    _count("pitch_yin")
+    check(L.load().ttsk_pitch_yin(_ptr(wav), _ptr(lens), Bsz, ld, int(hop), int(window), tau_min, tau_max, float(sr), float(threshold),
+                                  _ptr(f0), T_max, _stream()), "ttsk_pitch_yin")
+    return f0
+
+
+def phoneme_prosody(f0, energy, dur, T, Lp):
+    """f0, energy (B, ldT) fp32; dur (B, ldL) int32; T, Lp (B,) int32: frames and phonemes per row -> (pitch (B, ldL), energy (B, ldL),
+    pitch_mean (B,), pitch_std (B,), status (B,) int32): the reference's phoneme-level reduction (include/ttsk.h).  status 0: good;
+    1: fewer than two voiced frames; 2: more duration than frames; 3: constant pitch.  A row with a status holds zeros."""
+    _dev(f0, energy, dur, T, Lp)
+    if (f0.dim() != 2 or f0.shape != energy.shape or f0.dtype != torch.float32 or energy.dtype != torch.float32 or not f0.is_contiguous() or
+            not energy.is_contiguous()):
+        raise L.TtskError("phoneme_prosody: f0 and energy must be contiguous (B, frames) fp32 tensors of one shape")
+    Bsz, ldT = f0.shape
+    if dur.dim() != 2 or dur.shape[0] != Bsz or dur.dtype != torch.int32 or not dur.is_contiguous():
+        raise L.TtskError("phoneme_prosody: dur must be a contiguous (B, phonemes) int32 tensor")
+    for name, v in (("T", T), ("Lp", Lp)):
+        if v.dtype != torch.int32 or v.dim() != 1 or v.numel() != Bsz or not v.is_contiguous():
+            raise L.TtskError("phoneme_prosody: %s must be a contiguous int32 tensor of %d entries" % (name, Bsz))
+    ldL = dur.shape[1]
+    pitch = torch.empty(Bsz, ldL, dtype=torch.float32, device=f0.device)
+    en = torch.empty(Bsz, ldL, dtype=torch.float32, device=f0.device)
+    pmean = torch.empty(Bsz, dtype=torch.float32, device=f0.device)
+    pstd = torch.empty(Bsz, dtype=torch.float32, device=f0.device)
+    status = torch.empty(Bsz, dtype=torch.int32, device=f0.device)
+    _count("phoneme_prosody")
+    check(L.load().ttsk_phoneme_prosody(_ptr(f0), _ptr(energy), ldT, _ptr(dur), ldL, _ptr(T), _ptr(Lp), Bsz, _ptr(pitch), _ptr(en),
+                                        _ptr(pmean), _ptr(pstd), _ptr(status), _stream()), "ttsk_phoneme_prosody")
+    return pitch, en, pmean, pstd, status
