@@ -744,13 +744,30 @@ int ttsk_fs2_loss_finalize(const float* partials_mel, const float* partials_var,
  * `state` is a device block of ttsk_optim_state_bytes() bytes:
  *   { int64 sched_step; int64 adam_t; uint64 rng_seed; uint64 rng_step; float lr, bc1, bc2, clip_coef, gnorm; ... }
  * (its address + 16 is the `rng` pointer handed to the dropout kernels).
- * optim_advance: ++sched_step, ++adam_t, recompute lr/bc1/bc2 on device (graph-replay safe).
- * clip_adam_step: ||g|| -> clip_coef = min(1, max_norm/(||g||+1e-6)) -> Adam on the flat buffers, writes the bf16
- * weight shadow and (optionally) zeroes the gradients.  n % 4 == 0.  partials: 1024 floats.
+ *
+ * ttsk_optim_step is the whole update as TWO launches over the flat buffers (n % 4 == 0; partials: 1024 floats), with no atomics and no
+ * host synchronisation: capturable.  What it covers is given by three device tables.
+ *   dev_ranges [n_ranges][3] (int64, ascending, disjoint): {start, end, sum of (end - start) / 4 over the ranges before this one}, every
+ *     start / end a multiple of 4; range_floats = their total.  One range {0, n, 0} is the whole model; several are the trainable
+ *     stretches when some parameter groups are frozen (speaker adaptation; torch: requires_grad_(False) on the rest — clip_grad_norm_
+ *     and Adam then skip them).  n_ranges == 0 is an error.
+ *   dev_items [n_items] (ttsk_adam_item, sorted by tile0): the window kernels' packed weights INSIDE the ranges — tap-major storage
+ *     (Cs, K, Ds) at element offset `off` of the flat buffers, Ds % 256 == 0 and Cs % 32 == 0, its plain pack (`pack`, the weight as
+ *     it is: Cout = Cs, Cin = Ds) and / or its transposed, tap-flipped pack (`pack_t`: Cout = Ds, Cin = Cs), either may be NULL; a
+ *     tile = 32 storage rows x 256 storage columns of one tap, item i owns tiles [tile0, tile0 + K * (Cs/32) * (Ds/256)).
+ *   dev_gaps [n_gaps][3] (int64): the layout of dev_ranges, for the parts of the ranges outside every item; gap_floats = their total,
+ *     and n_tiles * 8192 + gap_floats must equal range_floats.
+ *   n_items == 0 (then dev_items, dev_gaps NULL and n_tiles, n_gaps, gap_floats 0): launch 2 walks dev_ranges.
+ * Launch 1 sums g^2 over the ranges only (one fixed slot of `partials` per workgroup, a fixed order: equal inputs give equal bits) and
+ * advances the counters on device (graph-replay safe): ++sched_step, ++adam_t, lr / bc1 / bc2 recomputed, and ++rng_step when
+ * advance_rng (ttsk_rng_advance folded in).  Launch 2 derives ||g|| -> clip_coef = min(1, max_norm / (||g|| + 1e-6)) from those partials
+ * in every workgroup, applies Adam, writes the bf16 weight shadow and (zero_grad) zeroes the gradients — over the elements of the ranges
+ * only: elements outside them are neither read nor written in any of the five buffers, and the bytes moved are proportional to
+ * range_floats.  state.gnorm is the norm over the ranges.  The workgroup that updates a tile of an item also writes that tile's
+ * fragments of the item's packs, bit-identical to ttsk_win_conv_pack_table run on the shadow afterwards; packs of weights that are no
+ * item are not touched.
  */
 int ttsk_optim_state_bytes(void);
-int ttsk_optim_advance(void* state, float d_model, float warmup, const float* anneal_steps_host, int n_anneal,
-                       float anneal_rate, float beta1, float beta2, void* stream);
 int ttsk_rng_advance(void* state, void* stream);
 /* The keep-mask of dropout site `site` at the state `rng` points to ({uint64 seed, uint64 step}): keep[e] = 1 iff element e (row-major
  * index into the site's [rows][C] tensor) survives with drop probability p — the very function of (seed, step, site, e) every kernel of
@@ -758,16 +775,18 @@ int ttsk_rng_advance(void* state, void* stream);
  * block i: 100 + 2 i, 101 + 2 i; predictor g in (duration, pitch, energy): 200 + 2 g, 201 + 2 g; PostNet layer i: 300 + i
  * (reference sites: SubLayers.py:62,98; modules.py:283,295; Layers.py:137-140).  n % 4 == 0.  For parity tests. */
 int ttsk_dropout_keep_mask(const uint64_t* rng, uint32_t site, int64_t n, float p, uint8_t* keep, void* stream);
-int ttsk_clip_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t n,
-                        void* state, float* partials, float max_norm, float beta1, float beta2, float eps, int zero_grad,
-                        void* stream);
-int ttsk_grad_sumsq(const float* grads, int64_t n, float* partials, void* stream);
-/* optim_advance (+ rng_advance when advance_rng) + clip_adam_step as TWO launches: the first sums g^2 per block and advances
- * the counters, the second derives the clip coefficient from the partials in every workgroup and applies Adam.  Same
- * arithmetic, same state block as the three calls it replaces. */
+typedef struct ttsk_adam_item {
+  int64_t off;
+  void* pack;
+  void* pack_t;
+  int32_t Cs, K, Ds, tile0;
+} ttsk_adam_item;
 int ttsk_optim_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t n, void* state,
                     float* partials, float max_norm, float beta1, float beta2, float eps, int zero_grad, float d_model, float warmup,
-                    const float* anneal_steps_host, int n_anneal, float anneal_rate, int advance_rng, void* stream);
+                    const float* anneal_steps_host, int n_anneal, float anneal_rate, int advance_rng,
+                    const int64_t* dev_ranges, int n_ranges, int64_t range_floats,
+                    const ttsk_adam_item* dev_items, int n_items, int n_tiles, const int64_t* dev_gaps, int n_gaps,
+                    int64_t gap_floats, void* stream);
 
 /* Weight gradient of a Conv1d with K taps ("same" zero padding, dilation 1) as a kernel of its own (csrc/dwconv.hip):
  *   dw[co][tap][ci] (+)= sum_b sum_{t < len_b} dy[(b*S + t)*ldy + co] * x[(b*S + t + tap - K/2)*ldx + ci],   0 <= t + tap - K/2 < S
@@ -803,44 +822,6 @@ int ttsk_dwgemm_supported(int Cout, int Cin, int K);
 int64_t ttsk_dwgemm_workspace_floats(int Cout, int Cin, int K, int splits);
 /* max_wgs > 0: at most that many workgroups, each walking several tiles (one per CU on part of the chip, the rest left to a concurrent stream) */
 int ttsk_dwgemm_batch(const ttsk_dwgemm_item* items, int n /* <= 28 */, int max_wgs, void* stream);
-
-/* ttsk_optim_step whose Adam launch also writes the window kernels' weight packs (no ttsk_win_conv_pack_table launch after the step).
- * dev_items [n_items] (device memory, sorted by tile0): the packed weights — tap-major storage (Cs, K, Ds) at element offset `off` of the
- * flat buffers, Ds % 256 == 0 and Cs % 32 == 0, its plain pack (`pack`, the weight as it is: Cout = Cs, Cin = Ds) and / or its transposed,
- * tap-flipped pack (`pack_t`: Cout = Ds, Cin = Cs), either may be NULL; a tile = 32 storage rows x 256 storage columns of one tap,
- * item i owns tiles [tile0, tile0 + K * (Cs/32) * (Ds/256)).  dev_gaps [n_gaps][3] (device, int64): {start, end, sum of (end - start) / 4
- * over the gaps before this one} for the element ranges outside every item, each start / end a multiple of 4; gap_floats = their total.
- * n_tiles * 8192 + gap_floats must equal n.  Parameters, moments, shadow and packs come out bit-identical to ttsk_optim_step followed by
- * ttsk_win_conv_pack_table.  reference: train.py:47-54, fs_two/model/optimizer.py:35-53, torch.optim.Adam. */
-typedef struct ttsk_adam_item {
-  int64_t off;
-  void* pack;
-  void* pack_t;
-  int32_t Cs, K, Ds, tile0;
-} ttsk_adam_item;
-int ttsk_optim_step_packed(float* params, float* grads, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t n, void* state,
-                           float* partials, float max_norm, float beta1, float beta2, float eps, int zero_grad, float d_model, float warmup,
-                           const float* anneal_steps_host, int n_anneal, float anneal_rate, int advance_rng,
-                           const ttsk_adam_item* dev_items, int n_items, int n_tiles, const int64_t* dev_gaps, int n_gaps,
-                           int64_t gap_floats, void* stream);
-/* The optimizer step over a SUBSET of the flat buffers (speaker adaptation: some parameter groups trained, the rest frozen; torch:
- * requires_grad_(False) on the rest — clip_grad_norm_ and Adam then skip them).  Two launches, like ttsk_optim_step_packed.
- * dev_ranges [n_ranges][3] (device, int64, ascending, disjoint): {start, end, sum of (end - start) / 4 over the ranges before this one},
- * every start / end a multiple of 4; range_floats = their total.  Launch 1 sums g^2 over the ranges only (one fixed slot of `partials`
- * per workgroup, a fixed order: equal inputs give equal bits) and advances sched_step / adam_t / lr / the bias corrections (and the
- * dropout counter when advance_rng).  Launch 2 derives the clip coefficient from those partials in every workgroup, applies Adam, writes
- * the bf16 shadow and (zero_grad) zeroes the gradients — over the elements of the ranges only: elements outside them are neither read
- * nor written in any of the five buffers, and the bytes moved are proportional to range_floats.  state.gnorm is the norm over the ranges.
- * dev_items / dev_gaps as for ttsk_optim_step_packed, restricted to the ranges: the packed weights among the trainable ones (their
- * packs are rewritten by launch 2; packs of other weights are not touched) and the rest of the ranges as gaps,
- * n_tiles * 8192 + gap_floats == range_floats.  n_items == 0 (then dev_items, dev_gaps NULL and n_tiles, n_gaps, gap_floats 0): no
- * packed weight is trainable, launch 2 walks dev_ranges.  No atomics, no host synchronisation, capturable.  n_ranges == 0 is an error. */
-int ttsk_optim_step_ranges(float* params, float* grads, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t n, void* state,
-                           float* partials, float max_norm, float beta1, float beta2, float eps, int zero_grad, float d_model, float warmup,
-                           const float* anneal_steps_host, int n_anneal, float anneal_rate, int advance_rng,
-                           const int64_t* dev_ranges, int n_ranges, int64_t range_floats,
-                           const ttsk_adam_item* dev_items, int n_items, int n_tiles, const int64_t* dev_gaps, int n_gaps,
-                           int64_t gap_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------- CWT pitch branch
  * model_config.use_cwt: True.  reference: fs_two/model/modules.py:18-141 (get_pitch_embedding_cwt), :358-385 (CNNflat / CNNscalar),

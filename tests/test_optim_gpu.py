@@ -1,6 +1,7 @@
-"""GPU: the optimizer step's two forms — `ttsk_optim_step` + `ttsk_win_conv_pack_table` (round 2) and `ttsk_optim_step_packed`, whose
-Adam launch writes the window kernels' weight packs itself — leave bit-identical parameters, moments, bf16 shadow and packs; the
-global gradient norm the step records equals the norm of the flat gradient buffer.
+"""GPU: the optimizer step on the model, `ttsk_optim_step` with the model's tables.  Its Adam launch writing the window kernels'
+weight packs itself (the packed weights as items of the tables) and the same step without items + `ttsk_win_conv_pack_table` behind
+it leave bit-identical parameters, moments, bf16 shadow and packs; the global gradient norm the step records equals the norm of the
+flat gradient buffer.
 reference: train.py:47-54 (clip -> lr -> Adam -> zero_grad), torch.optim.Adam."""
 import copy
 
@@ -26,9 +27,10 @@ def test_packed_adam_equals_adam_then_pack(cfg, scale):
     res = []
     for packed in (False, True):
         m, opt = _model(cfg, 3)
-        assert m._adam_tables is not None, "the shipped configuration's packed weights all tile"
+        assert m._optim_tables["n_items"] > 0 and not m._repack_after_step, "the shipped configuration's packed weights all tile"
         if not packed:
-            m._adam_tables = None
+            m._build_optim_tables(adam_writes_packs=False)
+            assert m._optim_tables["n_items"] == 0 and m._repack_after_step
         g = torch.Generator(device=DEV).manual_seed(11)
         flat, grad, shadow = m.flat_buffers()
         for step in range(3):

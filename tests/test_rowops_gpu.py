@@ -308,35 +308,41 @@ def test_loss_and_grads():
 
 @pytest.mark.parametrize("start", [0, 3999, 300000])
 def test_clip_adam_lr(start):
+    """ttsk_optim_step with one range over the whole buffer and no items, against clip + Adam + the lr rule restated in fp64; the
+    scheduler / Adam counters (start 3999: across the warm-up boundary, 4000 -> 4001 at the second step), the lr of every step, the
+    dropout counter with and without `advance_rng`, and the zeroed gradients."""
     from oracle import fs2 as ofs2
     from tts_king_amd import ops
     n = 100000
     p, g = rnd(n, seed=37), rnd(n, seed=38, scale=0.05)
-    st = ops.optim_state(DEV, seed=1, sched_step=start)
-    dp, dg = p.to(DEV), g.to(DEV)
-    m, v = torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)
-    shadow = torch.empty(n, dtype=BF, device=DEV)
-    partials = torch.empty(1024, device=DEV)
+    tables = ops.optim_tables([(0, n)], [], DEV)
+    sched = (256, 4000, [300000, 400000, 500000], 0.7)
     b1, b2, eps = 0.95, 0.999, 1e-5
-    pr, mr, vr = p.double().clone(), torch.zeros(n).double(), torch.zeros(n).double()
-    for t in range(1, 4):
-        dg.copy_(g * t)
-        ops.optim_advance(st, 256, 4000, [300000, 400000, 500000], 0.7, b1, b2)
-        ops.clip_adam_step(dp, dg, m, v, shadow, st, partials, 1.0, b1, b2, eps, zero_grad=True)
-        gg = (g * t).double()
-        coef = min(1.0, 1.0 / (float(gg.norm()) + 1e-6))
-        gg = gg * coef
-        lr = ofs2.lr_at(start + t)
-        mr = b1 * mr + (1 - b1) * gg
-        vr = b2 * vr + (1 - b2) * gg * gg
-        pr = pr - lr / (1 - b1 ** t) * mr / (vr.sqrt() / math.sqrt(1 - b2 ** t) + eps)
-        assert float(dg.abs().max()) == 0.0
-    stc = st.cpu()
-    assert int(stc[0]) == start + 3 and int(stc[1]) == 3
-    lr_dev = stc[4:5].view(torch.float32)[0]
-    assert abs(float(lr_dev) - ofs2.lr_at(start + 3)) < 1e-9 + 1e-6 * ofs2.lr_at(start + 3)
-    np.testing.assert_allclose((dp.cpu().double() - p.double()).numpy(), (pr - p.double()).numpy(), rtol=2e-3, atol=6e-7)  # fp32 ulp of |p| <= 4
-    assert torch.equal(shadow.cpu(), dp.cpu().to(BF))
+    for advance_rng in (False, True):
+        st = ops.optim_state(DEV, seed=1, sched_step=start)
+        dp, dg = p.to(DEV), g.to(DEV)
+        m, v = torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)
+        shadow = torch.empty(n, dtype=BF, device=DEV)
+        partials = torch.empty(1024, device=DEV)
+        pr, mr, vr = p.double().clone(), torch.zeros(n).double(), torch.zeros(n).double()
+        for t in range(1, 4):
+            dg.copy_(g * t)
+            ops.optim_step(dp, dg, m, v, shadow, st, partials, 1.0, b1, b2, eps, *sched, tables, zero_grad=True, advance_rng=advance_rng)
+            gg = (g * t).double()
+            coef = min(1.0, 1.0 / (float(gg.norm()) + 1e-6))
+            gg = gg * coef
+            lr = ofs2.lr_at(start + t)
+            mr = b1 * mr + (1 - b1) * gg
+            vr = b2 * vr + (1 - b2) * gg * gg
+            pr = pr - lr / (1 - b1 ** t) * mr / (vr.sqrt() / math.sqrt(1 - b2 ** t) + eps)
+            assert float(dg.abs().max()) == 0.0
+            stc = st.cpu()
+            assert int(stc[0]) == start + t and int(stc[1]) == t
+            assert int(stc[2]) == 1 and int(stc[3]) == (t if advance_rng else 0)          # dropout seed kept, counter ticked on request only
+            lr_dev = stc[4:5].view(torch.float32)[0]
+            assert abs(float(lr_dev) - lr) < 1e-9 + 1e-6 * lr
+        np.testing.assert_allclose((dp.cpu().double() - p.double()).numpy(), (pr - p.double()).numpy(), rtol=2e-3, atol=6e-7)  # fp32 ulp of |p| <= 4
+        assert torch.equal(shadow.cpu(), dp.cpu().to(BF))
 
 
 def test_conversions():
@@ -410,31 +416,6 @@ def test_grouped_layernorm_equals_single_launches():
         dz1, _, p1, n1 = ops.layernorm_bwd(None, y[sl], m1, r1, gg, bb, lens, seg, relu_in=True, p_post=p, site_post=201 + 2 * g, rng=rng,
                                            dhead=dhead[sl], head_w=ww)
         assert n1 == nblk and torch.equal(dz1, dz[sl]) and torch.equal(p1, part[g])
-
-
-def test_optim_step_equals_separate_launches():
-    """ttsk_optim_step (2 launches) == rng_advance + optim_advance + clip_adam_step (5 launches), bit for bit."""
-    from tts_king_amd import ops
-    n = 40000
-    outs = []
-    for fused in (True, False):
-        p, g = rnd(n, seed=30).to(DEV), (rnd(n, seed=31) * 3).to(DEV)
-        m, v = torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)
-        sh = torch.zeros(n, dtype=BF, device=DEV)
-        st = ops.optim_state(DEV, seed=9, sched_step=3999)
-        part = torch.empty(1024, device=DEV)
-        for _ in range(2):
-            g.copy_((rnd(n, seed=31) * 3).to(DEV))
-            if fused:
-                ops.optim_step(p, g, m, v, sh, st, part, 1.0, 0.95, 0.999, 1e-5, 256, 4000, [300000, 400000, 500000], 0.7, advance_rng=True)
-            else:
-                ops.rng_advance(st)
-                ops.optim_advance(st, 256, 4000, [300000, 400000, 500000], 0.7, 0.95, 0.999)
-                ops.clip_adam_step(p, g, m, v, sh, st, part, 1.0, 0.95, 0.999, 1e-5)
-        outs.append((p.clone(), m.clone(), v.clone(), sh.clone(), st.clone(), g.clone()))
-    for a, w in zip(*outs):
-        assert torch.equal(a, w)
-    assert int(outs[0][4][0]) == 4001 and int(outs[0][4][3]) == 2 and float(outs[0][5].abs().max()) == 0.0
 
 
 # ------------------------------------------------------------------------------------------------ bias-gradient column sums

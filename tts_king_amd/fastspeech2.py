@@ -151,14 +151,15 @@ class FastSpeech2(nn.Module):
         # optimizer step).
         self.window_ffn = switches.get("TTSK_WINDOW_FFN") != "0"
         self._w1_packed = None
-        self._adam_tables = None
-        # Speaker adaptation (set_trainable): the units that are trained, None = all of them; the optimizer's tables over their
-        # ranges of the flat buffer (ops.optim_range_tables) and the pack table of the trainable 80-channel ends
+        self._adam_items = None         # the packed weights the optimizer's Adam launch can write itself (_build_packs)
+        # Speaker adaptation (set_trainable): the units that are trained, None = all of them
         self._trainable = None
         self._optimizer_built = False
-        self._range_tables = None
-        self._range_repack = False
-        self._odd_pack_table_sub = None
+        # the optimizer step's device tables over the trainable ranges of the flat buffer (ops.optim_tables; None on the CPU), and what
+        # refresh_after_step has to do behind it (_build_optim_tables)
+        self._optim_tables = None
+        self._repack_after_step = False
+        self._odd_after_step = None
         self.flash_attention = True     # attention without the S x S tensors when d_k = 128 (csrc/flash_attn.hip); False / other head sizes: scores GEMM + softmax + P V GEMM
         self.fused_ln = True            # fc / w_2 + dropout + residual + LayerNorm + PAD zeroing in one kernel when d = 256
         self._postnet_ends_win = True       # the PostNet's 80 -> 512 / 512 -> 80 convs and their input gradients on the window kernel too (round 5; property below)
@@ -223,6 +224,8 @@ class FastSpeech2(nn.Module):
             assert o[2] - o[1] == self._pred_stride and self._pred_stride % 8 == 0
         if self.window_ffn and self._shadow.is_cuda:
             self._build_packs()
+        else:
+            self._build_optim_tables()
 
     # ------------------------------------------------------------------ parameter plumbing
     def _register(self, en, device):
@@ -278,7 +281,7 @@ class FastSpeech2(nn.Module):
             raise NotImplementedError("train_only together with use_cwt: True is not supported")
         self._trainable = tu
         self._apply_trainable_flags()
-        self._build_range_tables()
+        self._build_optim_tables()
 
     @property
     def trainable_units(self):
@@ -309,33 +312,39 @@ class FastSpeech2(nn.Module):
                 par.requires_grad_(on)
                 par.grad = self._view(self._flat_grad, en) if on else None
 
-    def _build_range_tables(self):
-        """The device tables of the subset optimizer step (host -> device copies: at construction, set_trainable and `_apply`, never
-        inside a step).  The trainable packed weights keep the Adam launch's tile walk (their packs are written there, the frozen
-        weights' packs are left alone); the trainable 80-channel ends get a pack table of their own."""
-        self._range_tables, self._range_repack, self._odd_pack_table_sub = None, False, None
-        if self._trainable is None or not self._flat.is_cuda:
+    def _build_optim_tables(self, adam_writes_packs=True):
+        """The optimizer step's device tables (host -> device copies: at construction, set_trainable, `_apply` and a change of
+        `postnet_ends_win`, never inside a step): the trainable ranges of the flat buffer — everything trained: one range — and the
+        trainable packed weights as the Adam launch's items (their packs are written there, the frozen weights' packs are left alone).
+        The trainable 80-channel ends, which that launch cannot write, get a pack table of their own.  When the items cannot be used —
+        a packed weight that does not tile, one with two packs of a kind, or `adam_writes_packs` False (tests: the same step with
+        the pack launch behind it) — Adam walks the plain ranges and every pack is rewritten from the shadow afterwards."""
+        self._optim_tables, self._repack_after_step, self._odd_after_step = None, False, None
+        if not self._flat.is_cuda:
             return
-        dev, items = self._flat.device, []
+        dev, ranges, tables = self._flat.device, self.trainable_ranges(), None
         packed = self.window_ffn and bool(self._w1_packed)
-        if packed and self._adam_tables is not None:
-            items = [tuple(v) for k, v in self._adam_items.items() if self._unit_on(P.unit_of(k))]
-        tables = ops.optim_range_tables(self.trainable_ranges(), items, dev)
-        if tables is None or (packed and self._adam_tables is None):
-            # a packed weight that does not tile: Adam over the plain ranges, every pack rewritten from the shadow behind it
-            tables, self._range_repack = ops.optim_range_tables(self.trainable_ranges(), [], dev), True
-        self._range_tables = tables
-        if packed and not self._range_repack:
-            odd = [(W, pk, tr) for key, W, pk, tr in getattr(self, "_odd_items", []) if self._unit_on(P.unit_of(key))]
-            if odd:
-                self._odd_pack_table_sub = ops.win_conv_pack_table(odd, dev)
+        if packed and adam_writes_packs and self._adam_items is not None:
+            tables = ops.optim_tables(ranges, [tuple(v) for k, v in self._adam_items.items() if self._unit_on(P.unit_of(k))], dev)
+        if tables is None:
+            tables, self._repack_after_step = ops.optim_tables(ranges, [], dev), packed
+        self._optim_tables = tables
+        if packed and not self._repack_after_step:
+            odd = [(W, pk, tr) for key, W, pk, tr in self._odd_items if self._unit_on(P.unit_of(key))]
+            if len(odd) == len(self._odd_items):
+                self._odd_after_step = self._odd_pack_table
+            elif odd:
+                self._odd_after_step = ops.win_conv_pack_table(odd, dev)
 
-    def refresh_trainable_packs(self):
-        """Behind the subset optimizer step: the packs that step did not write itself — of trainable weights only."""
-        if self._range_repack:
+    def refresh_after_step(self):
+        """Behind the optimizer step, which rewrote the bf16 shadow: the window kernels' packs that step did not write itself — every
+        pack when its Adam launch had no items, else the trainable 80-channel ends in one small launch."""
+        if not self.window_ffn:
+            return
+        if self._repack_after_step:
             self.refresh_packed()
-        elif self._odd_pack_table_sub is not None:
-            ops.win_conv_pack_run(*self._odd_pack_table_sub)
+        elif self._odd_after_step is not None:
+            ops.win_conv_pack_run(*self._odd_after_step)
 
     def mark_dirty(self):
         """Call after writing the fp32 masters through anything torch cannot see (raw pointers): the next forward
@@ -355,7 +364,7 @@ class FastSpeech2(nn.Module):
         self._flat, self._flat_grad = flat, grad
         self._shadow = shadow.to(bf16) if shadow.dtype != bf16 else shadow
         self._w1_packed = None
-        self._adam_tables = None
+        self._adam_items = None
         self._shadow_version = -1
         self._rng_state = None
         self._dw_side = self._fin_side = self._pred_stream = None
@@ -363,7 +372,7 @@ class FastSpeech2(nn.Module):
         if self.window_ffn and self._shadow.is_cuda:
             self._build_packs()
         else:
-            self._build_range_tables()
+            self._build_optim_tables()
         return self
 
     def get(self, key):
@@ -456,7 +465,7 @@ class FastSpeech2(nn.Module):
         if on != self._postnet_ends_win:
             self._postnet_ends_win = on
             self._w1_packed = None
-            self._adam_tables = None
+            self._adam_items = None
             if self.window_ffn and self._shadow.is_cuda:
                 self._build_packs()
 
@@ -470,11 +479,7 @@ class FastSpeech2(nn.Module):
             self._build_packs()
         if self._pack_table is not None:
             ops.win_conv_pack_run(*self._pack_table)
-        self.refresh_odd_packs()
-
-    def refresh_odd_packs(self):
-        """The packs the optimizer's Adam launch does not write itself (the PostNet's 80-channel ends), from the bf16 shadow: one small launch."""
-        if self.window_ffn and getattr(self, "_odd_pack_table", None) is not None:
+        if self._odd_pack_table is not None:       # the PostNet's 80-channel ends: one small launch
             ops.win_conv_pack_run(*self._odd_pack_table)
 
     def _build_packs(self):
@@ -495,7 +500,7 @@ class FastSpeech2(nn.Module):
                [("pn", "postnet.convolutions.%d.0.conv.weight" % i, None, False) for i in range(1, 4)] + \
                [("pnT", "postnet.convolutions.%d.0.conv.weight" % i, None, True) for i in range(1, 4)]
         # the PostNet's ends (80 -> 512 and 512 -> 80 channels, round 5): packs Adam's tile walk cannot write (80 is neither a multiple of
-        # 32 storage rows nor of 256 storage columns); one small launch of their own behind the optimizer step (refresh_odd_packs)
+        # 32 storage rows nor of 256 storage columns); one small launch of their own behind the optimizer step (refresh_after_step)
         odd = [(t, "postnet.convolutions.%d.0.conv.weight" % i, None, tr) for t, i, tr in
                (("pn", 0, False), ("pnT", 0, True), ("pn", 4, False), ("pnT", 4, True))] if self.postnet_ends_win else []
         if self.postnet_ends_win:            # ... and mel_linear (256 -> 80) both ways
@@ -539,10 +544,10 @@ class FastSpeech2(nn.Module):
             self._odd_items.append((key, W, pk, tr))
         if odd_items:
             self._odd_pack_table = ops.win_conv_pack_table(odd_items, self._shadow.device)
-        # ... and the tables with which the optimizer's Adam launch writes these packs itself (ttsk_optim_step_packed): per weight its
-        # flat offset, storage shape and its plain / transposed packs.  A weight with more than one pack of a kind (w_1's transposed
-        # pack exists once) or one that does not tile leaves `_adam_tables` None: the optimizer then calls refresh_packed as before.
-        self._adam_tables = None
+        # ... and the items with which the optimizer's Adam launch writes these packs itself (ttsk_optim_step): per weight its flat
+        # offset, storage shape and its plain / transposed packs.  A weight with more than one pack of a kind (w_1's transposed pack
+        # exists once) leaves `_adam_items` None: every pack is then rewritten behind the step (_build_optim_tables).
+        self._adam_items = None
         if self._pack_items:
             by_key, ok = {}, True
             for key, fr, out, tr in self._pack_items:
@@ -552,9 +557,8 @@ class FastSpeech2(nn.Module):
                     ok = False
                 ent[3 if tr else 2] = out
             if ok:
-                self._adam_tables = ops.adam_pack_tables([tuple(v) for v in by_key.values()], self._n_flat, self._shadow.device)
                 self._adam_items = by_key
-        self._build_range_tables()
+        self._build_optim_tables()
 
     def _pack(self, tag, key):
         """The window kernel's pack `(tag, key)` of `_build_packs`, or None: no such pack, or no packs at all (TTSK_WINDOW_FFN=0)."""

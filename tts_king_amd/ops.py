@@ -1684,82 +1684,16 @@ def dropout_keep_mask(state, site, n, p):
     return keep
 
 
-def optim_advance(state, d_model, warmup, anneal_steps, anneal_rate, beta1, beta2):
-    arr = (C.c_float * 4)(*([float(a) for a in anneal_steps] + [0.0] * (4 - len(anneal_steps))))
-    check(L.load().ttsk_optim_advance(_ptr(state), float(d_model), float(warmup), C.cast(arr, C.c_void_p), len(anneal_steps),
-                                      anneal_rate, beta1, beta2, _stream()), "ttsk_optim_advance")
-
-
 def rng_advance(state):
     check(L.load().ttsk_rng_advance(_ptr(state), _stream()), "ttsk_rng_advance")
 
 
-def clip_adam_step(params, grads, m, v, shadow, state, partials, max_norm, beta1, beta2, eps, zero_grad=True):
-    _dev(params, grads, m, v, shadow, state, partials)
-    check(L.load().ttsk_clip_adam_step(_ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(shadow), params.numel(), _ptr(state),
-                                       _ptr(partials), max_norm, beta1, beta2, eps, int(zero_grad), _stream()),
-          "ttsk_clip_adam_step")
-
-
-@_family("clip_adam", lambda *a, **kw: 0.0)
-def optim_step(params, grads, m, v, shadow, state, partials, max_norm, beta1, beta2, eps, d_model, warmup, anneal_steps, anneal_rate,
-               zero_grad=True, advance_rng=False):
-    """optim_advance (+ rng_advance) + clip_adam_step in two launches (ttsk_optim_step)."""
-    _dev(params, grads, m, v, shadow, state, partials)
-    arr = (C.c_float * 4)(*([float(a) for a in anneal_steps] + [0.0] * (4 - len(anneal_steps))))
-    check(L.load().ttsk_optim_step(_ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(shadow), params.numel(), _ptr(state), _ptr(partials),
-                                   max_norm, beta1, beta2, eps, int(zero_grad), float(d_model), float(warmup), C.cast(arr, C.c_void_p),
-                                   len(anneal_steps), anneal_rate, int(advance_rng), _stream()), "ttsk_optim_step")
-
-
-def adam_pack_tables(items, n_flat, device):
-    """Device tables for optim_step_packed.  items: [(flat offset, (Cs, K, Ds), plain pack tensor or None, transposed pack tensor or
-    None)] — the window kernels' packed weights; everything else of [0, n_flat) becomes the gap ranges.  Returns a dict of the tensors /
-    counts the call needs (the tensors must stay alive and the packs where they are), or None when a weight does not tile
-    (Cs % 32, Ds % 256) or the ranges overlap."""
-    items = sorted(items, key=lambda it: it[0])
-    arr = (L.AdamItem * len(items))()
-    tile0, pos, gaps = 0, 0, []
-    for i, (off, (Cs, K, Ds), pk, pkt) in enumerate(items):
-        if Cs % 32 or Ds % 256 or off % 4 or off < pos:
-            return None
-        if off > pos:
-            gaps.append((pos, off))
-        arr[i].off, arr[i].pack, arr[i].pack_t = off, _ptr(pk), _ptr(pkt)
-        arr[i].Cs, arr[i].K, arr[i].Ds, arr[i].tile0 = Cs, K, Ds, tile0
-        tile0 += K * (Cs // 32) * (Ds // 256)
-        pos = off + Cs * K * Ds
-    if pos < n_flat:
-        gaps.append((pos, n_flat))
-    g, acc = [], 0
-    for a, b in gaps:
-        if (b - a) % 4:
-            return None
-        g += [a, b, acc]
-        acc += (b - a) // 4
-    dev_items = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64).clone().to(device)
-    dev_gaps = torch.tensor(g if g else [0, 0, 0], dtype=torch.int64).to(device)
-    return {"items": dev_items, "n_items": len(items), "n_tiles": tile0, "gaps": dev_gaps, "n_gaps": len(gaps), "gap_floats": acc * 4}
-
-
-@_family("clip_adam", lambda *a, **kw: 0.0)
-def optim_step_packed(params, grads, m, v, shadow, state, partials, max_norm, beta1, beta2, eps, d_model, warmup, anneal_steps, anneal_rate,
-                      tables, zero_grad=True, advance_rng=False):
-    """optim_step whose Adam launch also writes the window kernels' weight packs (ttsk_optim_step_packed): no pack launch afterwards."""
-    _dev(params, grads, m, v, shadow, state, partials, tables["items"], tables["gaps"])
-    arr = (C.c_float * 4)(*([float(a) for a in anneal_steps] + [0.0] * (4 - len(anneal_steps))))
-    check(L.load().ttsk_optim_step_packed(_ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(shadow), params.numel(), _ptr(state), _ptr(partials),
-                                          max_norm, beta1, beta2, eps, int(zero_grad), float(d_model), float(warmup), C.cast(arr, C.c_void_p),
-                                          len(anneal_steps), anneal_rate, int(advance_rng), _ptr(tables["items"]), tables["n_items"],
-                                          tables["n_tiles"], _ptr(tables["gaps"]), tables["n_gaps"], tables["gap_floats"], _stream()),
-          "ttsk_optim_step_packed")
-
-
-def optim_range_tables(ranges, items, device):
-    """Device tables for optim_step_ranges.  ranges: sorted, disjoint [start, end) element ranges of the flat buffers (multiples of 4):
-    what the step may touch.  items: as for adam_pack_tables, the packed weights INSIDE the ranges whose packs the Adam launch is to
-    write (may be empty).  Returns a dict (the tensors must stay alive and the packs where they are), or None when an item does not
-    tile, the ranges overlap or an item sticks out of them."""
+def optim_tables(ranges, items, device):
+    """Device tables for optim_step.  ranges: sorted, disjoint [start, end) element ranges of the flat buffers (multiples of 4): what
+    the step may touch; [(0, n)] is everything.  items: [(flat offset, (Cs, K, Ds), plain pack tensor or None, transposed pack tensor
+    or None)] — the window kernels' packed weights INSIDE the ranges whose packs the Adam launch is to write (may be empty); the rest
+    of the ranges becomes the gap ranges.  Returns a dict of the tensors / counts the call needs (the tensors must stay alive and the
+    packs where they are), or None when an item does not tile (Cs % 32, Ds % 256), the ranges overlap or an item sticks out of them."""
     ranges = sorted((int(a), int(b)) for a, b in ranges)
     r, acc, pos = [], 0, 0
     for a, b in ranges:
@@ -1810,21 +1744,21 @@ def optim_range_tables(ranges, items, device):
 
 
 @_family("clip_adam", lambda *a, **kw: 0.0)
-def optim_step_ranges(params, grads, m, v, shadow, state, partials, max_norm, beta1, beta2, eps, d_model, warmup, anneal_steps, anneal_rate,
-                      tables, zero_grad=True, advance_rng=False):
-    """The optimizer step over the element ranges of `tables` (optim_range_tables) only: norm, clip, Adam, bf16 shadow and the packs of
-    the tables' items, in two launches (ttsk_optim_step_ranges).  Elements outside the ranges are neither read nor written."""
+def optim_step(params, grads, m, v, shadow, state, partials, max_norm, beta1, beta2, eps, d_model, warmup, anneal_steps, anneal_rate,
+               tables, zero_grad=True, advance_rng=False):
+    """The optimizer step over the element ranges of `tables` (optim_tables) only: counters / lr advanced, norm, clip, Adam, bf16 shadow
+    and the packs of the tables' items, in two launches (ttsk_optim_step).  Elements outside the ranges are neither read nor written."""
     _dev(params, grads, m, v, shadow, state, partials, tables["ranges"], tables["items"], tables["gaps"])
     n = params.numel()
     if tables["end"] > n or min(grads.numel(), m.numel(), v.numel(), shadow.numel()) < n:
-        raise L.TtskError("optim_step_ranges: the ranges end at element %d, the buffers hold %d" % (tables["end"], n))
+        raise L.TtskError("optim_step: the ranges end at element %d, the buffers hold %d" % (tables["end"], n))
     arr = (C.c_float * 4)(*([float(a) for a in anneal_steps] + [0.0] * (4 - len(anneal_steps))))
-    check(L.load().ttsk_optim_step_ranges(_ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(shadow), params.numel(), _ptr(state), _ptr(partials),
-                                          max_norm, beta1, beta2, eps, int(zero_grad), float(d_model), float(warmup), C.cast(arr, C.c_void_p),
-                                          len(anneal_steps), anneal_rate, int(advance_rng), _ptr(tables["ranges"]), tables["n_ranges"],
-                                          tables["range_floats"], _ptr(tables["items"]), tables["n_items"], tables["n_tiles"],
-                                          _ptr(tables["gaps"]), tables["n_gaps"], tables["gap_floats"], _stream()),
-          "ttsk_optim_step_ranges")
+    check(L.load().ttsk_optim_step(_ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(shadow), params.numel(), _ptr(state), _ptr(partials),
+                                   max_norm, beta1, beta2, eps, int(zero_grad), float(d_model), float(warmup), C.cast(arr, C.c_void_p),
+                                   len(anneal_steps), anneal_rate, int(advance_rng), _ptr(tables["ranges"]), tables["n_ranges"],
+                                   tables["range_floats"], _ptr(tables["items"]), tables["n_items"], tables["n_tiles"],
+                                   _ptr(tables["gaps"]), tables["n_gaps"], tables["gap_floats"], _stream()),
+          "ttsk_optim_step")
 
 
 # ---------------------------------------------------------------------------------------------------- HiFi-GAN helpers

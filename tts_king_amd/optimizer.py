@@ -27,14 +27,13 @@ class ScheduledOptim:
         self.init_lr = np.power(self.d_model, -0.5)
         # Speaker adaptation (FastSpeech2.set_trainable): clip and Adam cover the trainable ranges of the flat buffer only; from here
         # on the units are fixed (the Adam state, the device tables and the checkpoint layout follow them)
-        self._subset = getattr(model, "trainable_units", None) is not None
-        if hasattr(model, "_optimizer_built"):
-            model._optimizer_built = True
+        self._subset = model.trainable_units is not None
+        model._optimizer_built = True
         flat, grad, _ = model.flat_buffers()
         self.exp_avg = torch.zeros_like(flat)
         self.exp_avg_sq = torch.zeros_like(flat)
         # the device state block (a plain CPU tensor for a CPU-resident model: checkpoint plumbing works there, kernels do not)
-        self.state = ops.optim_state(flat.device, seed=getattr(model, "_seed", 1234), sched_step=int(current_step))
+        self.state = ops.optim_state(flat.device, seed=model._seed, sched_step=int(current_step))
         model.attach_state(self.state)
         self._partials = torch.empty(1024, dtype=torch.float32, device=flat.device)
         self._host_step = int(current_step)
@@ -59,36 +58,22 @@ class ScheduledOptim:
         zero the gradient buffer (the sync-free step path: its next backward overwrites, FastSpeech2.backward_native); the default
         leaves zeros, as the reference's `zero_grad()` right after the step does (train.py:54)."""
         flat, grad, shadow = self.model.flat_buffers()
-        tables = getattr(self.model, "_adam_tables", None) if getattr(self.model, "window_ffn", False) else None
-        if self._subset:
-            # norm, clip, Adam, shadow over the trainable ranges only; the Adam launch writes the packs of the trainable packed weights,
-            # the packs of frozen weights are not rewritten (ttsk_optim_step_ranges)
-            rt = self.model._range_tables
-            if rt is None:
-                raise ops.L.TtskError("the subset optimizer step needs the model on a HIP device (no tables were built)")
-            ops.optim_step_ranges(flat, grad, self.exp_avg, self.exp_avg_sq, shadow, self.state, self._partials, self.grad_clip_thresh,
-                                  self.betas[0], self.betas[1], self.eps, self.d_model, self.n_warmup_steps, self.anneal_steps,
-                                  self.anneal_rate, rt, zero_grad=not keep_grads, advance_rng=advance_rng)
-            self.model.refresh_trainable_packs()   # the trainable 80-channel ends, when there are any
-        elif tables is not None:
-            # the Adam launch writes the window kernels' fragment-major weight packs itself (tile by tile, from LDS)
-            ops.optim_step_packed(flat, grad, self.exp_avg, self.exp_avg_sq, shadow, self.state, self._partials, self.grad_clip_thresh,
-                                  self.betas[0], self.betas[1], self.eps, self.d_model, self.n_warmup_steps, self.anneal_steps,
-                                  self.anneal_rate, tables, zero_grad=not keep_grads, advance_rng=advance_rng)
-            if hasattr(self.model, "refresh_odd_packs"):
-                self.model.refresh_odd_packs()     # the few packs that launch does not write (the PostNet's 80-channel ends)
-        else:
-            ops.optim_step(flat, grad, self.exp_avg, self.exp_avg_sq, shadow, self.state, self._partials, self.grad_clip_thresh,
-                           self.betas[0], self.betas[1], self.eps, self.d_model, self.n_warmup_steps, self.anneal_steps, self.anneal_rate,
-                           zero_grad=not keep_grads, advance_rng=advance_rng)
-            self.model.refresh_packed()      # the step rewrote the bf16 shadow: so are the fragment-major copies read by the window conv
+        tables = self.model._optim_tables
+        if tables is None:
+            raise ops.L.TtskError("the optimizer step needs the model on a HIP device (no tables were built)")
+        # norm, clip, Adam, shadow over the trainable ranges (everything trained: one range); the Adam launch writes the packs of the
+        # trainable packed weights, the packs of frozen weights are not rewritten
+        ops.optim_step(flat, grad, self.exp_avg, self.exp_avg_sq, shadow, self.state, self._partials, self.grad_clip_thresh,
+                       self.betas[0], self.betas[1], self.eps, self.d_model, self.n_warmup_steps, self.anneal_steps, self.anneal_rate,
+                       tables, zero_grad=not keep_grads, advance_rng=advance_rng)
+        self.model.refresh_after_step()      # the packs that launch does not write (the 80-channel ends; all of them without items)
         self._host_step += 1
         self.model.grads_partial = False     # zeroed, or stale and to be overwritten: either way the next backward need not accumulate
 
     def zero_grad(self):
         """reference: ScheduledOptim.zero_grad (optimizer.py:29-30).  After `step_and_update_lr()` the buffer is already zero; in the
         middle of an accumulation cycle this discards it."""
-        if getattr(self.model, "grads_partial", False):
+        if self.model.grads_partial:
             grad = self.model.flat_buffers()[1]
             if self._subset:
                 for a, b in self.model.trainable_ranges():     # (frozen stretches are never read: they may hold anything)
