@@ -8,7 +8,17 @@ Pipeline (all on the current stream, no host math after construction): `ttsk_stf
 fp16 hi/lo split) -> one `ttsk_gemm` conv launch with the windowed Fourier basis (hi*hi + hi*lo + lo*hi as one contraction,
 fp32 accumulate: the reference's own conv-STFT, stft.py:77-84) -> `ttsk_mel_from_spec` (magnitude, Slaney mel filterbank,
 log-clamp, energy).  The filterbank is librosa 0.7.2's `filters.mel(htk=False, norm=1)` (reference requirements.txt:3),
-built here from its published definition because librosa is not a dependency of this package."""
+built here from its published definition because librosa is not a dependency of this package.
+
+Accepted envelope (pinned by tests/test_mel_envelope_gpu.py against an fp64 restatement): n_fft % hop == 0, hop % 8 == 0,
+1 <= win <= n_fft <= 2048 (a shorter window is centre-padded), 1 <= num_mels <= 80, any sampling rate, fmin and fmax (None = Nyquist);
+anything else is a ValueError at construction.  Every accepted configuration runs: n_fft / hop is the conv's tap count and is not
+limited (ttsk_gemm plans more than 32 taps onto its register-staged kernels; tested to 128 taps at hop = 8), n_fft <= 1150
+launches mel_from_spec_kernel<9> and larger ones <17>.  A signal must be longer than its reflect padding ((n_fft - hop)//2 on the
+vocoder surface, n_fft//2 on Tacotron's) and give one frame, else ValueError.  Amplitude: the signal is scaled by 4096 and rounded to fp16,
+so |y| must stay below MAX_AMPLITUDE = 65520/4096 (just under 16).  `mel_spectrogram` checks that (one reduction and one host read per
+call) and raises ValueError; `TacotronSTFT` keeps the reference's own |y| <= 1 assertion.  Log-mel is within 1e-4 of fp64 on broadband
+input at every such configuration, energy within 1e-4 relative."""
 import numpy as np
 import torch
 
@@ -16,6 +26,7 @@ from . import ops
 
 _SIG_SCALE = 4096.0      # powers of two: keep the fp16 low parts of signal and basis in the normal range
 _BASIS_SCALE = 1024.0
+MAX_AMPLITUDE = 65520.0 / _SIG_SCALE     # 15.996...: from here on the scaled sample rounds to fp16 inf
 
 
 def _hz_to_mel(f):
@@ -45,8 +56,10 @@ class MelExtractor:
     the magnitude's square root (1e-9 in hifi/meldataset.py:69, 0 in fs_two/audio/stft.py:86)."""
 
     def __init__(self, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, pad, eps, device="cuda:0"):
-        if n_fft % hop_size or hop_size % 8 or win_size > n_fft or num_mels > 80 or n_fft > 2048:
-            raise ValueError("MelExtractor needs n_fft % hop_size == 0, hop_size % 8 == 0, win_size <= n_fft <= 2048, num_mels <= 80")
+        if hop_size < 8 or n_fft % hop_size or hop_size % 8 or not 1 <= win_size <= n_fft or not 1 <= num_mels <= 80 or n_fft > 2048:
+            raise ValueError("MelExtractor needs n_fft %% hop_size == 0, hop_size %% 8 == 0, win_size <= n_fft <= 2048, num_mels <= 80 "
+                             "(any number n_fft / hop_size of taps), got n_fft=%r hop_size=%r win_size=%r num_mels=%r"
+                             % (n_fft, hop_size, win_size, num_mels))
         self.n_fft, self.hop, self.num_mels, self.pad, self.eps = n_fft, hop_size, num_mels, int(pad), float(eps)
         self.taps = n_fft // hop_size
         self.nbins = n_fft // 2 + 1
@@ -84,13 +97,15 @@ class MelExtractor:
         return 1 + (n_samples + 2 * self.pad - self.n_fft) // self.hop
 
     def __call__(self, y):
-        """y (B, L) fp32 on the device, |y| <= 1 -> (log-mel (B, num_mels, T), energy (B, T))."""
+        """y (B, L) fp32 on the device, |y| < MAX_AMPLITUDE (not checked here) -> (log-mel (B, num_mels, T), energy (B, T))."""
         if y.dim() != 2 or y.dtype != torch.float32:
             raise ValueError("MelExtractor: y must be (B, L) fp32")
         Bsz, n = y.shape
         T = self.frames(n)
         if T < 1:
             raise ValueError("MelExtractor: signal shorter than one frame")
+        if n <= self.pad:
+            raise ValueError("MelExtractor: reflect padding by %d samples needs a signal longer than that, got %d" % (self.pad, n))
         rows = T + self.taps - 1
         sig = ops.stft_frames(y.contiguous(), self.pad, rows, self.hop, _SIG_SCALE)
         spec = torch.empty(Bsz * rows, self.cout, dtype=torch.float32, device=y.device)
@@ -112,6 +127,11 @@ def mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin,
     if key not in _extractors:
         _extractors[key] = MelExtractor(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax,
                                         pad=(n_fft - hop_size) // 2, eps=1e-9, device=y.device)
+    # the reference takes any amplitude; here the scaled signal must fit fp16.  One reduction and one host read per call.
+    peak = float(y.abs().max()) if y.numel() else 0.0
+    if not peak < MAX_AMPLITUDE:
+        raise ValueError("mel_spectrogram: |y| must stay below 16 (%g: the signal is scaled by %g and rounded to fp16), got %g"
+                         % (MAX_AMPLITUDE, _SIG_SCALE, peak))
     return _extractors[key](y)[0]
 
 
