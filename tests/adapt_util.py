@@ -14,22 +14,25 @@ def _handle(x):
 class LibProxy:
     """Stands in for the loaded library (`lib._lib`): every call whose last argument is the current torch stream's handle (an entry
     point of include/ttsk.h that takes a stream takes it last) is logged as [name, stream index, integer arguments below 2^31], then
-    forwarded.  No pointers in the log (tensor addresses arrive as plain integers too, far above that): they differ from run to run."""
+    forwarded.  No pointers in the log (tensor addresses arrive as plain integers too, far above that): they differ from run to run.
+    `floats`: plain float arguments (slopes, scales) are logged too, in place among the integers."""
 
-    def __init__(self, real, log):
+    def __init__(self, real, log, floats=False):
         self.__dict__["_real"], self.__dict__["_log"], self.__dict__["_streams"] = real, log, {}
+        self.__dict__["_floats"] = floats
 
     def __setattr__(self, name, value):
         setattr(self._real, name, value)
 
     def __getattr__(self, name):
-        fn, log, streams = getattr(self._real, name), self._log, self._streams
+        fn, log, streams, floats = getattr(self._real, name), self._log, self._streams, self._floats
 
         def forward(*args):
             cur = torch.cuda.current_stream().cuda_stream
             last = _handle(args[-1]) if args else None
             if type(last) is int and last == cur:
-                log.append([name, streams.setdefault(cur, len(streams)), [a for a in args[:-1] if type(a) is int and abs(a) < (1 << 31)]])
+                log.append([name, streams.setdefault(cur, len(streams)),
+                            [a for a in args[:-1] if (type(a) is int and abs(a) < (1 << 31)) or (floats and type(a) is float)]])
             return fn(*args)
         return forward
 

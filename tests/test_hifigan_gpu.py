@@ -411,13 +411,11 @@ def test_window_upsample8_generator_agrees(cfg):
     gen = build_generator(cfg, DEV)
     mel = make_mel(2, 40, seed=4).to(DEV)
     gen.window_upsample = True
-    gen._packed = None
     a = gen(mel)
-    assert any(p is not None for p in gen._packed["ups8"])
+    assert any(st.ups in ("win", "loop") for st in gen._plan().stages)
     gen.window_upsample = False
-    gen._packed = None
     b = gen(mel)
-    assert all(p is None for p in gen._packed["ups8"])
+    assert not any(st.ups in ("win", "loop") for st in gen._plan().stages)
     r = rel_rms(a.cpu(), b.cpu())
     print("window-conv vs polyphase-GEMM stride-8 upsamplers: rel-RMS %.3f%%" % (100 * r))
     assert r <= 2e-3

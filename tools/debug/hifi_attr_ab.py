@@ -16,7 +16,6 @@ def build(attrs):
         k, v = kv.split("=")
         assert hasattr(gen, k), k
         setattr(gen, k, eval(v))
-    gen._packed = None
     gen(mel)
     gr = torch.cuda.CUDAGraph()
     with torch.cuda.graph(gr):

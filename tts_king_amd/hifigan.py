@@ -10,6 +10,8 @@ and cast to bf16 once.  Forward only: the reference's generator is used for infe
 raises).
 """
 import os
+from collections import namedtuple
+
 import torch
 import torch.nn as nn
 
@@ -25,6 +27,96 @@ LRELU_SLOPE = 0.1          # reference: hifi/models.py:9
 def get_padding(kernel_size, dilation=1):
     """reference: hifi/vocoder/utils.py:36-37."""
     return int((kernel_size * dilation - dilation) / 2)
+
+
+# ---------------------------------------------------------------------------------------------------- which kernel runs what
+# The kernel-family switches of a Generator: plain attributes, read by `Generator._plan()` and nowhere else.
+TOGGLES = ("window_conv", "conv_pair", "conv_pair_small", "pair_ws", "pair_ws_min_tiles", "fused", "stream_upsample", "window_upsample",
+           "loop_upsample", "mrf_fused", "resblock2_fused")
+_Toggles = namedtuple("_Toggles", TOGGLES)
+# conv_pre: "win" | "gemm"; conv_post: "fused" (inside the mrf32_post launch) | "stream" | "gemm"; refusal: None, or why `_prepare` raises
+_Plan = namedtuple("_Plan", "key c0 conv_pre stages conv_post refusal")
+# One upsampler + MRF stage.  C: its channels; ups: "loop" | "win" | "stream" | "gemm"; act_copy: the upsampler also writes lrelu(x);
+# route: "resblock2" | "pair" | "fused" | "mrf32_post" | "gemm"; gemm (that route only): "window" | "lockstep" | "blocks";
+# fused_for: kernel sizes of a pair stage that go to the six-conv kernel; nxt_slope: the LeakyReLU of whatever reads the stage's output
+_Stage = namedtuple("_Stage", "C stride ksize ups act_copy route gemm fused_for nxt_slope ws_min_tiles blocks")
+# One ResBlock.  win (gemm route): its convs on the window kernel; ws_ok (pair route, None = never): frames per utterance -> the
+# weights-stationary kernel has an instance and its 32-bit offsets reach
+_Block = namedtuple("_Block", "kind k dilation win ws_ok")
+K_PRE = K_POST = 7          # conv_pre / conv_post kernel size, hard-coded in the reference (hifi/models.py:152, :183)
+# The weight packs of a plan (`Generator._prepare`).  pre / post: (weight, bias); per stage ups: (weight, bias) as its planned upsampler
+# reads them, blocks: per ResBlock what its planned route reads
+_Packs = namedtuple("_Packs", "key plan pre stages post")
+_StagePacks = namedtuple("_StagePacks", "ups blocks")
+
+
+def build_plan(h, dt, t, key=None):
+    """Which kernel runs conv_pre, every upsampler, every MRF stage and conv_post: a pure function of the configuration `h`, the storage
+    type `dt` and the toggles `t` (a `_Toggles`).  No tensor is touched: every `ops.hifi_*_supported` is a host predicate of the library.
+    The weight packs (`Generator._prepare`), `forward_ntc`, `stage_routes()` and `short_rows()` all read the record this returns."""
+    c0, kind, n_up = int(h.upsample_initial_channel), str(h.resblock), len(h.upsample_rates)
+    kds = [(int(k), tuple(d)) for k, d in zip(h.resblock_kernel_sizes, h.resblock_dilation_sizes)]
+    ks, nk = [k for k, _ in kds], len(kds)
+    win16 = t.window_upsample and dt == torch.float16            # conv_pre and the upsamplers on the window-conv kernels: fp16 instances only
+    stages, refusal = [], None
+    for i, (u, ku) in enumerate(zip(h.upsample_rates, h.upsample_kernel_sizes)):
+        u, ku, Cin, C = int(u), int(ku), c0 // 2 ** i, c0 // 2 ** (i + 1)
+        six = kind == "1" and all(ops.hifi_resblock1_supported(C, k) for k in ks)          # the six-conv fused kernel covers every block
+        # C = 32: the fused kernel is as fast or faster for every kernel size (86 / 143 / 181 us against 102 / 139 / 178)
+        want_pair = (t.conv_pair and t.window_conv) if C >= 128 else (t.conv_pair_small and t.fused and C == 64)
+        if t.resblock2_fused and nk >= 2 and kind == "2" and all(len(d) == 2 and ops.hifi_resblock2_supported(C, k, *d) for k, d in kds):
+            route = "resblock2"
+        elif want_pair and nk >= 2 and kind == "1" and all(ops.hifi_conv_pair_supported(C, k, dd) for k, d in kds for dd in d):
+            route = "pair"
+        elif t.fused and nk >= 2 and six:
+            # the whole last stage — three blocks, their average, LeakyReLU(0.01), conv_post, tanh — in one launch
+            last = t.mrf_fused and i + 1 == n_up and ops.hifi_mrf32_post_supported(C, ks, K_POST)
+            route = "mrf32_post" if last else "fused"
+        else:
+            route = "gemm"
+            if nk != 3 and refusal is None:
+                refusal = ("HiFi-GAN stage %d runs conv by conv, where the MRF average is written for 3 resblock kernels per stage "
+                           "(got %d)" % (i, nk))
+        # as measured and shipped: the fused and mrf32_post routes choose their upsampler from {stream, gemm} only, the pair and
+        # resblock2 routes from {loop, win, stream, gemm}; the conv-by-conv route needs the polyphase GEMMs' second, activated output
+        if route in ("pair", "resblock2") and win16 and ops.hifi_upsample_win_supported(Cin, C, u, ku):
+            ups = "loop" if t.loop_upsample and ops.hifi_upsample_loop_supported(Cin, C, u, ku) else "win"
+        elif route != "gemm" and t.stream_upsample and ops.hifi_upsample2_supported(Cin, C, u, ku):
+            ups = "stream"
+        else:
+            ups = "gemm"
+        # conv by conv: the window kernel where it has an instance (C = 128), else every block's conv m as one grouped launch (equal
+        # dilation counts), else block after block
+        win = [route == "gemm" and t.window_conv and kind == "1" and all(ops.hifi_conv_window_supported(C, k, dd) for dd in d) for k, d in kds]
+        gemm = None
+        if route == "gemm":
+            gemm = "window" if all(win) else "lockstep" if kind == "1" and len({len(d) for _, d in kds}) == 1 else "blocks"
+            if gemm == "lockstep":
+                win = [False] * nk
+
+        def ws_ok(k, d, C=C):           # the predicate also bounds the utterance length, which only a call knows
+            return lambda ln: all(ops.hifi_conv_pair_ws_supported(C, k, dd, ln) for dd in d)
+
+        blocks = tuple(_Block(kind, k, d, w, ws_ok(k, d) if route == "pair" and t.pair_ws else None) for (k, d), w in zip(kds, win))
+        # measured per block at the bench shape (tools/debug/convpair_micro.py): three pair launches beat the six-conv fused kernel at
+        # C = 64 for k = 7, 11 (228 vs 242 us, 290 vs 370 us) and lose at k = 3 (158 vs 141 us: the block is then bound by its HBM
+        # passes, and the fused kernel makes one instead of three)
+        fused_for = (3,) if route == "pair" and C == 64 and six else ()
+        # slope of the activation that consumes this stage's output: 0.1 before the next upsampler, F.leaky_relu's default 0.01 before
+        # conv_post (hifi/models.py:197)
+        stages.append(_Stage(C, u, ku, ups, route == "gemm", route, gemm, fused_for, LRELU_SLOPE if i + 1 < n_up else 0.01,
+                             t.pair_ws_min_tiles, blocks))
+    conv_pre = "win" if win16 and ops.hifi_conv_pre_win_supported(80, c0, K_PRE) else "gemm"
+    conv_post = "fused" if stages and stages[-1].route == "mrf32_post" else "stream" if c0 // 2 ** n_up <= 128 else "gemm"
+    return _Plan(key, c0, conv_pre, tuple(stages), conv_post, refusal)
+
+
+def _dense(t, stage):
+    """A stage's input is a fresh `torch.empty` output of an `ops` wrapper (conv1d, hifi_conv_pre_win, avg3, the MRF kernels' `out`; the
+    upsamplers' outputs likewise), and the planned kernels index it densely: anything else is refused, there are no fall-back packs."""
+    if not t.is_contiguous():
+        raise ops.L.TtskError("HiFi-GAN stage %d: the activation tensor is not contiguous" % stage)
+    return t
 
 
 class _WNConv(nn.Module):
@@ -87,7 +179,7 @@ class Generator(nn.Module):
         for i, (u, k) in enumerate(zip(h.upsample_rates, h.upsample_kernel_sizes)):
             ops.check_upsampler(int(k), int(u), "HiFi-GAN upsampler %d" % i)
         c0 = h.upsample_initial_channel
-        self.conv_pre = _WNConv((c0, 80, 7), c0)                       # 80 is hard-coded in the reference (:152)
+        self.conv_pre = _WNConv((c0, 80, K_PRE), c0)                       # 80 is hard-coded in the reference (:152)
         self.ups = nn.ModuleList()
         for i, (u, k) in enumerate(zip(h.upsample_rates, h.upsample_kernel_sizes)):
             self.ups.append(_WNConv((c0 // (2 ** i), c0 // (2 ** (i + 1)), k), c0 // (2 ** (i + 1))))
@@ -97,9 +189,9 @@ class Generator(nn.Module):
             ch = c0 // (2 ** (i + 1))
             for k, d in zip(h.resblock_kernel_sizes, h.resblock_dilation_sizes):
                 self.resblocks.append(_ResBlock(ch, k, d, str(h.resblock)))
-        self.conv_post = _WNConv((1, ch, 7), 1)
-        self._packed = None
-        self._packed_key = None
+        self.conv_post = _WNConv((1, ch, K_POST), 1)
+        self._packed = None           # weight packs in kernel layouts (`_prepare`)
+        self._plan_memo = None        # (`_plan`)
         self.act_dtype = f16         # storage type of activations and packed weights (fp32 accumulate); bf16 also works
         self.window_conv = True      # window-conv kernel at the C = 128 stage; False = implicit-GEMM convs
         self.conv_pair = True        # each (c1, c2) pair of a ResBlock1 as one launch (ttsk_hifi_conv_pair) at C = 128 ...
@@ -144,60 +236,61 @@ class Generator(nn.Module):
     def _weights_key(self):
         return tuple((id(p), p._version) for c in self._all_convs() for p in c._parameters.values())
 
+    def _plan(self, refuse=True):
+        """`build_plan` for this generator as it is toggled now: rebuilt when `act_dtype` or one of TOGGLES changed since the last call, the
+        same object otherwise.  Needs no device.  `refuse`: raise the plan's refusal (NotImplementedError naming the stage), if any."""
+        key = (self.act_dtype,) + tuple(getattr(self, n) for n in TOGGLES)
+        if self._plan_memo is None or self._plan_memo.key != key:
+            self._plan_memo = build_plan(self.h, key[0], _Toggles(*key[1:]), key)
+        if refuse and self._plan_memo.refusal:
+            raise NotImplementedError(self._plan_memo.refusal)
+        return self._plan_memo
+
     def _prepare(self):
-        """16-bit copies of the folded weights in kernel layouts (tap-major for the implicit-GEMM convs, MFMA-fragment-
-        major for the fused ResBlock kernel), rebuilt when any parameter was written."""
-        dt = self.act_dtype
-        key = self._weights_key() + (dt,)
-        if self._packed is not None and self._packed_key == key:
+        """16-bit copies of the folded weights in the layouts the planned kernels read (tap-major for the implicit-GEMM convs and the
+        streaming kernels, MFMA-fragment-major for the window, pair and fused kernels), stage by stage: rebuilt when a parameter was
+        written or the plan changed, otherwise the same objects with no allocation and no launch (captured graphs hold their addresses)."""
+        plan = self._plan()
+        key = (self._weights_key(), plan.key)
+        if self._packed is not None and self._packed.key == key:
             return self._packed
-        self._check_mrf()
-        pk = {}
-        pk["pre"] = (ops.pack_conv_weight(self.conv_pre.folded_weight(), dtype=dt), self.conv_pre.bias.data)
-        cpre, kpre = pk["pre"][0].shape[0], pk["pre"][0].shape[1]
-        pk["pre_win"] = (ops.hifi_conv_pre_win_pack(pk["pre"][0]) if (self.window_upsample and dt == torch.float16 and
-                                                                      ops.hifi_conv_pre_win_supported(int(pk["pre"][0].shape[2]), cpre, kpre)) else None)
-        pk["ups"] = [(ops.pack_conv_weight(u.folded_weight(), transposed=True, dtype=dt), u.bias.data) for u in self.ups]
-        # the stride-8 upsamplers and the 128 -> 64 stride-2 one on the window-conv kernel (fp16 rows): a two-tap conv over the input frames
-        # with stride * Cout phase-major channels
-        pk["ups8"] = [ops.hifi_upsample_win_pack(w, b, uu) if (self.window_upsample and dt == torch.float16 and
-                                                               ops.hifi_upsample_win_supported(w.shape[2], w.shape[1], uu, kk)) else None
-                      for (w, b), uu, kk in zip(pk["ups"], self.h.upsample_rates, self.h.upsample_kernel_sizes)]
-        pk["rb"], pk["rbf"], pk["rbw"], pk["rb2"] = [], [], [], []
-        for rb in self.resblocks:
-            convs = rb.all_convs()
-            ch = convs[0].bias.shape[0]
-            if rb.kind == "2" and len(rb.dilation) == 2 and ops.hifi_resblock2_supported(ch, rb.k, *rb.dilation):
-                pk["rb2"].append(([ops.pack_resblock_weight(c.folded_weight(), dtype=dt) for c in convs], [c.bias.data for c in convs]))
-            else:
-                pk["rb2"].append(None)
-            if rb.kind == "1" and ops.hifi_resblock1_supported(ch, rb.k):
-                n = len(rb.dilation)
-                order = [convs[m // 2 + (n if m % 2 else 0)] for m in range(2 * n)]          # c1_0, c2_0, c1_1, c2_1, ...
-                pk["rbf"].append(([ops.pack_resblock_weight(c.folded_weight(), dtype=dt) for c in order], [c.bias.data for c in order]))
-            else:
-                pk["rbf"].append(None)
-            if rb.kind == "1" and pk["rbf"][-1] is None and (all(ops.hifi_conv_window_supported(ch, rb.k, dd) for dd in rb.dilation) or
-                                                             all(ops.hifi_conv_pair_supported(ch, rb.k, dd) for dd in rb.dilation)):
-                pk["rbw"].append([ops.pack_resblock_weight(c.folded_weight(), dtype=dt) for c in convs])     # window-conv packs
-            else:
-                pk["rbw"].append(None)
-            pk["rb"].append([(ops.pack_conv_weight(c.folded_weight(), dtype=dt), c.bias.data) for c in convs])
-        pk["post"] = (ops.pack_conv_weight(self.conv_post.folded_weight(), dtype=dt), self.conv_post.bias.data)
-        self._packed, self._packed_key = pk, key
-        return pk
+        dt = self.act_dtype
+        tap = lambda c, transposed=False: ops.pack_conv_weight(c.folded_weight(), transposed=transposed, dtype=dt)
+        frag = lambda c: ops.pack_resblock_weight(c.folded_weight(), dtype=dt)
+        pre = tap(self.conv_pre)
+        if plan.conv_pre == "win":
+            pre = ops.hifi_conv_pre_win_pack(pre)
+        rbs, stages = iter(self.resblocks), []
+        for st, up in zip(plan.stages, self.ups):
+            ups = (tap(up, True), up.bias.data)
+            if st.ups in ("loop", "win"):       # a two-tap conv over the input frames with stride * Cout phase-major channels
+                ups = ops.hifi_upsample_win_pack(ups[0], ups[1], st.stride)
+            blocks = []
+            for blk, rb in zip(st.blocks, rbs):
+                convs = rb.all_convs()
+                if st.route == "gemm":          # ([(tap-major weight, bias)] convs1 then convs2, the window kernel's packs or None)
+                    blocks.append(([(tap(c), c.bias.data) for c in convs], [frag(c) for c in convs] if blk.win else None))
+                    continue
+                if rb.kind == "1":              # launch order: c1_0, c2_0, c1_1, c2_1, ...
+                    n = len(rb.dilation)
+                    convs = [convs[m // 2 + (n if m % 2 else 0)] for m in range(2 * n)]
+                blocks.append(([frag(c) for c in convs], [c.bias.data for c in convs]))
+            stages.append(_StagePacks(ups, blocks))
+        self._packed = _Packs(key, plan, (pre, self.conv_pre.bias.data), stages, (tap(self.conv_post), self.conv_post.bias.data))
+        return self._packed
 
     # ------------------------------------------------------------------ forward
     def _resblock(self, rb, packed, x, xl, wpacks=None):
-        """reference: hifi/models.py:88-95 (ResBlock1) / :136-140 (ResBlock2), conv by conv on the implicit-GEMM kernel.
-        x = block input, xl = lrelu(x).  Every LeakyReLU is applied by the PRODUCING conv's epilogue (LRELU_OUT, or a
-        second output C2 = lrelu(v) next to the raw v the residual path needs), the residual add is an epilogue too."""
+        """reference: hifi/models.py:88-95 (ResBlock1) / :136-140 (ResBlock2), conv by conv on the implicit-GEMM kernel, or (`wpacks`:
+        ResBlock1 at C = 128) on the window kernel.  x = block input, xl = lrelu(x).  Every LeakyReLU is applied by the PRODUCING conv's
+        epilogue (LRELU_OUT, or a second output C2 = lrelu(v) next to the raw v the residual path needs), the residual add is an epilogue
+        too."""
         nd = len(rb.dilation)
         for m, d in enumerate(rb.dilation):
             lastp = m == nd - 1
             xl_next = None if lastp else torch.empty_like(x)
-            if rb.kind == "1" and wpacks is not None and self.window_conv:
-                # C = 128: one window-conv launch per conv (activation window in LDS, weights streamed)
+            if wpacks is not None:
+                # one window-conv launch per conv (activation window in LDS, weights streamed)
                 tl = ops.hifi_conv_window(xl, wpacks[m], packed[m][1], rb.k, d, lrelu_out=True, slope=LRELU_SLOPE)
                 x = ops.hifi_conv_window(tl, wpacks[nd + m], packed[nd + m][1], rb.k, 1, R=x, out2=xl_next, slope=LRELU_SLOPE)
             elif rb.kind == "1":
@@ -211,49 +304,35 @@ class Generator(nn.Module):
             xl = xl_next
         return x
 
-    def _pair_blocks(self, rbs, packs, a, nxt_slope, fused_for=(), rows=None):
-        """The stage's ResBlock1s on the pair kernel (hifi/models.py:88-95, :190-197): per block three launches, each one
-        (c1 dilated -> lrelu -> c2 -> + x); every block's last launch adds into `out` and the last block's scales by 1/num_kernels and
-        applies the consumer's LeakyReLU (the MRF average).  packs[j] = (weight packs, biases), both in the order c1_0, c2_0, c1_1,
-        c2_1, ...; blocks whose kernel size is in `fused_for` run on the six-conv fused kernel instead (same packs, same modes).
+    def _mrf_blocks(self, st, packs, a, rows=None):
+        """The resblock2, fused and pair routes: the stage's ResBlocks on kernels that fold the MRF average (hifi/models.py:190-197) into their
+        epilogue.  Every block's (last) launch adds into `out` (modes 0 / 1 / 2), the last block's scales by 1/num_kernels and applies the
+        consumer's LeakyReLU.  a = the raw upsampler output: the kernels activate it themselves.  packs[j] = (weight packs, biases) in launch
+        order.  Pair route (per block three launches, each c1 dilated -> lrelu -> c2 -> + x): blocks whose kernel size is in `st.fused_for`
+        run on the six-conv fused kernel instead (same packs, same modes), unless the weights-stationary kernel takes them.
         `rows`: per-row lengths (ops._row_args): the kernels store nothing past a row's end, so `out` starts as zeros — what the next
         upsampler must read there."""
-        nk = len(rbs)
+        nk = len(st.blocks)
         out = torch.empty_like(a) if rows is None else torch.zeros_like(a)
-        for j, rb in enumerate(rbs):
-            ws, bs = packs[j]
-            mode = 0 if j == 0 else (2 if j == nk - 1 else 1)
-            fs = nxt_slope if j == nk - 1 else 1.0
-            # the persistent kernel walks runs of 192-frame tiles (96 at C = 128), one workgroup per CU, and pays a pipeline fill and drain of one tile each per
-            # launch: worth it from ~4 tiles per CU on (the bench batch: 8); one utterance of 5 s is 299 tiles at the last stage and stays on the round-5 kernels
-            tt = ops.hifi_conv_pair_ws_tile(a.shape[2])
-            ws_kernel = (self.pair_ws and a.is_contiguous() and a.shape[0] * ((a.shape[1] + tt - 1) // tt) >= self.pair_ws_min_tiles and
-                         all(ops.hifi_conv_pair_ws_supported(a.shape[2], rb.k, d, a.shape[1]) for d in rb.dilation))
-            if rb.k in fused_for and not ws_kernel:
-                ops.hifi_resblock1(a, ws, bs, rb.dilation, out, rb.k, mode=mode, scale=1.0 / nk, slope=LRELU_SLOPE, final_slope=fs, rows=rows)
+        # the persistent kernel walks runs of 192-frame tiles (96 at C = 128), one workgroup per CU, and pays a pipeline fill and drain of one tile each per
+        # launch: worth it from ~4 tiles per CU on (the bench batch: 8); one utterance of 5 s is 299 tiles at the last stage and stays on the round-5 kernels
+        tt = ops.hifi_conv_pair_ws_tile(st.C)
+        tiles = a.shape[0] * ((a.shape[1] + tt - 1) // tt)
+        for j, (blk, (ws, bs)) in enumerate(zip(st.blocks, packs)):
+            last = j == nk - 1
+            mrf = dict(mode=0 if j == 0 else (2 if last else 1), scale=1.0 / nk, final_slope=st.nxt_slope if last else 1.0)
+            if st.route == "resblock2":
+                ops.hifi_resblock2(a, ws[0], bs[0], ws[1], bs[1], blk.k, blk.dilation, slope=LRELU_SLOPE, out=out, rows=rows, **mrf)
                 continue
-            x, nd = a, len(rb.dilation)
-            for m, d in enumerate(rb.dilation):
-                kw = dict(out=out, mode=mode, scale=1.0 / nk, final_slope=fs) if m == nd - 1 else {}
-                x = ops.hifi_conv_pair(x, ws[2 * m], bs[2 * m], ws[2 * m + 1], bs[2 * m + 1], rb.k, d, slope=LRELU_SLOPE, ws=ws_kernel, rows=rows, **kw)
+            ws_kernel = blk.ws_ok is not None and tiles >= st.ws_min_tiles and blk.ws_ok(a.shape[1])
+            if st.route == "fused" or (blk.k in st.fused_for and not ws_kernel):
+                ops.hifi_resblock1(a, ws, bs, blk.dilation, out, blk.k, slope=LRELU_SLOPE, rows=rows, **mrf)
+                continue
+            x, nd = a, len(blk.dilation)
+            for m, d in enumerate(blk.dilation):
+                kw = dict(out=out, **mrf) if m == nd - 1 else {}
+                x = ops.hifi_conv_pair(x, ws[2 * m], bs[2 * m], ws[2 * m + 1], bs[2 * m + 1], blk.k, d, slope=LRELU_SLOPE, ws=ws_kernel, rows=rows, **kw)
         return out
-
-    def _pair_packs(self, pk, i, nk, rbs, C):
-        """Weight packs / biases of stage i in `_pair_blocks` order, or None when the pair kernel does not cover the stage."""
-        if nk < 2 or not all(rb.kind == "1" and all(ops.hifi_conv_pair_supported(C, rb.k, d) for d in rb.dilation) for rb in rbs):
-            return None
-        packs = []
-        for j, rb in enumerate(rbs):
-            n = len(rb.dilation)
-            if pk["rbf"][i * nk + j] is not None:                      # packed for the fused kernel: already in pair order
-                packs.append(pk["rbf"][i * nk + j])
-            elif pk["rbw"][i * nk + j] is not None:                    # window packs: convs1 then convs2
-                w, b = pk["rbw"][i * nk + j], [p[1] for p in pk["rb"][i * nk + j]]
-                order = [m // 2 + (n if m % 2 else 0) for m in range(2 * n)]
-                packs.append(([w[o] for o in order], [b[o] for o in order]))
-            else:
-                return None
-        return packs
 
     def _resblocks_lockstep(self, rbs, packs, x, xl):
         """The stage's ResBlock1s (one per MRF kernel size, hifi/models.py:190-196) advanced conv by conv TOGETHER: they read
@@ -277,18 +356,21 @@ class Generator(nn.Module):
             xls = nxt
         return xs
 
-    def _upsample_raw(self, al, pk, i):
-        """ConvTranspose1d i (hifi/models.py:189) without an activated copy: the window / looped kernels where `pk["ups8"]` has a pack
-        (fp16: stride 8 from 256 / 512 channels, 128 -> 64 at stride 2), the streaming stride-2 kernel, else the polyphase implicit GEMMs."""
-        wu, bu = pk["ups"][i]
-        u, k, C_out = self.h.upsample_rates[i], self.h.upsample_kernel_sizes[i], wu.shape[1]
-        if pk["ups8"][i] is not None and al.is_contiguous():
-            if self.loop_upsample and ops.hifi_upsample_loop_supported(al.shape[2], C_out, u, k):
-                return ops.hifi_upsample_loop(al, pk["ups8"][i][0], pk["ups8"][i][1], C_out, u)      # 256 -> 128: channel groups looped per frame tile
-            return ops.hifi_upsample_win(al, pk["ups8"][i][0], pk["ups8"][i][1], C_out, u)
-        if self.stream_upsample and ops.hifi_upsample2_supported(wu.shape[2], wu.shape[1], u, k) and al.is_contiguous():
-            return ops.hifi_upsample2(al, wu, bu)
-        return ops.conv_transpose1d(al, wu, bu, u, k)
+    def _upsample(self, st, packs, al):
+        """ConvTranspose1d of a stage (hifi/models.py:189) on its planned kernel -> (x, lrelu(x) where the plan asks for that copy, else None):
+        the looped / window kernels (fp16: stride 8 from 256 / 512 channels, 128 -> 64 at stride 2), the streaming stride-2 kernel (both
+        phases from one read of `al`), else the polyphase implicit GEMMs."""
+        w, b = packs
+        if st.ups == "loop":
+            return ops.hifi_upsample_loop(al, w, b, st.C, st.stride), None       # 256 -> 128: channel groups looped per frame tile
+        if st.ups == "win":
+            return ops.hifi_upsample_win(al, w, b, st.C, st.stride), None
+        if st.ups == "stream":
+            return ops.hifi_upsample2(al, w, b), None
+        if not st.act_copy:
+            return ops.conv_transpose1d(al, w, b, st.stride, st.ksize), None
+        axl = torch.empty(al.shape[0], al.shape[1] * st.stride, st.C, dtype=al.dtype, device=al.device)
+        return ops.conv_transpose1d(al, w, b, st.stride, st.ksize, C2=axl, flags=ops.C2_LRELU, out_slope=LRELU_SLOPE), axl
 
     _stage_marks = None     # bench.py's per-stage timing: a list to which forward appends (name, HIP event) at stage boundaries
 
@@ -317,101 +399,50 @@ class Generator(nn.Module):
         `row_frames` (1-D int32 device tensor or view of B entries, e.g. column `windows.VALID` of a plan table; needs `short_rows()`):
         row b holds an utterance of row_frames[b] frames (0 = all T) and its waveform is what the utterance gives alone — at a stage
         with s samples per frame the positions >= row_frames[b] * s are zero padding for every conv.  a0 must be zero
-        there (ttsk_mel_windows writes it so); the samples of the output past a row's end are unspecified."""
+        there (ttsk_mel_windows writes it so); the samples of the output past a row's end are unspecified.
+
+        Every kernel is the plan's; only what depends on the shapes is decided here (`rows`, the weights-stationary pair kernel)."""
         if pk is None:
             pk = self._prepare()
-        h = self.h
-        nk = self.num_kernels
-        rows, spf = None, 1
+        plan, rows, spf = pk.plan, None, 1
         with torch.no_grad():
-            if pk["pre_win"] is not None:
-                al = ops.hifi_conv_pre_win(a0, pk["pre_win"], pk["pre"][1], pk["pre"][0].shape[0], pk["pre"][0].shape[1], LRELU_SLOPE)   # window kernel
+            w, b = pk.pre
+            if plan.conv_pre == "win":
+                al = ops.hifi_conv_pre_win(a0, w, b, plan.c0, K_PRE, LRELU_SLOPE)             # lrelu(conv_pre(x)), window kernel
             else:
-                al = ops.conv1d(a0, pk["pre"][0], pk["pre"][1], flags=ops.LRELU_OUT, out_slope=LRELU_SLOPE)   # lrelu(conv_pre(x))
+                al = ops.conv1d(a0, w, b, flags=ops.LRELU_OUT, out_slope=LRELU_SLOPE)
             if row_frames is not None:
                 # conv_pre and the upsamplers know no row length: what conv_pre leaves past a row's end (bias, the taps that reach back)
                 # is zeroed here, every MRF stage below masks its reads of the upsampler's output and hands on zeros past the end
                 ops.zero_rows_past(al, (row_frames, 1))
-            for i, (u, k) in enumerate(zip(h.upsample_rates, h.upsample_kernel_sizes)):
+            for i, (st, sp) in enumerate(zip(plan.stages, pk.stages)):
                 self._mark("conv_pre" if i == 0 else "mrf%d" % (i - 1))
-                spf *= int(u)
+                spf *= st.stride
                 if row_frames is not None:
+                    if st.route == "gemm":
+                        raise ops.L.TtskError("HiFi-GAN stage %d runs conv by conv, which takes no per-row length (Generator.short_rows() is False)" % i)
                     rows = (row_frames, spf)
-                wu, bu = pk["ups"][i]
-                # slope of the activation that consumes this stage's output: 0.1 before the next upsampler,
-                # F.leaky_relu's default 0.01 before conv_post (hifi/models.py:197)
-                nxt_slope = LRELU_SLOPE if i + 1 < self.num_upsamples else 0.01
-                rbs = [self.resblocks[i * nk + j] for j in range(nk)]
-                C_out = wu.shape[1]
-                if self.resblock2_fused and nk >= 2 and all(pk["rb2"][i * nk + j] is not None for j in range(nk)):
-                    # V3 (ResBlock2): one launch per block on the raw upsampler output, the MRF average and the consumer's LeakyReLU
-                    # folded into the last block's epilogue (modes 0 / 1 / 2): no lrelu copy from the upsampler, no avg3 pass
-                    a = self._upsample_raw(al, pk, i)
-                    self._mark("ups%d" % i)
-                    out = torch.empty_like(a) if rows is None else torch.zeros_like(a)
-                    for j, rb in enumerate(rbs):
-                        (w0, w1), (b0, b1) = pk["rb2"][i * nk + j]
-                        lastb = j == nk - 1
-                        ops.hifi_resblock2(a, w0, b0, w1, b1, rb.k, rb.dilation, slope=LRELU_SLOPE, out=out, mode=0 if j == 0 else (2 if lastb else 1),
-                                           scale=1.0 / nk, final_slope=nxt_slope if lastb else 1.0, rows=rows)
-                    al = out
-                    continue
-                # C = 32: the fused kernel is as fast or faster for every kernel size (86 / 143 / 181 us against 102 / 139 / 178)
-                want_pair = (self.conv_pair and self.window_conv) if C_out >= 128 else (self.conv_pair_small and self.fused and C_out == 64)
-                ppacks = self._pair_packs(pk, i, nk, rbs, C_out) if want_pair else None
-                if ppacks is not None:
-                    a = self._upsample_raw(al, pk, i)                                        # raw x: the pair kernels activate it themselves
-                    # measured per block at the bench shape (tools/debug/convpair_micro.py): three pair launches beat the six-conv
-                    # fused kernel at C = 64 for k = 7, 11 (228 vs 242 us, 290 vs 370 us) and lose at k = 3 (158 vs 141 us: the block is
-                    # then bound by its HBM passes, and the fused kernel makes one instead of three)
-                    fused_for = (3,) if C_out == 64 and all(pk["rbf"][i * nk + j] is not None for j in range(nk)) else ()
-                    self._mark("ups%d" % i)
-                    al = self._pair_blocks(rbs, ppacks, a, nxt_slope, fused_for, rows)
-                    continue
-                fused = self.fused and all(pk["rbf"][i * nk + j] is not None for j in range(nk)) and nk >= 2
-                if fused:
-                    if self.stream_upsample and ops.hifi_upsample2_supported(wu.shape[2], wu.shape[1], u, k) and al.is_contiguous():
-                        a = ops.hifi_upsample2(al, wu, bu)                                 # both phases from one read of `al`
-                    else:
-                        a = ops.conv_transpose1d(al, wu, bu, u, k)                         # raw x: the fused blocks activate it themselves
-                    self._mark("ups%d" % i)
-                    if (self.mrf_fused and i + 1 == self.num_upsamples and nk == 3 and a.is_contiguous() and
-                            ops.hifi_mrf32_post_supported(C_out, [rb.k for rb in rbs], pk["post"][0].shape[1])):
-                        # the whole last stage — three blocks, their average, LeakyReLU(0.01), conv_post, tanh — in one launch: x is
-                        # read once, the waveform written once (hifi/models.py:190-199)
-                        ws = [w for j in range(nk) for w in pk["rbf"][i * nk + j][0]]
-                        bs = [b for j in range(nk) for b in pk["rbf"][i * nk + j][1]]
-                        y = ops.hifi_mrf32_post(a, ws, bs, [rb.dilation for rb in rbs], [rb.k for rb in rbs], pk["post"][0], pk["post"][1],
-                                                slope=LRELU_SLOPE, final_slope=nxt_slope, scale=1.0 / nk, rows=rows)
-                        self._mark("mrf%d" % i)
-                        self._mark("conv_post")
-                        return y
-                    out = torch.empty_like(a) if rows is None else torch.zeros_like(a)
-                    for j, rb in enumerate(rbs):
-                        ws, bs = pk["rbf"][i * nk + j]
-                        lastb = j == nk - 1
-                        ops.hifi_resblock1(a, ws, bs, rb.dilation, out, rb.k, mode=0 if j == 0 else (2 if lastb else 1),
-                                           scale=1.0 / nk, slope=LRELU_SLOPE, final_slope=nxt_slope if lastb else 1.0, rows=rows)
-                    al = out
-                    continue
-                if rows is not None:
-                    raise ops.L.TtskError("HiFi-GAN stage %d runs conv by conv, which takes no per-row length (Generator.short_rows() is False)" % i)
-                windowed = self.window_conv and all(pk["rbw"][i * nk + j] is not None and ops.hifi_conv_window_supported(C_out, rbs[j].k, dd)
-                                                    for j in range(nk) for dd in rbs[j].dilation)
-                axl = torch.empty(al.shape[0], al.shape[1] * u, wu.shape[1], dtype=al.dtype, device=al.device)
-                a = ops.conv_transpose1d(al, wu, bu, u, k, C2=axl, flags=ops.C2_LRELU, out_slope=LRELU_SLOPE)   # x and lrelu(x)
+                a, axl = self._upsample(st, sp.ups, _dense(al, i))
                 self._mark("ups%d" % i)
-                if all(rb.kind == "1" for rb in rbs) and len({len(rb.dilation) for rb in rbs}) == 1 and not windowed:
-                    outs = self._resblocks_lockstep(rbs, [pk["rb"][i * nk + j] for j in range(nk)], a, axl)
+                if st.route == "mrf32_post":
+                    # x is read once, the waveform written once (hifi/models.py:190-199)
+                    y = ops.hifi_mrf32_post(a, [w for p in sp.blocks for w in p[0]], [b for p in sp.blocks for b in p[1]],
+                                            [blk.dilation for blk in st.blocks], [blk.k for blk in st.blocks], pk.post[0], pk.post[1],
+                                            slope=LRELU_SLOPE, final_slope=st.nxt_slope, scale=1.0 / len(st.blocks), rows=rows)
+                    self._mark("mrf%d" % i)
+                    self._mark("conv_post")
+                    return y
+                if st.route != "gemm":
+                    al = self._mrf_blocks(st, sp.blocks, a, rows)
+                    continue
+                if st.gemm == "lockstep":
+                    outs = self._resblocks_lockstep(st.blocks, [taps for taps, _ in sp.blocks], a, axl)
                 else:
-                    outs = [self._resblock(rb, pk["rb"][i * nk + j], a, axl, pk["rbw"][i * nk + j]) for j, rb in enumerate(rbs)]
-                if nk == 3:
-                    al = ops.avg3(outs[0], outs[1], outs[2], 1.0 / 3.0, slope=nxt_slope)   # lrelu(xs / num_kernels)
-                else:
-                    raise NotImplementedError("MRF average is written for 3 resblock kernels per stage")
-            wp, bp = pk["post"]
-            self._mark("mrf%d" % (self.num_upsamples - 1))
-            if al.shape[2] <= 128:
+                    outs = [self._resblock(blk, taps, a, axl, wpacks) for blk, (taps, wpacks) in zip(st.blocks, sp.blocks)]
+                al = ops.avg3(outs[0], outs[1], outs[2], 1.0 / 3.0, slope=st.nxt_slope)         # lrelu(xs / num_kernels); three blocks: `build_plan`
+            wp, bp = pk.post
+            self._mark("mrf%d" % (len(plan.stages) - 1))
+            if plan.conv_post == "stream":
                 y = ops.hifi_conv_post(al, wp, bp)                                         # conv_post -> tanh, streaming kernel
                 self._mark("conv_post")
                 return y
@@ -434,50 +465,15 @@ class Generator(nn.Module):
         """True when an utterance shorter than a window can run as a row of the windowed batch: every MRF stage of this configuration, with
         the kernel families as they are toggled on this object, runs on kernels that take a per-row length (ResBlock2 fused, the conv
         pairs, the fused ResBlock1 / last-stage kernel).  False for a stage on the conv-by-conv implicit-GEMM path: such a generator keeps
-        the solo route for short utterances (`forward_short`).  The same walk as `forward_ntc`'s route choice."""
-        if self.conv_pre.bias.device.type != "cuda":
-            return False
-        # the answer depends on the configuration, the storage type and the toggles, not on the weights: kept per such key, so that a
-        # replayed list call does not walk the parameters (`_prepare`'s key) just to plan
-        key = (self.act_dtype, self.window_conv, self.conv_pair, self.conv_pair_small, self.fused, self.resblock2_fused, self.window_upsample)
-        if self._short_rows_memo is not None and self._short_rows_memo[0] == key:
-            return self._short_rows_memo[1]
-        self._short_rows_memo = (key, self._short_rows_walk())
-        return self._short_rows_memo[1]
-
-    _short_rows_memo = None
+        the solo route for short utterances (`forward_short`).  From the plan (`_plan`, kept per toggle setting): no walk over the
+        parameters, so a replayed list call plans for nothing."""
+        return self.conv_pre.bias.device.type == "cuda" and "gemm" not in self.stage_routes()
 
     def stage_routes(self):
         """Per MRF stage, the kernel family `forward_ntc` runs it on: "resblock2" (fused ResBlock2), "pair" (conv pairs), "fused" (the
         six-conv ResBlock1 kernel / the fused last stage) or "gemm" (conv by conv on the implicit-GEMM kernel).  From the configuration
-        and the toggles on this object alone — the same conditions as `_prepare`'s packs and `forward_ntc`'s route choice."""
-        nk, routes = self.num_kernels, []
-        for i in range(self.num_upsamples):
-            rbs = [self.resblocks[j] for j in range(i * nk, (i + 1) * nk)]
-            C_out = self.ups[i].bias.shape[0]
-            want_pair = (self.conv_pair and self.window_conv) if C_out >= 128 else (self.conv_pair_small and self.fused and C_out == 64)
-            if self.resblock2_fused and nk >= 2 and all(rb.kind == "2" and len(rb.dilation) == 2 and
-                                                        ops.hifi_resblock2_supported(C_out, rb.k, *rb.dilation) for rb in rbs):
-                routes.append("resblock2")
-            elif want_pair and nk >= 2 and all(rb.kind == "1" and all(ops.hifi_conv_pair_supported(C_out, rb.k, d) for d in rb.dilation) for rb in rbs):
-                routes.append("pair")
-            elif self.fused and nk >= 2 and all(rb.kind == "1" and ops.hifi_resblock1_supported(C_out, rb.k) for rb in rbs):
-                routes.append("fused")
-            else:
-                routes.append("gemm")
-        return routes
-
-    def _check_mrf(self):
-        """The conv-by-conv route averages exactly three ResBlocks per stage (ttsk_avg3): any other count is refused before a launch."""
-        if self.num_kernels != 3:
-            for i, r in enumerate(self.stage_routes()):
-                if r == "gemm":
-                    raise NotImplementedError("HiFi-GAN stage %d runs conv by conv, where the MRF average is written for 3 resblock kernels "
-                                              "per stage (got %d)" % (i, self.num_kernels))
-
-    def _short_rows_walk(self):
-        self._prepare()
-        return "gemm" not in self.stage_routes()
+        and the toggles on this object alone (`_plan`)."""
+        return ["fused" if st.route == "mrf32_post" else st.route for st in self._plan(refuse=False).stages]
 
     def plan(self, lens):
         """The window plan of a call on this generator: short utterances as rows of the batch where `short_rows()` allows."""
