@@ -529,6 +529,41 @@ int ttsk_resample_tile(int L, int M, int P);
 int ttsk_resample(const float* src, int64_t n_src, const int32_t* segs, int n_segs, const float* table, int L, int M, int P, int C,
                   void* dst, int64_t n_dst, int to_i16, float scale, void* stream);
 
+/* ------------------------------------------------------------------------------------ device-resident training set
+ * One launch builds one packed training batch (the buffer of tts_king_amd/dataset.py `packed_layout`: what the DeviceFeeder uploads
+ * for the same utterances) from a training set that lives on the device (tts_king_amd/resident.py).  The
+ * kernel is "gather ragged rows, zero-pad" over a table of at most TTSK_COLLATE_MAX_FIELDS fields; it knows nothing of the batch
+ * tuple.  A field is one flat device array holding every utterance's rows back to back (each row `inner` elements of `elem_size`
+ * bytes) plus two device tables indexed by utterance: `offsets` (int64, first ELEMENT of the utterance) and `lens` (int32, its rows).
+ * In the destination the field is (B, padded_rows, inner) at byte `dst_off`; a per-utterance scalar is a field with one row.
+ *   dst[dst_off + ((b * padded_rows + r) * inner + c) * elem_size ...] = src[offsets[u] + r * inner + c],  u = idx[b], r < lens[u]
+ * and every other byte of dst is written as zero: the rest of a padded row, the gap between a field's end and the next field (or
+ * limit, or dst_bytes), anything before the first field.  So the buffer's old content never survives and equal arguments give
+ * equal bytes.  nan_to_zero (elem_size 4 only): an fp32 NaN is written as +0.  Fields must be in ascending dst_off order, 16-byte
+ * aligned, not overlapping; dst 16-byte aligned, dst_bytes a multiple of 16 below 2^31.  Sources may be larger than 2^31 bytes.
+ * The limits of a shape-bucketed batch come by value and follow the fields: fl_off >= 0: int32 t_true at byte fl_off; pl_off >= 0:
+ * B int64 l_true from byte pl_off (fl before pl when both are present); < 0: absent.
+ * idx_dev: the batch's B utterance numbers on the device (a slice of an epoch's uploaded plan); idx_host and every field's
+ * lens_host are the host's copies of the same numbers, read here and never by the kernel.  Refused before the launch: an index
+ * outside [0, n_utts), a row count above padded_rows, an element size other than 4 or 8.  The kernel checks again what it reads
+ * from device memory (index, offset and length against n_utts / n_src / padded_rows) and writes zeros for a row that fails: wrong
+ * tables give a wrong batch, never a wild access.  16-byte loads where the source piece is 16-byte aligned and lies inside one
+ * utterance's rows (mel rows are 320 bytes: always, when utterances start 16-byte aligned), dword loads elsewhere; 16-byte stores
+ * everywhere, each byte of dst written exactly once. */
+#define TTSK_COLLATE_MAX_FIELDS 16
+typedef struct ttsk_collate_field {
+  const void* src;            /* device: the field's flat array */
+  const int64_t* offsets;     /* device: (n_utts) first element of each utterance */
+  const int32_t* lens;        /* device: (n_utts) rows of each utterance */
+  const int32_t* lens_host;   /* host:   the same lengths (argument checking only) */
+  int64_t n_src;              /* elements src holds */
+  int64_t dst_off;            /* byte offset of the field in dst */
+  int32_t elem_size, inner, padded_rows, nan_to_zero;
+} ttsk_collate_field;
+int ttsk_collate_batch(const ttsk_collate_field* fields, int n_fields, const int32_t* idx_dev, const int32_t* idx_host, int B,
+                       int64_t n_utts, void* dst, int64_t dst_bytes, int64_t fl_off, int32_t t_true, int64_t pl_off, int64_t l_true,
+                       void* stream);
+
 /* ------------------------------------------------------------------------------------ HiFi-GAN generator
  * reference: hifi/models.py:146-210 (Generator), :12-95 (ResBlock1), hifi/vocoder/utils.py:24-37.
  * 16-bit tensors of this family are bf16 (f16 = 0) or IEEE fp16 (f16 = 1; what hifigan.py uses: the generator is

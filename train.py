@@ -35,30 +35,36 @@ def validation_shard(n_items, batch_size, rank=0, world=1):
     return batches[rank::world]
 
 
-def evaluate(model, step, cfg, logger=None, train_val="val", vocoder=None, device=0, ctrl=None):
+def evaluate(model, step, cfg, logger=None, train_val="val", vocoder=None, device=0, ctrl=None, store=None):
     """reference: fs_two/evaluate.py:18-101 — teacher-forced forward in eval mode over `val.txt`, loss means weighted by
     batch size over len(dataset); returns the reference's message string (logger output is not reproduced).
     `ctrl` (parallel.ControlPlane of a multi-rank job): every rank evaluates its share of the reference's batches
     (`validation_shard`) and the weighted sums are added over the control-plane group — no rank waits for rank 0 to walk the whole
     set alone, and the wait for the slowest shard runs against the control plane's bound, not the gradient all-reduces' (VERDICT r05
-    item 11).  Every rank returns the same message."""
-    dataset = Dataset("%s.txt" % train_val, cfg.preprocess_config, cfg.train_config, sort=False, drop_last=False)
+    item 11).  Every rank returns the same message.
+    `store` (a tts_king_amd.resident.ResidentStore of the same metadata file; `mi355x.resident_data`): the same batches gathered on the
+    device from the resident set instead of loaded from disk — bit-identical inputs, the same message."""
     batch_size = cfg.train_config["optimizer"]["batch_size"]
     rank, world = (ctrl.rank, ctrl.world) if ctrl is not None else (0, 1)
-    loader = DataLoader(dataset, batch_sampler=validation_shard(len(dataset), batch_size, rank, world), collate_fn=dataset.collate_fn)
-    Loss = FastSpeech2Loss(cfg.preprocess_config, cfg.model_config)
     dev = model.device
+    if store is not None:
+        dataset = store
+        feed = store.batches(validation_shard(len(store), batch_size, rank, world))
+    else:
+        dataset = Dataset("%s.txt" % train_val, cfg.preprocess_config, cfg.train_config, sort=False, drop_last=False)
+        loader = DataLoader(dataset, batch_sampler=validation_shard(len(dataset), batch_size, rank, world), collate_fn=dataset.collate_fn)
+        feed = (batch for batchs in loader for batch in DeviceFeeder(batchs, dev))
+    Loss = FastSpeech2Loss(cfg.preprocess_config, cfg.model_config)
     was_training = model.training
     model.eval()
     loss_sums = [0.0 for _ in range(6)]
     with torch.no_grad():
-        for batchs in loader:
-            for batch in DeviceFeeder(batchs, dev):
-                output = model(*(batch[2:]))
-                losses = Loss(batch, output)
-                vals = torch.stack([l.reshape(-1)[0].float() for l in losses[1:]]).cpu().tolist()   # one host read per batch
-                for i, v in enumerate(vals):
-                    loss_sums[i] += v * len(batch[0])
+        for batch in feed:
+            output = model(*(batch[2:]))
+            losses = Loss(batch, output)
+            vals = torch.stack([l.reshape(-1)[0].float() for l in losses[1:]]).cpu().tolist()   # one host read per batch
+            for i, v in enumerate(vals):
+                loss_sums[i] += v * len(batch[0])
     model.train(was_training)
     if ctrl is not None:
         loss_sums = ctrl.all_reduce_sums(loss_sums)
@@ -89,7 +95,8 @@ def main(cfg, max_steps=None):
     What runs per step is tts_king_amd.engine.TrainEngine: batches padded to shape buckets on the host, one replayed hipGraph
     per shape (`mi355x.hip_graph`), and — under `python -m torch.distributed.run --nproc-per-node N train.py` — one process per
     GPU, each on its own shard of every epoch's shuffle, gradients all-reduced bucket by bucket over RCCL while backward runs
-    (tts_king_amd.parallel).  Losses are read from the device only when they are logged."""
+    (tts_king_amd.parallel).  Losses are read from the device only when they are logged.  `mi355x.resident_data: true` replaces the
+    DataLoader + DeviceFeeder chain by a training set kept on the device (tts_king_amd.resident): same batches, one kernel launch each."""
     from tts_king_amd.engine import TrainEngine
     from tts_king_amd.parallel import ControlPlane, GradReducer, init_distributed
     print("Prepare training ...")
@@ -106,8 +113,10 @@ def main(cfg, max_steps=None):
     if world > 1:       # every rank draws its own 1/N of each epoch's permutation (same seed on all ranks, disjoint indices)
         from torch.utils.data.distributed import DistributedSampler
         sampler = DistributedSampler(dataset, num_replicas=world, rank=rank, shuffle=True, seed=int(mi.get("seed", 1234)), drop_last=True)
-    loader = DataLoader(dataset, batch_size=batch_size * group_size, shuffle=sampler is None, sampler=sampler,
-                        collate_fn=dataset.collate_fn, num_workers=workers)
+    resident = bool(mi.get("resident_data", False)) if mi else False
+    if not resident:
+        loader = DataLoader(dataset, batch_size=batch_size * group_size, shuffle=sampler is None, sampler=sampler,
+                            collate_fn=dataset.collate_fn, num_workers=workers)
     model, optimizer = get_model(cfg, device, train=True)
     Loss = FastSpeech2Loss(cfg.preprocess_config, cfg.model_config)
     reducer = None
@@ -145,34 +154,55 @@ def main(cfg, max_steps=None):
     grad_acc = cfg.train_config["optimizer"]["grad_acc_step"]
     epoch = 1
     model.engine = engine
+    val_store = None
+    if resident:
+        # mi355x.resident_data: the whole training set (and val.txt) loaded once and kept on the device, batches gathered there by one
+        # kernel launch each (tts_king_amd/resident.py) — same sampler, same groups, same sort, same packed batch as the loader route.
+        # Every rank holds the full set: the shuffle spans all of it every epoch.
+        from torch.utils.data import RandomSampler
+        from tts_king_amd.resident import ResidentLoader, ResidentStore
+        max_gb = float(mi.get("resident_max_gb", 32))
+        store = ResidentStore("train.txt", cfg.preprocess_config, cfg.train_config, model.device, max_gb=max_gb)
+        val_store = ResidentStore("val.txt", cfg.preprocess_config, cfg.train_config, model.device, max_gb=max_gb)
+        if rank == 0:
+            print("Resident training set: %d utterances, %.1f MB on the device" % (len(store), store.nbytes / 2.0 ** 20))
+        loader = ResidentLoader(store, batch_size, group_size, sort=True, drop_last=True,
+                                sampler=sampler if sampler is not None else RandomSampler(store), bucket=bucket)
+
+    def epoch_batches():
+        if resident:
+            yield from loader
+        else:
+            for batchs in loader:
+                yield from DeviceFeeder(batchs, model.device, bucket=bucket)
+
     while True:
         if sampler is not None:
             sampler.set_epoch(epoch)
-        for batchs in loader:
-            for batch in DeviceFeeder(batchs, model.device, bucket=bucket):
-                losses, output = engine.step(batch, step)
-                if rank == 0 and step % st["log_step"] == 0:
-                    engine.wait()                                                     # (bounded when replayed collectives are outstanding)
-                    vals = [v / grad_acc for v in losses.cpu().tolist()[1:5]]         # the loop's only host read
-                    print("Step {}/{}, Total Loss: {:.4f}, Mel Loss: {:.4f}, Pitch Loss: {:.4f}, Energy Loss: {:.4f}, "
-                          "Duration Loss: {:.4f}".format(step, total_step, sum(vals), *vals))
-                # Validation and checkpoint: no rank may run ahead into the next step's gradient all-reduce while another is still busy
-                # here (that wait would run against the data-path bound and abort the job).  Every rank validates its share of the
-                # batches; rank 0 alone writes the checkpoint while the others wait at the control plane's barrier.
-                if step % st["val_step"] == 0:
-                    engine.wait()
-                    msg = evaluate(model, step, cfg, None, "val", None, device, ctrl=ctrl if world > 1 else None)
-                    if rank == 0:
-                        print(msg)
-                if step % st["save_step"] == 0:
-                    engine.wait()
-                    if rank == 0:
-                        save_checkpoint(model, optimizer, os.path.join(cfg.train_config["path"]["ckpt_path"], "{}.pth.tar".format(step)))
-                    ctrl.barrier()
-                if step == total_step:
-                    engine.wait()
-                    return model, optimizer
-                step += 1
+        for batch in epoch_batches():
+            losses, output = engine.step(batch, step)
+            if rank == 0 and step % st["log_step"] == 0:
+                engine.wait()                                                     # (bounded when replayed collectives are outstanding)
+                vals = [v / grad_acc for v in losses.cpu().tolist()[1:5]]         # the loop's only host read
+                print("Step {}/{}, Total Loss: {:.4f}, Mel Loss: {:.4f}, Pitch Loss: {:.4f}, Energy Loss: {:.4f}, "
+                      "Duration Loss: {:.4f}".format(step, total_step, sum(vals), *vals))
+            # Validation and checkpoint: no rank may run ahead into the next step's gradient all-reduce while another is still busy
+            # here (that wait would run against the data-path bound and abort the job).  Every rank validates its share of the
+            # batches; rank 0 alone writes the checkpoint while the others wait at the control plane's barrier.
+            if step % st["val_step"] == 0:
+                engine.wait()
+                msg = evaluate(model, step, cfg, None, "val", None, device, ctrl=ctrl if world > 1 else None, store=val_store)
+                if rank == 0:
+                    print(msg)
+            if step % st["save_step"] == 0:
+                engine.wait()
+                if rank == 0:
+                    save_checkpoint(model, optimizer, os.path.join(cfg.train_config["path"]["ckpt_path"], "{}.pth.tar".format(step)))
+                ctrl.barrier()
+            if step == total_step:
+                engine.wait()
+                return model, optimizer
+            step += 1
         epoch += 1
 
 

@@ -84,6 +84,12 @@ class AdamItem(C.Structure):
                 ("tile0", C.c_int32)]
 
 
+class CollateField(C.Structure):
+    """Mirror of `ttsk_collate_field` (include/ttsk.h)."""
+    _fields_ = [("src", C.c_void_p), ("offsets", C.c_void_p), ("lens", C.c_void_p), ("lens_host", C.c_void_p), ("n_src", C.c_int64),
+                ("dst_off", C.c_int64), ("elem_size", C.c_int32), ("inner", C.c_int32), ("padded_rows", C.c_int32), ("nan_to_zero", C.c_int32)]
+
+
 # flags (include/ttsk.h)
 A_TR, B_TR, C_F32, RELU, ADD_R, R_F32, MASK_G, LRELU_IN, TANH, ACCUM_C, LRELU_OUT, F16, C2_LRELU, DEFER_REDUCE, RAW_SLABS = [1 << i for i in range(15)]
 
@@ -165,6 +171,7 @@ def load(path=LIB_PATH):
     lib.ttsk_gemm_reduce_batch.argtypes = [C.POINTER(ReduceItem), C.c_int, C.c_void_p]
     lib.ttsk_dwconv_batch.argtypes = [C.POINTER(DwConvItem), C.c_int, C.c_void_p]
     lib.ttsk_dwgemm_batch.argtypes = [C.POINTER(DwGemmItem), C.c_int, C.c_int, C.c_void_p]
+    lib.ttsk_collate_batch.argtypes = [C.POINTER(CollateField)] + lib.ttsk_collate_batch.argtypes[1:]
     lib.ttsk_gemm_plan.argtypes = [C.POINTER(GemmDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     _lib = lib
     return lib

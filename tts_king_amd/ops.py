@@ -1320,6 +1320,25 @@ def resample(x_flat, segs, filt, out=None, int16_scale=None):
     return out
 
 
+def collate_batch(table, n_fields, idx_dev, idx_host, n_utts, out, fl_off=-1, t_true=0, pl_off=-1, l_true=0):
+    """One packed training batch gathered from a device-resident set (tts_king_amd/resident.py): `table` = a `lib.CollateField` array of
+    `n_fields` rows (include/ttsk.h: where each field's flat array and per-utterance offset / length tables live, and where the field
+    goes in `out`); idx_dev: contiguous int32 device tensor of the batch's utterance numbers, idx_host: the same as a contiguous int32
+    numpy array (checked on the host together with the fields' host-side lengths: an index outside the store or a row longer than
+    its padded length is refused, nothing is launched); out: contiguous uint8 device buffer with the feeder's layout, every byte of
+    which is written.  fl_off / pl_off >= 0: the int32 frame limit `t_true` / the B int64 phoneme limits `l_true` at those bytes."""
+    _dev(idx_dev, out)
+    B = idx_dev.numel()
+    if (idx_dev.dtype != torch.int32 or not idx_dev.is_contiguous() or out.dtype != torch.uint8 or not out.is_contiguous() or
+            idx_host.dtype.str != "<i4" or not idx_host.flags["C_CONTIGUOUS"] or idx_host.size != B):
+        raise L.TtskError("collate_batch: needs contiguous int32 indices (device tensor and numpy array of the same %d entries) and a "
+                          "contiguous uint8 batch buffer" % B)
+    _count("collate_batch")
+    check(L.load().ttsk_collate_batch(table, n_fields, _ptr(idx_dev), idx_host.ctypes.data, B, int(n_utts), _ptr(out), out.numel(), int(fl_off),
+                                      int(t_true), int(pl_off), int(l_true), _stream()), "ttsk_collate_batch")
+    return out
+
+
 def resample_tile(filt):
     """Samples of the destination one workgroup of `resample` serves for this filter (host only; segments need no alignment to it)."""
     return int(L.load().ttsk_resample_tile(filt.L, filt.M, filt.P))
