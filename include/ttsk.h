@@ -946,6 +946,29 @@ int ttsk_pitch_yin(const float* wav, const int32_t* lens, int B, int ld, int hop
 int ttsk_phoneme_prosody(const float* f0, const float* energy, int ldT, const int32_t* dur, int ldL, const int32_t* T, const int32_t* Lp,
                          int B, float* pitch, float* energy_ph, float* pitch_mean, float* pitch_std, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------- forced alignment: dynamic time warping
+ * One launch aligns B pairs of feature sequences.
+ *   x (B, ldx, C) fp32 and y (B, ldy, C) fp32, contiguous; x_lens, y_lens int32[B] or null (every row is full).  Tx, Ty are the
+ *   lengths clamped to [0, ld]; rows at or past a pair's length are never read.
+ *   Local cost: D(i, j) = sum_c (x[i, c] - y[j, c])^2 in fp32.
+ *   Cumulative cost: A(0, 0) = D(0, 0); A(i, j) = D(i, j) + min over the predecessors that exist, taken in the order (i-1, j-1),
+ *   (i-1, j), (i, j-1): a later candidate replaces an earlier one only if it is strictly smaller (on a tie the earliest wins).
+ *   Path: walked back from (Tx-1, Ty-1) to (0, 0) along the chosen predecessors.
+ *   Outputs: path_x (B, ldy) int32: for j < Ty the largest i with (i, j) on the path, -1 from Ty on; cost[B] fp32 = A(Tx-1, Ty-1);
+ *   status[B] int32.
+ *   Durations, written when both x_seg and dur are given: x_seg (B, ldL) int32 are the frames of x per phoneme, n_seg int32[B] the
+ *   phonemes per row (null: ldL); dur (B, ldL) int32: dur[b, l] = the number of j < Ty whose path_x[j] lies in phoneme l's span of
+ *   x.  A phoneme with x_seg = 0 gets 0, entries from n_seg[b] on are 0, and sum_l dur = Ty.
+ *   status: 0 good; 2: Tx < 1 or Ty < 1 (path_x = -1, dur = 0, cost = +inf); 3: x_seg has a negative entry or does not sum to Tx
+ *   (dur = 0; path_x and cost are written as usual).  A non-finite cost is left for the caller to judge.
+ *   Limits, refused before any launch: 1 <= C <= 128; 1 <= ldx, ldy <= 2048; 1 <= ldL <= 1024; 0 <= B <= 65535 (B = 0 launches
+ *   nothing).  workspace: ttsk_dtw_workspace_bytes(B, ldx, ldy) bytes, 16-byte aligned (the local costs and one byte of
+ *   back-pointer per cell, both skewed by anti-diagonal); -1 for sizes outside the limits. */
+int64_t ttsk_dtw_workspace_bytes(int B, int ldx, int ldy);
+int ttsk_dtw_align(const float* x, const float* y, const int32_t* x_lens, const int32_t* y_lens, int B, int ldx, int ldy, int C,
+                   const int32_t* x_seg, const int32_t* n_seg, int ldL, void* workspace, int64_t workspace_bytes, int32_t* path_x,
+                   float* cost, int32_t* status, int32_t* dur, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,17 +72,7 @@ class TTSKing:
             wav = self.vocoder(mels.transpose(1, 2), sample_rate=sample_rate)
         return (wav, prosody) if return_prosody else wav
 
-    def extract_prosody(self, wav, durations, sample_rate=22050):
-        """A recording's per-phoneme prosody in the form `speak` / `generate_mel` take: {"durations", "pitch", "energy"}, one
-        value per phoneme.  `wav`: 1-D samples (numpy or torch, any scale) at `sample_rate` Hz covering exactly the aligned speech;
-        `durations`: frames per phoneme (e.g. `textgrid.get_alignment`).  The recording goes through the data-preparation stages
-        (tts_king_amd/preprocess.py: resample to the model's rate, peak-normalise, energy from `TacotronSTFT`, F0 from
-        `PitchExtractor` (YIN), the phoneme-level reduction on the device), then `(x - mean) / std` with the pitch and energy mean
-        and std of the model's stats.json: exactly what the normalisation pass writes into the training targets.  Those are the
-        units of `pitch=` and `energy=` (DESIGN.md section 14: a set value is used as is, `scaled[l] = value[l]`, and bucketed
-        against the stats.json range), so `speak(text, **tts.extract_prosody(wav, durations))` reproduces the recording's prosody.
-        Raises ValueError when the recording has no usable pitch (fewer than two voiced frames, constant pitch) or fewer frames
-        than the durations ask for."""
+    def _device_features(self):
         import json
         import os
         from tts_king_amd import preprocess
@@ -90,9 +80,45 @@ class TTSKing:
             self._features = preprocess.Features(self.cfg.preprocess_config, self.cfg.gpu)
             with open(os.path.join(self.cfg.preprocess_config.path.preprocessed_path, "stats.json")) as f:
                 self._stats = json.load(f)
+        return self._features
+
+    def align(self, wav, text, speaker=0, sample_rate=22050, return_mels=False):
+        """A recording's frames per phoneme from the recording and its transcript alone (tts_king_amd/align.py, DESIGN.md section
+        19): the transcript is synthesized at the recording's frame count and the two mels are aligned by dynamic time warping on
+        the device.  `wav`: 1-D samples at `sample_rate` Hz; `text`: anything `generate_mel` takes.  -> {"durations" (one integer
+        per phoneme, summing to "frames"), "phonemes", "cost_per_frame", "frames"}.  The recording is taken whole: silence at its
+        ends lands in the first and last phoneme."""
+        from tts_king_amd.align import Aligner
+        if not hasattr(self, "_aligner"):
+            self._aligner = Aligner(self.tts, self.cfg.preprocess_config, self.cfg.gpu, features=self._device_features())
+        phonemes = text if isinstance(text, np.ndarray) else self.text_preprocess(text)
+        name = self.speakers[speaker] if isinstance(speaker, (int, np.integer)) else speaker
+        return self._aligner.align([wav], [phonemes], [name], [sample_rate], return_mels=return_mels)[0]
+
+    def extract_prosody(self, wav, durations=None, sample_rate=22050, *, text=None, speaker=0):
+        """A recording's per-phoneme prosody in the form `speak` / `generate_mel` take: {"durations", "pitch", "energy"}, one
+        value per phoneme.  `wav`: 1-D samples (numpy or torch, any scale) at `sample_rate` Hz covering exactly the aligned speech;
+        `durations`: frames per phoneme (e.g. `textgrid.get_alignment`), or None with `text` (and `speaker`) given: the durations
+        then come from `align(wav, text, speaker, sample_rate)`, so that `speak(text, **tts.extract_prosody(wav, text=text))` copies
+        a recording's prosody from the recording and its transcript alone.  Exactly one of `durations` and `text` must be given.
+        The recording goes through the data-preparation stages
+        (tts_king_amd/preprocess.py: resample to the model's rate, peak-normalise, energy from `TacotronSTFT`, F0 from
+        `PitchExtractor` (YIN), the phoneme-level reduction on the device), then `(x - mean) / std` with the pitch and energy mean
+        and std of the model's stats.json: exactly what the normalisation pass writes into the training targets.  Those are the
+        units of `pitch=` and `energy=` (DESIGN.md section 14: a set value is used as is, `scaled[l] = value[l]`, and bucketed
+        against the stats.json range), so `speak(text, **tts.extract_prosody(wav, durations))` reproduces the recording's prosody.
+        Raises ValueError when the recording has no usable pitch (fewer than two voiced frames, constant pitch) or fewer frames
+        than the durations ask for."""
+        from tts_king_amd import preprocess
+        if (durations is None) == (text is None):
+            raise ValueError("extract_prosody: give exactly one of `durations` (frames per phoneme) and `text` (the transcript, aligned "
+                             "to the recording by `align`); got %s" % ("neither" if durations is None else "both"))
+        self._device_features()
         if torch.is_tensor(wav):
             wav = wav.detach().cpu().numpy()
         wav = np.asarray(wav).reshape(-1)
+        if durations is None:
+            durations = self.align(wav, text, speaker=speaker, sample_rate=sample_rate)["durations"]
         durations = np.asarray(durations).reshape(-1).astype(np.int64)
         y = self._features.prepare(wav, int(sample_rate), "extract_prosody")
         _, energy, f0 = self._features.frame_level(y)

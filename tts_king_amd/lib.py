@@ -159,7 +159,7 @@ def load(path=LIB_PATH):
     lib.ttsk_last_error.restype = C.c_char_p
     for name, argtypes in declared_prototypes().items():
         fn = getattr(lib, name)
-        if name in ("ttsk_resblock_pack_elems", "ttsk_dwgemm_workspace_floats"):
+        if name in ("ttsk_resblock_pack_elems", "ttsk_dwgemm_workspace_floats", "ttsk_dtw_workspace_bytes"):
             fn.restype = C.c_int64
         elif name != "ttsk_last_error":
             fn.restype = C.c_int

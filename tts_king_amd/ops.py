@@ -2145,3 +2145,50 @@ def phoneme_prosody(f0, energy, dur, T, Lp):
     check(L.load().ttsk_phoneme_prosody(_ptr(f0), _ptr(energy), ldT, _ptr(dur), ldL, _ptr(T), _ptr(Lp), Bsz, _ptr(pitch), _ptr(en),
                                         _ptr(pmean), _ptr(pstd), _ptr(status), _stream()), "ttsk_phoneme_prosody")
     return pitch, en, pmean, pstd, status
+
+
+DTW_MAX_C, DTW_MAX_T, DTW_MAX_L = 128, 2048, 1024      # ttsk_dtw_align's limits
+
+
+def dtw_align(x, y, x_lens=None, y_lens=None, x_seg=None, n_seg=None):
+    """x (B, ldx, C), y (B, ldy, C) fp32; x_lens, y_lens (B,) int32 or None (full rows) -> (path_x (B, ldy) int32, cost (B,) fp32,
+    status (B,) int32): the dynamic-time-warping path of every pair (include/ttsk.h): path_x[b, j] is the last row of x matched to
+    row j of y (-1 from y_lens[b] on), cost the cumulative squared distance along the path.  With x_seg (B, ldL) int32, the rows of x
+    per phoneme (n_seg (B,) int32 phonemes per row, None: ldL), also dur (B, ldL) int32: the rows of y per phoneme.  status 0: good;
+    2: an empty sequence; 3: x_seg is negative somewhere or does not sum to x_lens.  The workspace is allocated here."""
+    for name, v in (("x", x), ("y", y)):
+        if v.dim() != 3 or v.dtype != torch.float32 or not v.is_contiguous():
+            raise L.TtskError("dtw_align: %s must be a contiguous (B, frames, C) fp32 tensor" % name)
+    Bsz, ldx, Cc = x.shape
+    if y.shape[0] != Bsz or y.shape[2] != Cc:
+        raise L.TtskError("dtw_align: y is %s, x is %s: batch and channels must agree" % (tuple(y.shape), tuple(x.shape)))
+    ldy = y.shape[1]
+    if not 1 <= Cc <= DTW_MAX_C:
+        raise L.TtskError("dtw_align: C = %d channels, 1..%d are taken" % (Cc, DTW_MAX_C))
+    for name, ld in (("x", ldx), ("y", ldy)):
+        if not 1 <= ld <= DTW_MAX_T:
+            raise L.TtskError("dtw_align: %s has %d frames per row, 1..%d are taken" % (name, ld, DTW_MAX_T))
+    for name, v in (("x_lens", x_lens), ("y_lens", y_lens), ("n_seg", n_seg)):
+        if v is not None and (v.dtype != torch.int32 or v.dim() != 1 or v.numel() != Bsz or not v.is_contiguous()):
+            raise L.TtskError("dtw_align: %s must be a contiguous int32 tensor of %d entries" % (name, Bsz))
+    ldL = 0
+    if x_seg is not None:
+        if x_seg.dim() != 2 or x_seg.shape[0] != Bsz or x_seg.dtype != torch.int32 or not x_seg.is_contiguous():
+            raise L.TtskError("dtw_align: x_seg must be a contiguous (B, phonemes) int32 tensor")
+        ldL = x_seg.shape[1]
+        if not 1 <= ldL <= DTW_MAX_L:
+            raise L.TtskError("dtw_align: x_seg has %d phonemes per row, 1..%d are taken" % (ldL, DTW_MAX_L))
+    elif n_seg is not None:
+        raise L.TtskError("dtw_align: n_seg without x_seg")
+    _dev(x, y, x_lens, y_lens, x_seg, n_seg)
+    lib = L.load()
+    path_x = torch.empty(Bsz, ldy, dtype=torch.int32, device=x.device)
+    cost = torch.empty(Bsz, dtype=torch.float32, device=x.device)
+    status = torch.empty(Bsz, dtype=torch.int32, device=x.device)
+    dur = torch.empty(Bsz, ldL, dtype=torch.int32, device=x.device) if x_seg is not None else None
+    nbytes = int(lib.ttsk_dtw_workspace_bytes(Bsz, ldx, ldy))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    _count("dtw_align")
+    check(lib.ttsk_dtw_align(_ptr(x), _ptr(y), _ptr(x_lens), _ptr(y_lens), Bsz, ldx, ldy, Cc, _ptr(x_seg), _ptr(n_seg), ldL, _ptr(ws), nbytes,
+                             _ptr(path_x), _ptr(cost), _ptr(status), _ptr(dur), _stream()), "ttsk_dtw_align")
+    return (path_x, cost, status) if dur is None else (path_x, cost, status, dur)

@@ -152,9 +152,34 @@ class Features:
         return int(st[0]), p[0].cpu().numpy(), e[0].cpu().numpy(), float(pm[0]), float(ps[0])
 
 
+def lab_phonemes(line, g2p=None):
+    """The phoneme-id sequence of a `.lab` line: the line itself when it is in the frontend's "{R A B O0 T ...}" notation, else
+    `g2p(line)` (a callable returning the ids), else None."""
+    from .text import text_to_sequence
+    line = line.strip()
+    if line.startswith("{") and line.endswith("}"):
+        return np.asarray(text_to_sequence(line, []), dtype=np.int64)
+    if g2p is not None:
+        return np.asarray(g2p(line), dtype=np.int64).reshape(-1)
+    return None
+
+
+def align_speaker(speaker, known, new_speaker_init=None):
+    """The model's speaker an utterance of folder `speaker` is synthesized with for alignment: the folder's name when the model
+    knows it, else `mi355x.new_speaker_init` when set, else the model's first speaker."""
+    if speaker in known:
+        return speaker
+    return new_speaker_init if new_speaker_init is not None else known[0]
+
+
 class Preprocessor:
-    def __init__(self, config, use_cwt=None, device="cuda:0", seed=1234):
+    def __init__(self, config, use_cwt=None, device="cuda:0", seed=1234, aligner=None, g2p=None, align_max_cost=None, new_speaker_init=None):
+        """`aligner` (an `align.Aligner`): an utterance without a `.TextGrid` is then aligned on the device instead of being
+        skipped: its phonemes are `lab_phonemes(.lab line, g2p)`, its durations the aligner's over the whole recording (no cut)
+        with `align_speaker(folder name, ...)`; one whose cost per frame exceeds `align_max_cost` (`mi355x.align_max_cost`;
+        None: no limit) is skipped with that reason."""
         self.config = config
+        self.aligner, self.g2p, self.align_max_cost, self.new_speaker_init = aligner, g2p, align_max_cost, new_speaker_init
         self.in_dir = config["path"]["raw_path"]
         self.out_dir = config["path"]["preprocessed_path"]
         pp = config["preprocessing"]
@@ -190,10 +215,13 @@ class Preprocessor:
                 if not wav_name.endswith(".wav"):
                     continue
                 basename = wav_name[:-4]
-                if not os.path.exists(os.path.join(self.in_dir, speaker, basename + ".TextGrid")):
+                if os.path.exists(os.path.join(self.in_dir, speaker, basename + ".TextGrid")):
+                    ret = self.process_utterance(speaker, basename)
+                elif self.aligner is not None:
+                    ret = self.process_unaligned(speaker, basename)
+                else:
                     self.skipped.append((speaker, basename, "no TextGrid"))
                     continue
-                ret = self.process_utterance(speaker, basename)
                 if ret is None:
                     continue
                 info, pitch, energy, n = ret
@@ -241,6 +269,27 @@ class Preprocessor:
         n = int(sum(duration))
         if len(wav) < 2 or n < 1:
             return self._skip(speaker, basename, "nothing left after the cut")
+        return self._write_utterance(speaker, basename, wav, duration, text, raw_text)
+
+    def process_unaligned(self, speaker, basename):
+        """An utterance without a `.TextGrid`: phonemes from the `.lab` line, durations from the aligner over the whole recording."""
+        from .text import sequence_to_text
+        base = os.path.join(self.in_dir, speaker, basename)
+        with open(base + ".lab", "r", encoding="utf-8") as f:
+            raw_text = f.readline().strip("\n")
+        ids = lab_phonemes(raw_text, self.g2p)
+        if ids is None or len(ids) < 1:
+            return self._skip(speaker, basename, "no TextGrid and no phonemes")
+        rate, samples = read_wav(base + ".wav")
+        name = align_speaker(speaker, self.aligner.tts.speaker_names, self.new_speaker_init)
+        got = self.aligner.align([samples], [ids], [name], [rate])[0]
+        if self.align_max_cost is not None and got["cost_per_frame"] > float(self.align_max_cost):
+            return self._skip(speaker, basename, "alignment cost per frame %.6g exceeds align_max_cost %.6g" % (got["cost_per_frame"], float(self.align_max_cost)))
+        wav = self.features.prepare(samples, rate, base + ".wav")
+        return self._write_utterance(speaker, basename, wav, got["durations"].tolist(), sequence_to_text(ids.tolist()), raw_text)
+
+    def _write_utterance(self, speaker, basename, wav, duration, text, raw_text):
+        n = int(sum(duration))
         mel, energy, f0 = self.features.frame_level(wav)
         status, pitch, energy_ph, pitch_mean, pitch_std = self.features.phoneme_level(f0, energy, duration)
         if status:
