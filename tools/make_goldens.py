@@ -374,7 +374,45 @@ def g11_mel():
     print("G11 mel", tuple(mel_hifi.shape), tuple(mel_taco.shape), float(mel_hifi.min()), float(mel_hifi.max()))
 
 
+def g14_fs2_configs():
+    """g1_eval_teacher_forced for every configuration of tests/fs2_configs.py: the reference model built with that configuration,
+    its state-dict keys / shapes / dtypes, seeded weights, eval teacher-forced at B = 2 on the configuration's golden batch; inputs
+    and outputs (mel, postnet mel, the three predictions) in tests/golden/fs2_cfg_<name>.npz."""
+    from tests import fs2_configs as FC
+
+    def plain(d):
+        return {k: plain(v) if isinstance(v, dict) else (list(v) if isinstance(v, list) else v) for k, v in d.items()}
+    for name in FC.CONFIGS:
+        c = AD(FC.config({"model_config": plain(cfg.model_config), "preprocess_config": plain(cfg.preprocess_config)}, name))
+        torch.manual_seed(0)
+        m = FastSpeech2(c.preprocess_config, c.model_config, N_SPK)
+        n_mel = FC.n_mel_of(c)
+        if n_mel != 80:
+            # the reference's model builds `PostNet()` at that class's default of 80 channels whatever the configuration says
+            # (model/fastspeech2.py:41), while its mel_linear follows the configuration (:28): for another width the one module is
+            # rebuilt with the reference's own class and its own argument (Layers.py:76-82)
+            from fs_two.transformer.Layers import PostNet
+            m.postnet = PostNet(n_mel_channels=n_mel)
+        sd = m.state_dict()
+        seeded_fill(sd, WEIGHT_SEED)
+        m.eval()
+        b = FC.golden_batch(c, name)
+        with torch.no_grad():
+            o = m(*b[2:])
+        path = os.path.join(OUT, "fs2_cfg_%s.npz" % name)
+        np.savez_compressed(path, weight_seed=WEIGHT_SEED, keys=np.array(list(sd.keys())),
+                            shapes=np.array([";".join(map(str, v.shape)) for v in sd.values()]),
+                            dtypes=np.array([str(v.dtype) for v in sd.values()]),
+                            speakers=npy(b[2]), texts=npy(b[3]), src_lens=npy(b[4]), mels=npy(b[6]), mel_lens=npy(b[7]),
+                            energies=npy(b[9]), durations=npy(b[10]), pitches=npy(b[11]),
+                            mel=npy(o[0]), pitch=npy(o[1]), energy=npy(o[2]), logd=npy(o[3]), out_mel_lens=npy(o[8]), post=npy(o[9]))
+        print("G14 %s mel" % name, tuple(o[0].shape), "absmax", float(o[0].abs().max()), "keys", len(sd), os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "fs2_configs":
+        g14_fs2_configs()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "mel":
         g11_mel()
         sys.exit(0)
@@ -402,3 +440,4 @@ if __name__ == "__main__":
     g11_mel()
     g12_hifigan_v3()
     g13_hifigan_v2()
+    g14_fs2_configs()

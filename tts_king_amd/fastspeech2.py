@@ -132,8 +132,8 @@ class FastSpeech2(nn.Module):
         self.max_seq_len = model_config["max_seq_len"]
         self.n_mel = preprocess_config["preprocessing"]["mel"]["n_mel_channels"]
         self.n_speakers = n_speakers
-        assert self.d == 256 or self.d % 256 == 0, "LayerNorm kernel handles D in {256,512,768,1024}"
 
+        # (raises params.ConfigError, naming the key, for every configuration the kernels have no instance for: params.validate_config)
         entries = P.build_entries(model_config, self.n_mel, n_speakers, N_VOCAB)
         self._table, self._n_flat = P.layout(entries)
         self._flat = torch.zeros(self._n_flat, dtype=torch.float32, device=device)
@@ -219,7 +219,6 @@ class FastSpeech2(nn.Module):
                    "flat_two.net.0.bias", "flat_two.net.2.weight", "flat_two.net.2.bias", "linear.weight", "linear.bias")]
             assert tuple(h - hm[0] for h in hm) == ops.CNNSCALAR_OFFSETS, "CNNscalar block layout (include/ttsk.h)"
             assert self._table[va + "pitch_std.flat_one.net.0.weight"].offset - hm[0] == ops.CNNSCALAR_FLOATS
-            assert self.d == 256 and model_config["variance_predictor"]["filter_size"] == 256, "the CWT kernels handle 256 channels"
         else:
             assert o[2] - o[1] == self._pred_stride and self._pred_stride % 8 == 0
         if self.window_ffn and self._shadow.is_cuda:
@@ -671,8 +670,11 @@ class FastSpeech2(nn.Module):
         # (6) FFN: Conv1d(k=9)+ReLU, Conv1d(k=1), dropout, +residual, LayerNorm, zero PAD rows: SubLayers.py:96-99, Layers.py:32
         W1 = self._w(f + "w_1.weight")
         pk = self._pack("w1", f + "w_1.weight")
-        if pk is not None and x1.dtype == bf16:
+        if pk is not None and x1.dtype == bf16 and d == 256:
             h = ops.ffn_conv_fwd(x1.view(Bn, S, d), W1, self._m(f + "w_1.bias"), relu=True, packed=pk)      # window kernel (csrc/ffn_conv.hip)
+        elif pk is not None and x1.dtype == bf16:
+            # d = 512: ttsk_ffn_conv_fwd is the 256-channel entry point; the same pack runs on the window kernel's 512-channel instance
+            h = ops.win_conv(x1.view(Bn, S, d), pk, W1.shape[0], self.k1, bias=self._m(f + "w_1.bias"), relu=True)
         else:
             h = ops.conv1d(x1.view(Bn, S, d), W1, self._m(f + "w_1.bias"), flags=ops.RELU)
         if fuse and self.k2 == 1:

@@ -1007,6 +1007,12 @@ def colsum_into(x, dst, accumulate=True, defer=None):
     """dst[C] (+)= column sums of x (rows, C) — bias gradients."""
     _dev(x, dst)
     rows, Cn = x.shape
+    if Cn > 1024:
+        # ttsk_colsum sums at most 1024 columns per pass (a hidden size of 512: the q|k|v bias gradient has 1536): column slices of
+        # the same rows, each a column sum of its own (1024 columns keep a slice's rows 16-byte aligned)
+        for c0 in range(0, Cn, 1024):
+            colsum_into(x[:, c0:c0 + 1024], dst[c0:c0 + 1024], accumulate=accumulate, defer=defer)
+        return dst
     lib = L.load()
     nblk = lib.ttsk_colsum_nblocks(rows)
     partials = _f32(nblk, Cn, device=x.device)

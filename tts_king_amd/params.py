@@ -78,12 +78,76 @@ def _cnn_scalar(pre, size_one, size_two, reduce=30, kind=UNUSED):
     return out
 
 
+class ConfigError(ValueError):
+    """A model / preprocess configuration the kernels have no instance for: names the key, its value and the accepted values."""
+
+    def __init__(self, key, value, accepted):
+        self.key, self.value, self.accepted = key, value, accepted
+        super().__init__("%s = %r is not supported; accepted: %s" % (key, value, accepted))
+
+
+FILTER_SIZES = (256, 512, 768, 1024)       # csrc/layernorm.hip: D = 256..1024 in steps of 256
+# ... and of those the block widths whose every launch has an instance: at 768 / 1024 the q|k|v input gradient (a contraction over
+# 3 d channels) would be 9 / 12 slabs of ttsk_win_conv_split, which takes at most 8, and no test runs the rest of their route
+HIDDEN_SIZES = (256, 512)
+MAX_KERNEL_SIZE = 15                       # csrc/dwgemm.hip: odd tap counts up to 15 (the window kernel: up to 9, else the implicit GEMM)
+MAX_FILTER_SIZE = 1024                     # csrc/layernorm.hip: a bias gradient's column sum holds at most 1024 columns per pass
+
+
+def validate_config(model_config, n_mel):
+    """Refuse, by key, what the kernel entry points would refuse at the first forward or backward (each limit is the TTSK_REQUIRE
+    or `*_supported` it cites).  Called by build_entries, so FastSpeech2.__init__ raises before it allocates anything."""
+    tr, vp = model_config["transformer"], model_config["variance_predictor"]
+    d = tr["encoder_hidden"]
+    if d not in HIDDEN_SIZES:              # ttsk_layernorm_fwd / _bwd: "D must be 256..1024 step 256"; ttsk_win_conv_split: nsplit <= 8
+        raise ConfigError("transformer.encoder_hidden", d, "one of %s" % (HIDDEN_SIZES,))
+    for key in ("decoder_hidden", "variance_hidden"):      # one residual width from the embedding to mel_linear: no projection between the stacks
+        if tr[key] != d:
+            raise ConfigError("transformer." + key, tr[key], "the value of transformer.encoder_hidden (%d)" % d)
+    for key in ("encoder_head", "decoder_head"):
+        # the scores / P V GEMMs step from head to head by d_k elements: ttsk_gemm wants batch strides in multiples of 8
+        h = tr[key]
+        if not (isinstance(h, int) and h >= 1 and d % h == 0 and (d // h) % 8 == 0):
+            raise ConfigError("transformer." + key, h, "a divisor of the hidden size %d that leaves a head size in multiples of 8 "
+                              "(head size 128 runs flash attention, every other one the softmax route)" % d)
+    for key in ("encoder_layer", "decoder_layer"):
+        if not (isinstance(tr[key], int) and tr[key] >= 1):
+            raise ConfigError("transformer." + key, tr[key], "an integer >= 1")
+    ks = list(tr["conv_kernel_size"])
+    if len(ks) != 2 or any((not isinstance(k, int)) or k < 1 or k % 2 == 0 or k > MAX_KERNEL_SIZE for k in ks):
+        # "same" padding (k - 1) / 2 on both sides: SubLayers.py:82-93; an even k changes the sequence length in the reference itself
+        raise ConfigError("transformer.conv_kernel_size", ks, "two odd kernel sizes in 1..%d" % MAX_KERNEL_SIZE)
+    ff = tr["conv_filter_size"]
+    if not (isinstance(ff, int) and 8 <= ff <= MAX_FILTER_SIZE and ff % 8 == 0):      # ttsk_gemm: 16-byte rows; ttsk_colsum: C <= 1024
+        raise ConfigError("transformer.conv_filter_size", ff, "a multiple of 8 in 8..%d" % MAX_FILTER_SIZE)
+    if vp["filter_size"] not in FILTER_SIZES:              # the predictors' LayerNorms: ttsk_layernorm_fwd_grouped / _fwd
+        raise ConfigError("variance_predictor.filter_size", vp["filter_size"], "one of %s" % (FILTER_SIZES,))
+    if vp["kernel_size"] != 3:
+        # the reference pads the predictor's second conv by 1 whatever the kernel size (model/modules.py:290): with any other size its
+        # own forward fails on the shortened sequence, so there is nothing to reproduce
+        raise ConfigError("variance_predictor.kernel_size", vp["kernel_size"], "3 (the only size the reference's predictor runs with: its second conv pads by 1)")
+    nb = model_config["variance_embedding"]["n_bins"]
+    if not (isinstance(nb, int) and nb >= 2):              # ttsk_bucketize / ttsk_va_embed: at least one bin edge
+        raise ConfigError("variance_embedding.n_bins", nb, "an integer >= 2")
+    if not (isinstance(model_config["max_seq_len"], int) and model_config["max_seq_len"] >= 1):
+        raise ConfigError("max_seq_len", model_config["max_seq_len"], "an integer >= 1")
+    # mel rows are GEMM operands (mel_linear's output, the PostNet's ends: 16-byte rows of bf16 = 8 channels; ttsk_zero_frames_from
+    # the same), the loss and BatchNorm take 4 at a time, a bias gradient's column sum at most 1024
+    if not (isinstance(n_mel, int) and 8 <= n_mel <= 1024 and n_mel % 8 == 0):
+        raise ConfigError("preprocessing.mel.n_mel_channels", n_mel, "a multiple of 8 in 8..1024")
+    if model_config["use_cwt"] and (d != 256 or vp["filter_size"] != 256):
+        # csrc/cwt.hip: the CNNscalar heads and the 11-output predictor head are built for 256 channels
+        key, val = ("transformer.encoder_hidden", d) if d != 256 else ("variance_predictor.filter_size", vp["filter_size"])
+        raise ConfigError(key, val, "256 when use_cwt is True (the CWT pitch kernels handle 256 channels)")
+
+
 def build_entries(model_config, n_mel, n_speakers, n_vocab):
     """Entries in FORWARD order (the flat buffer follows it, so backward completes buckets from the end).
-    reference shapes: fs_two/transformer/{Models,Layers,SubLayers}.py, fs_two/model/{fastspeech2,modules}.py."""
+    reference shapes: fs_two/transformer/{Models,Layers,SubLayers}.py, fs_two/model/{fastspeech2,modules}.py.
+    Raises ConfigError for a configuration the kernels cannot run (validate_config)."""
+    validate_config(model_config, n_mel)
     tr = model_config["transformer"]
     d = tr["encoder_hidden"]
-    assert tr["decoder_hidden"] == d and tr["variance_hidden"] == d, "kernels assume one hidden size"
     d_ff = tr["conv_filter_size"]
     k1, k2 = tr["conv_kernel_size"]
     n_pos = model_config["max_seq_len"] + 1
