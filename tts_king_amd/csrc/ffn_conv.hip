@@ -20,17 +20,10 @@
 
 namespace {
 
-#ifndef WC_XFIRST
-#define WC_XFIRST 1
-#endif
-#ifndef WC_WAVES
-#define WC_WAVES 8
-#endif
-// 256 output channels per workgroup: 8 waves x 32 channels (two MFMAs per activation fragment read, two waves per SIMD).  -DWC_WAVES=4
-// builds 4 waves x 64 (four MFMAs per fragment read, one wave per SIMD, accumulators in AGPRs): measured slower, 34.9 vs 31.5 us on
-// w_1's forward — the tap loop runs at the MFMA pipe's rate either way (tools/debug/wc_stamps.py), the prologue and epilogue have
-// half the threads.
-constexpr int WC_H = 4, WC_NW = WC_WAVES, WC_NT = WC_NW * 64, WC_KH = 4, WC_CT = 16 / WC_NW, WC_COUT = WC_NW * WC_CT * 16;
+// 256 output channels per workgroup: 8 waves x 32 channels (two MFMAs per activation fragment read, two waves per SIMD).  4 waves x 64
+// (four MFMAs per fragment read, one wave per SIMD, accumulators in AGPRs) measured slower, 34.9 vs 31.5 us on w_1's forward: the tap
+// loop runs at the MFMA pipe's rate either way (tools/debug/wc_stamps.py), the prologue and epilogue have half the threads.
+constexpr int WC_H = 4, WC_NW = 8, WC_NT = WC_NW * 64, WC_KH = 4, WC_CT = 2, WC_COUT = WC_NW * WC_CT * 16;
 
 struct WcArgs {
   const bf16_t* x;      // [B*S][CIN] bf16 (PAD rows are zeros)
@@ -290,11 +283,6 @@ __global__ __launch_bounds__(NWV * 64, (F16 && NWV == 4 && CIN == 128) ? 2 : 1) 
         for (int cc = 0; cc < CT; ++cc) w[ks][cc] = frag_load(wres, wlane, soff + ks * 64 + cc * (16 * K * C * 2));
     }
   };
-#if !WC_XFIRST
-  load_w(0, wa);
-  if (!F16 || 1 < NS) load_w(min(1, NS - 1), wb);
-  if (!F16 || 2 < NS) load_w(min(2, NS - 1), wc);
-#endif
 
   {  // ---- activation window: rows t0 - 4 .. t0 + TT + 4 of the utterance, zeros outside it (the conv's zero padding).
      // Requested BEFORE the weight fragments: loads return in order, nothing starts before the window is in LDS, and behind three
@@ -309,11 +297,9 @@ __global__ __launch_bounds__(NWV * 64, (F16 && NWV == 4 && CIN == 128) ? 2 : 1) 
       xv[it] = make_uint4(0, 0, 0, 0);
       if (idx < XROWS * CH8 && t >= 0 && t < S && ch * 8 < cin_valid) xv[it] = *(const uint4*)(xb + (int64_t)t * ldx + ch * 8);
     }
-#if WC_XFIRST
     load_w(0, wa);
     if (!F16 || 1 < NS) load_w(min(1, NS - 1), wb);      // (fp16 instances: no repeated requests, see the tap loop)
     if (!F16 || 2 < NS) load_w(min(2, NS - 1), wc);
-#endif
 #pragma unroll
     for (int it = 0; it < NCH; ++it) {
       const int idx = it * NT + tid;
@@ -667,6 +653,37 @@ extern "C" int ttsk_win_conv_set_stamps(void* dev_buffer) {
 }
 #endif
 
+// What every entry point starts from: the plain conv's operands, one contraction split over rows of Cin channels, everything else off.
+// The entry points add their own fields by name: no call site depends on the order of WcArgs's fields.
+WcArgs wc_args(const void* x, const void* w_packed, const float* bias, void* out, int S, int K, int Cout, int Cin) {
+  WcArgs a{};
+  a.x = (const bf16_t*)x; a.w = (const bf16_t*)w_packed; a.bias = bias; a.out = out;
+  a.S = S; a.K = K; a.Cout = Cout;
+  a.nsplit = 1; a.ldx = Cin;
+  return a;
+}
+
+// The argument checks the entry points share, reported under the entry point's name: the pointers it requires are there (`ptrs`), B
+// utterances of S rows are in range, an instance exists for the shape (`instance`; Cin, Cout and K — or the stride — only name it in the
+// message), the pointers or-ed into `align16` are 16-byte aligned and, where the entry point bounds it, the largest operand (B * S rows
+// of `row_bytes`) stays below 2^40 bytes.  What only one entry point asks stays beside it.
+int wc_check(const char* fn, bool ptrs, int B, int S, bool instance, int Cin, int Cout, int K, uintptr_t align16, int64_t row_bytes = 0) {
+  TTSK_REQUIRE(ptrs, "%s: null pointer", fn);
+  TTSK_REQUIRE(B > 0 && S > 0 && B <= 65535, "%s: bad sizes B=%d S=%d", fn, B, S);
+  TTSK_REQUIRE(instance, "%s: no instance for (Cin, Cout, K or stride) = (%d, %d, %d)", fn, Cin, Cout, K);
+  TTSK_REQUIRE((align16 & 15) == 0, "%s: 16-byte alignment", fn);
+  TTSK_REQUIRE((int64_t)B * S * row_bytes < ((int64_t)1 << 40), "%s: sizes out of range", fn);
+  return TTSK_OK;
+}
+uintptr_t bits(const void* p) { return (uintptr_t)p; }
+
+// A shape's bf16-operand instances on packed weights: the one with fp32 output or the one with bf16 output
+template <int CIN, int TT, int NWV = WC_NW, int CTV = WC_CT>
+void launch_out(int out_f32, dim3 grid, hipStream_t s, const WcArgs& a) {
+  if (out_f32) hipLaunchKernelGGL((win_conv_kernel<CIN, TT, true, true, NWV, CTV>), grid, dim3(NWV * 64), 0, s, a);
+  else hipLaunchKernelGGL((win_conv_kernel<CIN, TT, false, true, NWV, CTV>), grid, dim3(NWV * 64), 0, s, a);
+}
+
 int launch_win_conv(const WcArgs& a0, int B, int S, int Cin, int out_f32, int packed, hipStream_t s, int f16 = 0) {
   WcArgs a = a0;
 #ifdef TTSK_STAMPS
@@ -700,43 +717,28 @@ int launch_win_conv(const WcArgs& a0, int B, int S, int Cin, int out_f32, int pa
   }
   if (Cin == 256 && a.Cout == 80) {      // mel_linear (256 -> 80, k = 1): five waves of 16 channels over 64-frame tiles
     a.tiles_per_utt = (S + 63) / 64;
-    const dim3 g5(a.tiles_per_utt * B * a.nsplit);
-    if (out_f32) hipLaunchKernelGGL((win_conv_kernel<256, 64, true, true, 5, 1>), g5, dim3(320), 0, s, a);
-    else hipLaunchKernelGGL((win_conv_kernel<256, 64, false, true, 5, 1>), g5, dim3(320), 0, s, a);
+    launch_out<256, 64, 5, 1>(out_f32, dim3(a.tiles_per_utt * B * a.nsplit), s, a);
     return 0;
   }
   if (Cin == 80) {           // the PostNet's first conv (80 -> 512) / its last conv's input gradient: contraction padded to 96 channels
     a.cin_valid = 80;
-    if (out_f32) hipLaunchKernelGGL((win_conv_kernel<96, 64, true, true>), grid, dim3(WC_NT), 0, s, a);
-    else hipLaunchKernelGGL((win_conv_kernel<96, 64, false, true>), grid, dim3(WC_NT), 0, s, a);
+    launch_out<96, 64>(out_f32, grid, s, a);
     return 0;
   }
   if (Cin == 512 && a.Cout == 80) {      // the PostNet's last conv (512 -> 80) / its first conv's input gradient: 5 waves x 16 channels
-    const dim3 g5(a.tiles_per_utt * B * a.nsplit);
-    if (out_f32) hipLaunchKernelGGL((win_conv_kernel<512, 64, true, true, 5, 1>), g5, dim3(320), 0, s, a);
-    else hipLaunchKernelGGL((win_conv_kernel<512, 64, false, true, 5, 1>), g5, dim3(320), 0, s, a);
+    launch_out<512, 64, 5, 1>(out_f32, dim3(a.tiles_per_utt * B * a.nsplit), s, a);
     return 0;
   }
   if (short_seq && !a.delta && (int)grid.x <= 128) {     // few workgroups, each bound by its weight stream: 64-channel groups
-    dim3 g4(grid.x * 4);
-    if (out_f32) hipLaunchKernelGGL((win_conv_kernel<256, 64, true, true, 4, 1>), g4, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((win_conv_kernel<256, 64, false, true, 4, 1>), g4, dim3(256), 0, s, a);
+    launch_out<256, 64, 4, 1>(out_f32, dim3(grid.x * 4), s, a);
     return 0;
   }
   // (the 112-frame instances with nothing riding on the staged output tile store straight from the registers: WcArgs::direct)
   a.direct = packed && !short_seq && Cin == 256 && !a.gate && !a.delta && !a.stats && !a.bnb_x && !a.out16 && !a.ups_cout && !(a.lrelu_slope > 0.f);
-  if (Cin == 256 && out_f32) {
-    if (short_seq) hipLaunchKernelGGL((win_conv_kernel<256, 64, true, true>), grid, dim3(WC_NT), 0, s, a);
-    else hipLaunchKernelGGL((win_conv_kernel<256, 112, true, true>), grid, dim3(WC_NT), 0, s, a);
-  } else if (short_seq) {
-    hipLaunchKernelGGL((win_conv_kernel<256, 64, false, true>), grid, dim3(WC_NT), 0, s, a);
-  } else if (Cin == 256) {
-    if (packed) hipLaunchKernelGGL((win_conv_kernel<256, 112, false, true>), grid, dim3(WC_NT), 0, s, a);
-    else hipLaunchKernelGGL((win_conv_kernel<256, 112, false, false>), grid, dim3(WC_NT), 0, s, a);
-  } else {
-    if (out_f32) hipLaunchKernelGGL((win_conv_kernel<512, 64, true, true>), grid, dim3(WC_NT), 0, s, a);
-    else hipLaunchKernelGGL((win_conv_kernel<512, 64, false, true>), grid, dim3(WC_NT), 0, s, a);
-  }
+  if (short_seq) launch_out<256, 64>(out_f32, grid, s, a);            // (short_seq: Cin is 256, the weights are packed)
+  else if (Cin != 256) launch_out<512, 64>(out_f32, grid, s, a);
+  else if (packed || out_f32) launch_out<256, 112>(out_f32, grid, s, a);
+  else hipLaunchKernelGGL((win_conv_kernel<256, 112, false, false>), grid, dim3(WC_NT), 0, s, a);      // ttsk_ffn_conv_fwd(packed = 0): tap-major weights, bf16 output
   return 0;
 }
 
@@ -787,15 +789,15 @@ extern "C" int ttsk_ffn_pack_weight(const void* w_bf16, void* packed_bf16, int C
 
 extern "C" int ttsk_win_conv(const void* x_bf16, const void* w_packed, const float* bias, const void* gate_bf16, const float* delta_o32,
                              float* delta_out, void* out, int out_f32, int B, int S, int Cin, int Cout, int K, int relu, void* stream) {
-  TTSK_REQUIRE(x_bf16 && w_packed && out, "ttsk_win_conv: null pointer");
-  TTSK_REQUIRE(B > 0 && S > 0 && B <= 65535, "ttsk_win_conv: bad sizes B=%d S=%d", B, S);
-  TTSK_REQUIRE(ttsk_win_conv_supported(Cin, Cout, K), "ttsk_win_conv: no instance for Cin=%d Cout=%d K=%d", Cin, Cout, K);
-  TTSK_REQUIRE(((((uintptr_t)x_bf16) | ((uintptr_t)w_packed) | ((uintptr_t)bias) | ((uintptr_t)out)) & 15) == 0, "ttsk_win_conv: 16-byte alignment");
-  TTSK_REQUIRE((int64_t)B * S * (Cout > Cin ? Cout : Cin) * 4 < ((int64_t)1 << 40), "ttsk_win_conv: sizes out of range");
-  TTSK_REQUIRE(!(gate_bf16 && out_f32) && (((uintptr_t)gate_bf16) & 15) == 0, "ttsk_win_conv: the gate goes with bf16 output, 16-byte aligned");
-  WcArgs a{(const bf16_t*)x_bf16, (const bf16_t*)w_packed, bias, out, S, K, Cout, relu, 0, 0, (const bf16_t*)gate_bf16, 1, Cin, 0, delta_o32, delta_out};
-  TTSK_REQUIRE(!delta_out || (delta_o32 && !out_f32 && Cout % 128 == 0 && (((uintptr_t)delta_o32) & 15) == 0),
+  if (int rc = wc_check("ttsk_win_conv", x_bf16 && w_packed && out, B, S, ttsk_win_conv_supported(Cin, Cout, K), Cin, Cout, K,
+                        bits(x_bf16) | bits(w_packed) | bits(bias) | bits(out), (int64_t)(Cout > Cin ? Cout : Cin) * 4))
+    return rc;
+  TTSK_REQUIRE(!(gate_bf16 && out_f32) && (bits(gate_bf16) & 15) == 0, "ttsk_win_conv: the gate goes with bf16 output, 16-byte aligned");
+  TTSK_REQUIRE(!delta_out || (delta_o32 && !out_f32 && Cout % 128 == 0 && (bits(delta_o32) & 15) == 0),
                "ttsk_win_conv: delta needs o32 (16-byte aligned), bf16 output and Cout = heads * 128");
+  WcArgs a = wc_args(x_bf16, w_packed, bias, out, S, K, Cout, Cin);
+  a.relu = relu; a.gate = (const bf16_t*)gate_bf16;
+  a.o32 = delta_o32; a.delta = delta_out;
   launch_win_conv(a, B, S, Cin, out_f32, 1, (hipStream_t)stream);
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
@@ -805,11 +807,10 @@ extern "C" int ttsk_win_conv(const void* x_bf16, const void* w_packed, const flo
 // (512 -> 80 on the transposed pack) + the mel loss's own gradient (fastspeech2.py:104: postnet(output) + output)
 extern "C" int ttsk_win_conv_resid(const void* x_bf16, const void* w_packed, const float* resid_f32, void* out_bf16, int B, int S, int Cin,
                                    int Cout, int K, void* stream) {
-  TTSK_REQUIRE(x_bf16 && w_packed && resid_f32 && out_bf16, "ttsk_win_conv_resid: null pointer");
-  TTSK_REQUIRE(B > 0 && S > 0 && B <= 65535, "ttsk_win_conv_resid: bad sizes B=%d S=%d", B, S);
-  TTSK_REQUIRE(ttsk_win_conv_supported(Cin, Cout, K), "ttsk_win_conv_resid: no instance for Cin=%d Cout=%d K=%d", Cin, Cout, K);
-  TTSK_REQUIRE(((((uintptr_t)x_bf16) | ((uintptr_t)w_packed) | ((uintptr_t)resid_f32) | ((uintptr_t)out_bf16)) & 15) == 0, "ttsk_win_conv_resid: 16-byte alignment");
-  WcArgs a{(const bf16_t*)x_bf16, (const bf16_t*)w_packed, nullptr, out_bf16, S, K, Cout, 0, 0, 0, nullptr, 1, Cin, 0, nullptr, nullptr};
+  if (int rc = wc_check("ttsk_win_conv_resid", x_bf16 && w_packed && resid_f32 && out_bf16, B, S, ttsk_win_conv_supported(Cin, Cout, K), Cin, Cout, K,
+                        bits(x_bf16) | bits(w_packed) | bits(resid_f32) | bits(out_bf16)))
+    return rc;
+  WcArgs a = wc_args(x_bf16, w_packed, nullptr, out_bf16, S, K, Cout, Cin);
   a.resid32 = resid_f32;
   launch_win_conv(a, B, S, Cin, 0, 1, (hipStream_t)stream);
   TTSK_CHECK_LAUNCH();
@@ -820,13 +821,12 @@ extern "C" int ttsk_win_conv_resid(const void* x_bf16, const void* w_packed, con
 // behind the PostNet, the bf16 copy is the PostNet's input)
 extern "C" int ttsk_win_conv_dual(const void* x_bf16, const void* w_packed, const float* bias, float* out_f32, void* out_bf16, int B, int S,
                                   int Cin, int Cout, int K, void* stream) {
-  TTSK_REQUIRE(x_bf16 && w_packed && out_f32 && out_bf16, "ttsk_win_conv_dual: null pointer");
-  TTSK_REQUIRE(B > 0 && S > 0 && B <= 65535, "ttsk_win_conv_dual: bad sizes B=%d S=%d", B, S);
-  TTSK_REQUIRE(ttsk_win_conv_supported(Cin, Cout, K), "ttsk_win_conv_dual: no instance for Cin=%d Cout=%d K=%d", Cin, Cout, K);
-  TTSK_REQUIRE(((((uintptr_t)x_bf16) | ((uintptr_t)w_packed) | ((uintptr_t)bias) | ((uintptr_t)out_f32)) & 15) == 0 && (((uintptr_t)out_bf16) & 7) == 0,
-               "ttsk_win_conv_dual: 16-byte alignment (bf16 copy: 8)");
+  if (int rc = wc_check("ttsk_win_conv_dual", x_bf16 && w_packed && out_f32 && out_bf16, B, S, ttsk_win_conv_supported(Cin, Cout, K), Cin, Cout, K,
+                        bits(x_bf16) | bits(w_packed) | bits(bias) | bits(out_f32)))
+    return rc;
+  TTSK_REQUIRE((bits(out_bf16) & 7) == 0, "ttsk_win_conv_dual: the bf16 copy must be 8-byte aligned");
   TTSK_REQUIRE((Cout & 3) == 0, "ttsk_win_conv_dual: Cout must be a multiple of 4");
-  WcArgs a{(const bf16_t*)x_bf16, (const bf16_t*)w_packed, bias, out_f32, S, K, Cout, 0, 0, 0, nullptr, 1, Cin, 0, nullptr, nullptr};
+  WcArgs a = wc_args(x_bf16, w_packed, bias, out_f32, S, K, Cout, Cin);
   a.out16 = (bf16_t*)out_bf16;
   launch_win_conv(a, B, S, Cin, 1, 1, (hipStream_t)stream);
   TTSK_CHECK_LAUNCH();
@@ -846,14 +846,12 @@ extern "C" int ttsk_hifi_upsample8_supported(int Cin, int Cout) { return ttsk_hi
 // bias repeated for the `stride` phases.
 extern "C" int ttsk_hifi_upsample_win(const void* x16, const void* w_packed, const float* bias_rep, void* out16, int f16, int B, int T, int Cin,
                                       int Cout, int stride, void* stream) {
-  TTSK_REQUIRE(x16 && w_packed && bias_rep && out16, "ttsk_hifi_upsample_win: null pointer");
-  TTSK_REQUIRE(B > 0 && T > 0 && B <= 65535, "ttsk_hifi_upsample_win: bad sizes B=%d T=%d", B, T);
-  TTSK_REQUIRE(ttsk_hifi_upsample_win_supported(Cin, Cout, stride), "ttsk_hifi_upsample_win: no instance for Cin=%d Cout=%d stride=%d", Cin, Cout, stride);
+  if (int rc = wc_check("ttsk_hifi_upsample_win", x16 && w_packed && bias_rep && out16, B, T, ttsk_hifi_upsample_win_supported(Cin, Cout, stride), Cin, Cout,
+                        stride, bits(x16) | bits(w_packed) | bits(bias_rep) | bits(out16), (int64_t)stride * Cout * 2))
+    return rc;
   TTSK_REQUIRE(f16 == 1, "ttsk_hifi_upsample_win: built for fp16 rows (HiFi-GAN inference)");
-  TTSK_REQUIRE(((((uintptr_t)x16) | ((uintptr_t)w_packed) | ((uintptr_t)bias_rep) | ((uintptr_t)out16)) & 15) == 0, "ttsk_hifi_upsample_win: 16-byte alignment");
-  TTSK_REQUIRE((int64_t)B * T * stride * Cout * 2 < ((int64_t)1 << 40), "ttsk_hifi_upsample_win: sizes out of range");
-  WcArgs a{(const bf16_t*)x16, (const bf16_t*)w_packed, bias_rep, out16, T, 2, stride * Cout, 0, 0, 0, nullptr, 1, Cin, 0, nullptr, nullptr, nullptr, nullptr,
-           Cout, stride / 2};
+  WcArgs a = wc_args(x16, w_packed, bias_rep, out16, T, 2, stride * Cout, Cin);
+  a.ups_cout = Cout; a.ups_half = stride / 2;
   launch_win_conv(a, B, T, Cin, 0, 1, (hipStream_t)stream, 1);
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
@@ -866,13 +864,12 @@ extern "C" int ttsk_hifi_conv_pre_win_supported(int Cin, int Cout, int K) {
 }
 extern "C" int ttsk_hifi_conv_pre_win(const void* x16, const void* w_packed, const float* bias, void* out16, int f16, int B, int T, int Cin, int Cout,
                                       int K, float slope, void* stream) {
-  TTSK_REQUIRE(x16 && w_packed && bias && out16, "ttsk_hifi_conv_pre_win: null pointer");
-  TTSK_REQUIRE(B > 0 && T > 0 && B <= 65535, "ttsk_hifi_conv_pre_win: bad sizes B=%d T=%d", B, T);
-  TTSK_REQUIRE(ttsk_hifi_conv_pre_win_supported(Cin, Cout, K), "ttsk_hifi_conv_pre_win: no instance for Cin=%d Cout=%d K=%d", Cin, Cout, K);
+  if (int rc = wc_check("ttsk_hifi_conv_pre_win", x16 && w_packed && bias && out16, B, T, ttsk_hifi_conv_pre_win_supported(Cin, Cout, K), Cin, Cout, K,
+                        bits(x16) | bits(w_packed) | bits(bias) | bits(out16)))
+    return rc;
   TTSK_REQUIRE(f16 == 1, "ttsk_hifi_conv_pre_win: built for fp16 rows (HiFi-GAN inference)");
   TTSK_REQUIRE(slope >= 0.f && slope <= 1.f, "ttsk_hifi_conv_pre_win: slope in [0, 1] (0: no activation)");
-  TTSK_REQUIRE(((((uintptr_t)x16) | ((uintptr_t)w_packed) | ((uintptr_t)bias) | ((uintptr_t)out16)) & 15) == 0, "ttsk_hifi_conv_pre_win: 16-byte alignment");
-  WcArgs a{(const bf16_t*)x16, (const bf16_t*)w_packed, bias, out16, T, K, Cout, 0, 0, 0, nullptr, 1, Cin, 0, nullptr, nullptr};
+  WcArgs a = wc_args(x16, w_packed, bias, out16, T, K, Cout, Cin);
   a.lrelu_slope = slope;
   launch_win_conv(a, B, T, Cin, 0, 1, (hipStream_t)stream, 1);
   TTSK_CHECK_LAUNCH();
@@ -886,14 +883,15 @@ extern "C" int ttsk_hifi_upsample_loop_supported(int Cin, int Cout, int stride) 
 }
 extern "C" int ttsk_hifi_upsample_loop(const void* x16, const void* w_packed, const float* bias_rep, void* out16, int f16, int B, int T, int Cin,
                                        int Cout, int stride, void* stream) {
+  // (its own checks, not wc_check's: the batch is bounded through the grid, B * tiles < 2^31, not by B <= 65535)
   TTSK_REQUIRE(x16 && w_packed && bias_rep && out16, "ttsk_hifi_upsample_loop: null pointer");
   TTSK_REQUIRE(B > 0 && T > 0 && (int64_t)B * ((T + 95) / 96) < ((int64_t)1 << 31), "ttsk_hifi_upsample_loop: bad sizes B=%d T=%d", B, T);
   TTSK_REQUIRE(ttsk_hifi_upsample_loop_supported(Cin, Cout, stride), "ttsk_hifi_upsample_loop: no instance for Cin=%d Cout=%d stride=%d", Cin, Cout, stride);
   TTSK_REQUIRE(f16 == 1, "ttsk_hifi_upsample_loop: built for fp16 rows (HiFi-GAN inference)");
-  TTSK_REQUIRE(((((uintptr_t)x16) | ((uintptr_t)w_packed) | ((uintptr_t)bias_rep) | ((uintptr_t)out16)) & 15) == 0, "ttsk_hifi_upsample_loop: 16-byte alignment");
+  TTSK_REQUIRE(((bits(x16) | bits(w_packed) | bits(bias_rep) | bits(out16)) & 15) == 0, "ttsk_hifi_upsample_loop: 16-byte alignment");
   TTSK_REQUIRE((int64_t)B * T * stride * Cout * 2 < ((int64_t)1 << 40), "ttsk_hifi_upsample_loop: sizes out of range");
-  WcArgs a{(const bf16_t*)x16, (const bf16_t*)w_packed, bias_rep, out16, T, 2, stride * Cout, 0, 0, 0, nullptr, 1, Cin, 0, nullptr, nullptr, nullptr, nullptr,
-           Cout, stride / 2};
+  WcArgs a = wc_args(x16, w_packed, bias_rep, out16, T, 2, stride * Cout, Cin);
+  a.ups_cout = Cout; a.ups_half = stride / 2;
   a.B = B;
   a.tiles_per_utt = (T + 95) / 96;
   hipLaunchKernelGGL((ups_loop_kernel<256, 96>), dim3(a.tiles_per_utt * B), dim3(WC_NT), 0, (hipStream_t)stream, a);
@@ -910,11 +908,12 @@ extern "C" int ttsk_win_conv_stats_rows(int B, int S) { return B * ((S + 63) / 6
 // ttsk_win_conv with fp32 output whose BatchNorm statistics partials come out of the same kernel (Cin = 512)
 extern "C" int ttsk_win_conv_stats(const void* x_bf16, const void* w_packed, const float* bias, float* out_f32, float* stats,
                                    const int32_t* frame_limit, int B, int S, int Cin, int Cout, int K, void* stream) {
-  TTSK_REQUIRE(x_bf16 && w_packed && out_f32 && stats, "ttsk_win_conv_stats: null pointer");
-  TTSK_REQUIRE(B > 0 && S > 0 && B <= 65535, "ttsk_win_conv_stats: bad sizes B=%d S=%d", B, S);
-  TTSK_REQUIRE((Cin == 512 || Cin == 80) && ttsk_win_conv_supported(Cin, Cout, K), "ttsk_win_conv_stats: built for Cin = 512 or 80 (got Cin=%d Cout=%d K=%d)", Cin, Cout, K);
-  TTSK_REQUIRE(((((uintptr_t)x_bf16) | ((uintptr_t)w_packed) | ((uintptr_t)bias) | ((uintptr_t)out_f32)) & 15) == 0, "ttsk_win_conv_stats: 16-byte alignment");
-  WcArgs a{(const bf16_t*)x_bf16, (const bf16_t*)w_packed, bias, out_f32, S, K, Cout, 0, 0, 0, nullptr, 1, Cin, 0, nullptr, nullptr, stats, frame_limit};
+  // (an instance that can emit the statistics: Cin = 512 or 80)
+  if (int rc = wc_check("ttsk_win_conv_stats", x_bf16 && w_packed && out_f32 && stats, B, S, (Cin == 512 || Cin == 80) && ttsk_win_conv_supported(Cin, Cout, K),
+                        Cin, Cout, K, bits(x_bf16) | bits(w_packed) | bits(bias) | bits(out_f32)))
+    return rc;
+  WcArgs a = wc_args(x_bf16, w_packed, bias, out_f32, S, K, Cout, Cin);
+  a.stats = stats; a.frame_limit = frame_limit;
   launch_win_conv(a, B, S, Cin, 1, 1, (hipStream_t)stream);
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
@@ -925,14 +924,15 @@ extern "C" int ttsk_win_conv_stats(const void* x_bf16, const void* w_packed, con
 extern "C" int ttsk_win_conv_bnb(const void* x_bf16, const void* w_packed, void* out_bf16, float* stats, const float* bn_x_f32,
                                  const float* mean, const float* rstd, const float* gamma, const float* beta, const uint8_t* keep, float p,
                                  int use_tanh, const int32_t* frame_limit, int B, int S, int Cin, int Cout, int K, void* stream) {
-  TTSK_REQUIRE(x_bf16 && w_packed && out_bf16 && stats && bn_x_f32 && mean && rstd && gamma && beta, "ttsk_win_conv_bnb: null pointer");
-  TTSK_REQUIRE(B > 0 && S > 0 && B <= 65535, "ttsk_win_conv_bnb: bad sizes B=%d S=%d", B, S);
-  TTSK_REQUIRE((Cin == 512 || Cin == 80) && Cout % WC_COUT == 0 && ttsk_win_conv_supported(Cin, Cout, K), "ttsk_win_conv_bnb: built for Cin = 512 or 80, Cout a multiple of 256 (got Cin=%d Cout=%d K=%d)", Cin, Cout, K);
+  // (an instance that can emit the statistics: Cin = 512 or 80, 256-channel groups)
+  if (int rc = wc_check("ttsk_win_conv_bnb", x_bf16 && w_packed && out_bf16 && stats && bn_x_f32 && mean && rstd && gamma && beta, B, S,
+                        (Cin == 512 || Cin == 80) && Cout % WC_COUT == 0 && ttsk_win_conv_supported(Cin, Cout, K), Cin, Cout, K,
+                        bits(x_bf16) | bits(w_packed) | bits(out_bf16) | bits(bn_x_f32) | bits(mean) | bits(rstd) | bits(gamma) | bits(beta)))
+    return rc;
   TTSK_REQUIRE(p >= 0.f && p < 1.f && (p == 0.f || keep), "ttsk_win_conv_bnb: dropout needs the forward's keep bits");
-  TTSK_REQUIRE(((((uintptr_t)x_bf16) | ((uintptr_t)w_packed) | ((uintptr_t)out_bf16) | ((uintptr_t)bn_x_f32) | ((uintptr_t)mean) | ((uintptr_t)rstd) |
-                 ((uintptr_t)gamma) | ((uintptr_t)beta)) & 15) == 0, "ttsk_win_conv_bnb: 16-byte alignment");
-  WcArgs a{(const bf16_t*)x_bf16, (const bf16_t*)w_packed, nullptr, out_bf16, S, K, Cout, 0, 0, 0, nullptr, 1, Cin, 0, nullptr, nullptr, nullptr, frame_limit,
-           0, 0, bn_x_f32, mean, rstd, gamma, beta, keep, stats, p, use_tanh};
+  WcArgs a = wc_args(x_bf16, w_packed, nullptr, out_bf16, S, K, Cout, Cin);
+  a.bnb_x = bn_x_f32; a.bnb_mean = mean; a.bnb_rstd = rstd; a.bnb_gamma = gamma; a.bnb_beta = beta;
+  a.bnb_keep = keep; a.bnb_p = p; a.bnb_tanh = use_tanh; a.bnb_stats = stats; a.frame_limit = frame_limit;
   launch_win_conv(a, B, S, Cin, 0, 1, (hipStream_t)stream);
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
@@ -940,12 +940,11 @@ extern "C" int ttsk_win_conv_bnb(const void* x_bf16, const void* w_packed, void*
 
 extern "C" int ttsk_ffn_conv_fwd(const void* x_bf16, const void* w_bf16, const float* bias, void* out_bf16, int B, int S, int Cin, int Cout,
                                  int K, int relu, int packed, void* stream) {
-  TTSK_REQUIRE(x_bf16 && w_bf16 && bias && out_bf16, "ttsk_ffn_conv_fwd: null pointer");
-  TTSK_REQUIRE(B > 0 && S > 0 && B <= 65535, "ttsk_ffn_conv_fwd: bad sizes B=%d S=%d", B, S);
-  TTSK_REQUIRE(ttsk_ffn_conv_supported(Cin, Cout, K), "ttsk_ffn_conv_fwd: no instance for Cin=%d Cout=%d K=%d", Cin, Cout, K);
-  TTSK_REQUIRE(((((uintptr_t)x_bf16) | ((uintptr_t)w_bf16) | ((uintptr_t)bias) | ((uintptr_t)out_bf16)) & 15) == 0, "ttsk_ffn_conv_fwd: 16-byte alignment");
-  TTSK_REQUIRE((int64_t)B * S * (Cout > Cin ? Cout : Cin) * 2 < ((int64_t)1 << 40), "ttsk_ffn_conv_fwd: sizes out of range");
-  WcArgs a{(const bf16_t*)x_bf16, (const bf16_t*)w_bf16, bias, out_bf16, S, K, Cout, relu, 0, 0, nullptr, 1, Cin, 0, nullptr, nullptr};
+  if (int rc = wc_check("ttsk_ffn_conv_fwd", x_bf16 && w_bf16 && bias && out_bf16, B, S, ttsk_ffn_conv_supported(Cin, Cout, K), Cin, Cout, K,
+                        bits(x_bf16) | bits(w_bf16) | bits(bias) | bits(out_bf16), (int64_t)(Cout > Cin ? Cout : Cin) * 2))
+    return rc;
+  WcArgs a = wc_args(x_bf16, w_bf16, bias, out_bf16, S, K, Cout, Cin);
+  a.relu = relu;
   launch_win_conv(a, B, S, Cin, 0, packed, (hipStream_t)stream);
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
@@ -953,12 +952,12 @@ extern "C" int ttsk_ffn_conv_fwd(const void* x_bf16, const void* w_bf16, const f
 
 extern "C" int ttsk_win_conv_split(const void* x_bf16, const void* w_packed, float* slabs, int nsplit, int B, int S, int Cin_total, int Cout,
                                    int K, void* stream) {
-  TTSK_REQUIRE(x_bf16 && w_packed && slabs && nsplit >= 1 && nsplit <= 8, "ttsk_win_conv_split: bad arguments");
-  TTSK_REQUIRE(B > 0 && S > 0 && B <= 65535 && Cin_total == nsplit * 256, "ttsk_win_conv_split: Cin must be nsplit * 256 (got %d, nsplit %d)", Cin_total, nsplit);
-  TTSK_REQUIRE(ttsk_win_conv_supported(256, Cout, K), "ttsk_win_conv_split: no instance for Cout=%d K=%d", Cout, K);
-  TTSK_REQUIRE(((((uintptr_t)x_bf16) | ((uintptr_t)w_packed) | ((uintptr_t)slabs)) & 15) == 0, "ttsk_win_conv_split: 16-byte alignment");
-  WcArgs a{(const bf16_t*)x_bf16, (const bf16_t*)w_packed, nullptr, slabs, S, K, Cout, 0, 0, 0, nullptr, nsplit, Cin_total, (int64_t)B * S * Cout,
-           nullptr, nullptr};
+  TTSK_REQUIRE(nsplit >= 1 && nsplit <= 8 && Cin_total == nsplit * 256, "ttsk_win_conv_split: Cin must be nsplit * 256, nsplit 1..8 (got %d, nsplit %d)", Cin_total, nsplit);
+  if (int rc = wc_check("ttsk_win_conv_split", x_bf16 && w_packed && slabs, B, S, ttsk_win_conv_supported(256, Cout, K), 256, Cout, K,
+                        bits(x_bf16) | bits(w_packed) | bits(slabs)))
+    return rc;
+  WcArgs a = wc_args(x_bf16, w_packed, nullptr, slabs, S, K, Cout, Cin_total);      // rows of all nsplit * 256 channels
+  a.nsplit = nsplit; a.out_split = (int64_t)B * S * Cout;
   launch_win_conv(a, B, S, 256, 1, 1, (hipStream_t)stream);
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
