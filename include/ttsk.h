@@ -969,6 +969,43 @@ int ttsk_dtw_align(const float* x, const float* y, const int32_t* x_lens, const 
                    const int32_t* x_seg, const int32_t* n_seg, int ldL, void* workspace, int64_t workspace_bytes, int32_t* path_x,
                    float* cost, int32_t* status, int32_t* dur, void* stream);
 
+/* ------------------------------------------------------------------------------- Griffin-Lim: STFT, inverse STFT, iteration
+ * DESIGN.md section 21.  reference: fs_two/audio/stft.py:57-137 (STFT.transform / STFT.inverse),
+ * fs_two/audio/audio_processing.py:66-82 (griffin_lim), fs_two/audio/tools.py:18-25 (inv_mel_spec's mel-to-linear map).
+ * All fp32, an FFT in LDS.  n_fft a power of two in 64..2048, hop divides n_fft, 1 <= B <= 65535.
+ * window: n_fft floats (the analysis and synthesis window, centre-padded by the caller); twiddle: n_fft / 2 pairs
+ * (cos, -sin)(2 pi k / n_fft), built in fp64 and rounded once.  nbins = n_fft / 2 + 1.
+ * stft_polar: wav (B, len) -> mag, phase (B, nbins, T), T = 1 + len / hop, len > n_fft / 2: reflect padding by n_fft / 2, frame t
+ *   starts at padded sample t * hop, window, real FFT, phase = atan2f(im, re).  lens int32[B] or null: samples per row; a row
+ *   reflects about its own end, has 1 + lens[b] / hop frames and zeros in the others (all of them when lens[b] <= n_fft / 2).
+ * istft_frames: mag, phase with element (b, k, t) at b * sB + k * sk + t * st -> frames_out (B, T, n_fft): the inverse real FFT of
+ *   mag * (cos, sin)(phase), imaginary parts of bins 0 and n_fft / 2 ignored, times the window.  frames int32[B] or null: frames
+ *   per row; the frames past a row's count are neither read nor written.
+ * istft_ola: frames_in (B, T, n_fft) -> wav (B, hop * (T - 1)): sample j = sum over the frames t < frames[b] covering padded
+ *   sample p = j + n_fft / 2, in ascending t, of frames_in[t][p - t * hop], divided by sum_t window^2[p - t * hop] where that
+ *   exceeds float32 tiny; zeros from hop * (frames[b] - 1) on.  A gather: no atomics, a row depends on nothing but itself.
+ * istft: istft_frames into workspace (B * T * n_fft floats), then istft_ola: the reference's STFT.inverse.
+ * griffinlim_step: one iteration.  Source: wav (B, ld_wav) rows of hop * (frames[b] - 1) samples, or frames_in, the previous
+ *   step's frames_out, read through istft_ola's sum (exactly one of the two; frames_in != frames_out).  Z = STFT(source);
+ *   A = Z - momentum / (1 + momentum) * zprev and zprev <- Z when momentum > 0 (zprev (B, T, nbins) complex pairs; momentum
+ *   = 0 never touches it); bin <- mag * A / |A|, (mag, 0) where |A| == 0; inverse FFT, window -> frames_out.
+ *   hop * (T - 1) > n_fft / 2; a row with hop * (frames[b] - 1) <= n_fft / 2 is skipped.
+ * mel_to_spec: log-mel (B, n_mels, T) -> spec (B, nbins, T) = scale * sum_m exp(mel[m]) * fb[m][k] with the filterbank packed
+ *   as for mel_from_spec (filters summed in ascending m; a bin no filter covers is exactly 0). */
+int ttsk_stft_polar(const float* wav, const int32_t* lens, int B, int len, int n_fft, int hop, const float* window,
+                    const float* twiddle, float* mag, float* phase, int T, void* stream);
+int ttsk_istft_frames(const float* mag, const float* phase, int64_t sB, int64_t sk, int64_t st, const int32_t* frames, int B,
+                      int T, int n_fft, int hop, const float* window, const float* twiddle, float* frames_out, void* stream);
+int ttsk_istft_ola(const float* frames_in, const int32_t* frames, int B, int T, int n_fft, int hop, const float* window,
+                   float* wav, void* stream);
+int ttsk_istft(const float* mag, const float* phase, int64_t sB, int64_t sk, int64_t st, const int32_t* frames, int B, int T,
+               int n_fft, int hop, const float* window, const float* twiddle, float* workspace, float* wav, void* stream);
+int ttsk_griffinlim_step(const float* wav, int64_t ld_wav, const float* frames_in, const float* mag, int64_t sB, int64_t sk,
+                         int64_t st, const int32_t* frames, float* zprev, float momentum, int B, int T, int n_fft, int hop,
+                         const float* window, const float* twiddle, float* frames_out, void* stream);
+int ttsk_mel_to_spec(const float* mel, const float* basis_vals, const int32_t* basis_start, const int32_t* basis_off, int B,
+                     int n_mels, int nbins, int T, float scale, float* spec, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

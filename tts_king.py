@@ -12,14 +12,34 @@ import torch
 from tts_king_amd.config import load_config
 from fsapi import FSTWOapi
 from hifiapi import HIFIapi
+from tts_king_amd.audio import GriffinLimVocoder
 
 
 class TTSKing:
     def __init__(self, config_path="./config.yaml"):
         self.cfg = load_config(config_path)
         self.tts = FSTWOapi(self.cfg, self.cfg.gpu)
-        self.vocoder = HIFIapi(self.cfg, self.cfg.gpu)
+        self.vocoder = self._build_vocoder(self._configured_vocoder())   # "hifigan", or "griffin_lim": no `hifi` checkpoint is then needed
         self.speakers = self.tts.speaker_names
+
+    def _configured_vocoder(self):
+        """`mi355x.vocoder`: "hifigan" (the default) or "griffin_lim"."""
+        from tts_king_amd.audio import vocoder_name
+        return vocoder_name((self.cfg.get("mi355x", None) or {}).get("vocoder", None))
+
+    def _build_vocoder(self, name):
+        return (HIFIapi if name == "hifigan" else GriffinLimVocoder)(self.cfg, self.cfg.gpu)
+
+    def _vocoder(self, name):
+        """The vocoder object of `name`: None or the configured name is `self.vocoder`, the other one is built on first use."""
+        from tts_king_amd.audio import vocoder_name
+        configured = self._configured_vocoder()
+        name = vocoder_name(name, configured)
+        if name == configured:
+            return self.vocoder
+        if "_other_vocoder" not in self.__dict__:
+            self._other_vocoder = self._build_vocoder(name)
+        return self._other_vocoder
 
     def generate_mel(self, text, duration_control=1.0, pitch_control=1.0, energy_control=1.0, speaker=0, durations=None, pitch=None,
                      energy=None, target_frames=None, return_prosody=False):
@@ -48,28 +68,38 @@ class TTSKing:
             speaker = self.speakers[speaker]
         return self.tts.generate(phonemes, duration_control, pitch_control, energy_control, speaker_name=speaker)
 
-    def mel_to_wav(self, mel_spec, sample_rate=None):
+    def mel_to_wav(self, mel_spec, sample_rate=None, vocoder=None, griffin_iters=60):
         """(1, T, 80) mel -> int16 ndarray (1, 1, 256 T).  reference: tts_king.py:47-49.
         A list of (1, T_i, 80) mels of any lengths -> a list of such arrays, vocoded together as fixed-size windows
         (`HIFIapi.generate_ragged`); a one-element list is how a single long utterance gets onto the bounded graph set.
-        `sample_rate` (Hz): the waveform at that rate, ceil(256 T L / M) samples, resampled on the device (`HIFIapi.generate`)."""
+        `sample_rate` (Hz): the waveform at that rate, ceil(256 T L / M) samples, resampled on the device (`HIFIapi.generate`).
+        `vocoder`: "hifigan", "griffin_lim" or None for `mi355x.vocoder` (default "hifigan").  "griffin_lim" needs no checkpoint and
+        takes the preprocess_config's `n_mel_channels` up to 1024 and STFT parameters with filter_length a power of two in 64..2048
+        and hop_length a divisor of it (`audio.GriffinLimVocoder`, which refuses anything else by the config key's name; DESIGN.md
+        section 21): `griffin_iters` iterations, hop_length * (T - 1) samples, every utterance scaled to a peak of 0.95; a list runs
+        as one batch and each array equals its solo call's."""
+        voc = self._vocoder(vocoder)
+        extra = dict(griffin_iters=griffin_iters) if isinstance(voc, GriffinLimVocoder) else {}
         if isinstance(mel_spec, (list, tuple)):
-            return self.vocoder.generate_ragged(mel_spec, frames_first=True, sample_rate=sample_rate)
-        return self.vocoder.generate(mel_spec.transpose(1, 2), sample_rate=sample_rate)
+            return voc.generate_ragged(mel_spec, frames_first=True, sample_rate=sample_rate, **extra)
+        return voc.generate(mel_spec.transpose(1, 2), sample_rate=sample_rate, **extra)
 
     def speak(self, text, duration_control=1.0, pitch_control=1.0, energy_control=1.0, speaker=0, durations=None, pitch=None, energy=None,
-              target_frames=None, return_prosody=False, sample_rate=None):
+              target_frames=None, return_prosody=False, sample_rate=None, vocoder=None, griffin_iters=60):
         """reference: tts_king.py:51-57 calls a missing `generate_mel_batch`; here: mel -> float waveform.  A list of texts -> a list
         of float waveforms (1, 1, 256 T_i) on the device: the batched mels go straight into the vocoder's ragged route.  The prosody
         arguments are `generate_mel`'s (`target_frames` frames are 256 * target_frames samples); `return_prosody`: (waveforms, prosody).
-        `sample_rate` (Hz): the waveforms at that rate (`HIFIapi.__call__` / `call_ragged`)."""
+        `sample_rate` (Hz): the waveforms at that rate (`HIFIapi.__call__` / `call_ragged`).  `vocoder`, `griffin_iters`: as in
+        `mel_to_wav`; the Griffin-Lim route returns float waveforms too, hop_length * (T_i - 1) samples each."""
         out = self.generate_mel(text, duration_control, pitch_control, energy_control, speaker, durations=durations, pitch=pitch, energy=energy,
                                 target_frames=target_frames, return_prosody=return_prosody)
         mels, prosody = out if return_prosody else (out, None)
+        voc = self._vocoder(vocoder)
+        extra = dict(griffin_iters=griffin_iters) if isinstance(voc, GriffinLimVocoder) else {}
         if isinstance(text, (list, tuple)):
-            wav = self.vocoder.call_ragged(mels, frames_first=True, sample_rate=sample_rate)
+            wav = voc.call_ragged(mels, frames_first=True, sample_rate=sample_rate, **extra)
         else:
-            wav = self.vocoder(mels.transpose(1, 2), sample_rate=sample_rate)
+            wav = voc(mels.transpose(1, 2), sample_rate=sample_rate, **extra)
         return (wav, prosody) if return_prosody else wav
 
     def _device_features(self):

@@ -18,7 +18,13 @@ launches mel_from_spec_kernel<9> and larger ones <17>.  A signal must be longer 
 vocoder surface, n_fft//2 on Tacotron's) and give one frame, else ValueError.  Amplitude: the signal is scaled by 4096 and rounded to fp16,
 so |y| must stay below MAX_AMPLITUDE = 65520/4096 (just under 16).  `mel_spectrogram` checks that (one reduction and one host read per
 call) and raises ValueError; `TacotronSTFT` keeps the reference's own |y| <= 1 assertion.  Log-mel is within 1e-4 of fp64 on broadband
-input at every such configuration, energy within 1e-4 relative."""
+input at every such configuration, energy within 1e-4 relative.
+
+The way back, mel -> waveform without a vocoder checkpoint, is a second, phase-carrying transform pair in fp32
+on the FFT kernels of csrc/griffinlim.hip: `STFT` (fs_two/audio/stft.py:17-142), `griffin_lim` (audio_processing.py:66-82),
+`mel_to_spec` / `inv_mel_spec` (tools.py:18-34), and `GriffinLimVocoder`, what `TTSKing` runs for `vocoder="griffin_lim"`.  It shares
+the window and the filterbank's packing (`PackedMelFilterbank`) with the extractor above and none of its launches or limits: the
+vocoder takes n_mel_channels up to 1024 and any hop that divides a power-of-two filter_length in 64..2048."""
 import numpy as np
 import torch
 
@@ -51,6 +57,27 @@ def slaney_mel_filterbank(sr, n_fft, n_mels, fmin, fmax):
     return w.astype(np.float32)
 
 
+class PackedMelFilterbank:
+    """The Slaney filterbank (num_mels, n_fft//2 + 1) on the device, each filter as its run of non-zero weights: `vals` (nnz,) fp32,
+    `start` (num_mels,) int32 the first bin of each run, `off` (num_mels + 1,) int32 the runs' offsets into `vals`.  What
+    `ttsk_mel_from_spec` (through `MelExtractor`) and `ttsk_mel_to_spec` read; it has no limits of its own, each user states its."""
+
+    def __init__(self, sampling_rate, n_fft, num_mels, fmin, fmax, device):
+        self.num_mels, self.nbins = int(num_mels), n_fft // 2 + 1
+        fb = slaney_mel_filterbank(sampling_rate, n_fft, num_mels, fmin, fmax)
+        start, off, vals = [], [0], []
+        for m in range(num_mels):
+            nz = np.nonzero(fb[m])[0]
+            lo, hi = (int(nz[0]), int(nz[-1]) + 1) if len(nz) else (0, 0)
+            start.append(lo)
+            vals.append(fb[m, lo:hi])
+            off.append(off[-1] + hi - lo)
+        self.nnz = off[-1]
+        self.vals = torch.from_numpy(np.concatenate(vals) if self.nnz else np.zeros(1, np.float32)).to(device)
+        self.start = torch.tensor(start, dtype=torch.int32, device=device)
+        self.off = torch.tensor(off, dtype=torch.int32, device=device)
+
+
 class MelExtractor:
     """Device-resident bases + the launch sequence.  `pad` samples are reflected on each side; `eps` is added under
     the magnitude's square root (1e-9 in hifi/meldataset.py:69, 0 in fs_two/audio/stft.py:86)."""
@@ -79,19 +106,8 @@ class MelExtractor:
         b_lo = (b - b_hi.float()).half()
         # per tap [hi | lo | hi] against the signal rows' [hi | hi | lo]: one contraction = hi*hi + hi*lo + lo*hi
         self.basis = torch.cat([b_hi, b_lo, b_hi], dim=2).contiguous().to(self.device)      # (cout, taps, 3*hop)
-        # packed mel filterbank
-        fb = slaney_mel_filterbank(sampling_rate, n_fft, num_mels, fmin, fmax)
-        start, off, vals = [], [0], []
-        for m in range(num_mels):
-            nz = np.nonzero(fb[m])[0]
-            lo, hi = (int(nz[0]), int(nz[-1]) + 1) if len(nz) else (0, 0)
-            start.append(lo)
-            vals.append(fb[m, lo:hi])
-            off.append(off[-1] + hi - lo)
-        self.nnz = off[-1]
-        self.fb_vals = torch.from_numpy(np.concatenate(vals) if self.nnz else np.zeros(1, np.float32)).to(self.device)
-        self.fb_start = torch.tensor(start, dtype=torch.int32, device=self.device)
-        self.fb_off = torch.tensor(off, dtype=torch.int32, device=self.device)
+        self.fb = PackedMelFilterbank(sampling_rate, n_fft, num_mels, fmin, fmax, self.device)
+        self.nnz, self.fb_vals, self.fb_start, self.fb_off = self.fb.nnz, self.fb.vals, self.fb.start, self.fb.off
 
     def frames(self, n_samples):
         return 1 + (n_samples + 2 * self.pad - self.n_fft) // self.hop
@@ -135,18 +151,326 @@ def mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin,
     return _extractors[key](y)[0]
 
 
+def _frame_counts(what, lens, Bsz, T):
+    """`lens` (a sequence or tensor of B frame counts, or None) as a list of ints in 1..T."""
+    if lens is None:
+        return None
+    lens = [int(v) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
+    if len(lens) != Bsz or any(not 1 <= v <= T for v in lens):
+        raise ValueError("%s: lens must hold %d frame counts in 1..%d, got %r" % (what, Bsz, T, lens))
+    return lens
+
+
+class STFT:
+    """Drop-in for fs_two/audio/stft.py:17-142 (`STFT(filter_length, hop_length, win_length, window)`, `transform`, `inverse`,
+    `forward`) on the fp32 FFT kernels of csrc/griffinlim.hip, not the conv-GEMM of `MelExtractor`.
+    Accepted: filter_length a power of two in 64..2048, hop_length a divisor of it, 1 <= win_length <= filter_length, window
+    "hann" (periodic, centre-padded, as `MelExtractor` builds it); anything else is a ValueError that names the argument.  The
+    tensors live on the device of the input; the window and the twiddle table (fp64, rounded once) are uploaded once per device."""
+
+    def __init__(self, filter_length, hop_length, win_length, window="hann"):
+        def is_int(v):
+            return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        if not is_int(filter_length) or not 64 <= filter_length <= 2048 or filter_length & (filter_length - 1):
+            raise ValueError("STFT: filter_length must be a power of two in 64..2048, got %r" % (filter_length,))
+        if not is_int(hop_length) or hop_length < 1 or filter_length % hop_length:
+            raise ValueError("STFT: hop_length must be a positive divisor of filter_length = %d, got %r" % (filter_length, hop_length))
+        if not is_int(win_length) or not 1 <= win_length <= filter_length:
+            raise ValueError("STFT: win_length must be in 1..filter_length = %d, got %r" % (filter_length, win_length))
+        if window != "hann":
+            raise ValueError("STFT: window must be 'hann' (periodic Hann, centre-padded to filter_length), got %r" % (window,))
+        self.filter_length, self.hop_length, self.win_length, self.window = int(filter_length), int(hop_length), int(win_length), window
+        self.nbins = self.filter_length // 2 + 1
+        self.pad = self.filter_length // 2
+        win = torch.hann_window(self.win_length, periodic=True, dtype=torch.float64).numpy()
+        lpad = (self.filter_length - self.win_length) // 2
+        self._win = np.pad(win, (lpad, self.filter_length - self.win_length - lpad)).astype(np.float32)
+        ang = 2.0 * np.pi * np.arange(self.filter_length // 2, dtype=np.float64) / self.filter_length
+        self._tw = np.stack([np.cos(ang), -np.sin(ang)], axis=1).astype(np.float32)
+        self._on_device = {}
+
+    def tables(self, device):
+        """(window (n_fft,), twiddle (n_fft/2, 2)) fp32 on `device`."""
+        key = str(device)
+        if key not in self._on_device:
+            self._on_device[key] = (torch.from_numpy(self._win).to(device), torch.from_numpy(self._tw).to(device))
+        return self._on_device[key]
+
+    def min_frames(self):
+        """The fewest frames whose hop_length * (T - 1) samples are longer than the reflect padding."""
+        return self.pad // self.hop_length + 2
+
+    def check_frames(self, what, T, lens=None):
+        for v in [T] + list(lens or []):
+            if self.hop_length * (v - 1) <= self.pad:
+                raise ValueError("%s: %d frames are hop_length * (T - 1) = %d samples, not longer than the reflect padding filter_length / 2 = %d "
+                                 "(at least %d frames)" % (what, v, self.hop_length * (v - 1), self.pad, self.min_frames()))
+
+    def transform(self, input_data, lens=None):
+        """y (B, N) fp32 on the device -> (magnitude, phase), each (B, filter_length/2 + 1, 1 + N // hop_length).  `lens`: samples per
+        row; a row then reflects about its own end and its frames past 1 + lens[b] // hop_length are zeros."""
+        if input_data.dim() != 2 or input_data.dtype != torch.float32:
+            raise ValueError("STFT.transform: input_data must be (B, N) fp32")
+        Bsz, n = input_data.shape
+        if lens is not None:
+            lens = [int(v) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
+            if len(lens) != Bsz or any(not 0 <= v <= n for v in lens):
+                raise ValueError("STFT.transform: lens must hold %d sample counts in 0..%d, got %r" % (Bsz, n, lens))
+        for v in [n] + list(lens or []):
+            if v <= self.pad:
+                raise ValueError("STFT.transform: reflect padding by filter_length / 2 = %d samples needs a signal longer than that, got %d"
+                                 % (self.pad, v))
+        win, tw = self.tables(input_data.device)
+        dl = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=input_data.device)
+        return ops.stft_polar(input_data.contiguous(), dl, self.filter_length, self.hop_length, win, tw)
+
+    def inverse(self, magnitude, phase, lens=None):
+        """(magnitude, phase) (B, filter_length/2 + 1, T) -> (B, 1, hop_length * (T - 1)): inverse real FFT per frame (imaginary parts of
+        DC and Nyquist ignored), window, overlap-add, division by the window's sum of squares where it exceeds float32 tiny, filter_length / 2
+        trimmed from both ends.  `lens`: frames per row; zeros past hop_length * (lens[b] - 1)."""
+        if magnitude.dim() != 3 or magnitude.shape[1] != self.nbins or magnitude.shape != phase.shape or magnitude.shape[2] < 2:
+            raise ValueError("STFT.inverse: magnitude and phase must both be (B, %d, T >= 2), got %s and %s"
+                             % (self.nbins, tuple(magnitude.shape), tuple(phase.shape)))
+        Bsz, _, T = magnitude.shape
+        lens = _frame_counts("STFT.inverse", lens, Bsz, T)
+        win, tw = self.tables(magnitude.device)
+        dl = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=magnitude.device)
+        wav = ops.istft(magnitude.float().contiguous(), phase.float().contiguous(), dl, self.filter_length, self.hop_length, win, tw)
+        return wav.unsqueeze(1)
+
+    def forward(self, input_data):
+        self.magnitude, self.phase = self.transform(input_data)
+        return self.inverse(self.magnitude, self.phase)
+
+    __call__ = forward
+
+
+def griffin_lim(magnitudes, stft_fn, n_iters=30, *, momentum=0.0, phase0=None, seed=None, lens=None):
+    """Drop-in for fs_two/audio/audio_processing.py:66-82 on the device: magnitudes (B, filter_length/2 + 1, T) fp32 -> signal
+    (B, hop_length * (T - 1)) after `n_iters` iterations x <- inverse(magnitudes, phase(transform(x))), one launch each.
+    momentum a in [0, 1): the phase comes from Z - a / (1 + a) Zprev (fast Griffin-Lim, Perraudin et al. 2013); 0 is the reference's
+    iteration.  phase0: the initial phases, a device tensor shaped like `magnitudes`; absent, uniform in [0, 2 pi) from `torch.rand`
+    with a generator seeded by `seed` (None: torch's default generator).  lens: frames per row; a row's frames past its count do not
+    exist for it, and its signal is zero from hop_length * (lens[b] - 1) on."""
+    import math
+    if magnitudes.dim() != 3 or magnitudes.shape[1] != stft_fn.nbins or magnitudes.dtype != torch.float32:
+        raise ValueError("griffin_lim: magnitudes must be (B, %d, T) fp32, got %s %s" % (stft_fn.nbins, tuple(magnitudes.shape), magnitudes.dtype))
+    if not 0.0 <= float(momentum) < 1.0:
+        raise ValueError("griffin_lim: momentum must be in [0, 1), got %r" % (momentum,))
+    if int(n_iters) < 0:
+        raise ValueError("griffin_lim: n_iters must be at least 0, got %r" % (n_iters,))
+    Bsz, nbins, T = magnitudes.shape
+    lens = _frame_counts("griffin_lim", lens, Bsz, T)
+    stft_fn.check_frames("griffin_lim", T, lens)
+    dev = magnitudes.device
+    if phase0 is None:
+        gen = None
+        if seed is not None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed))
+        phase0 = torch.rand(magnitudes.shape, generator=gen, device=dev, dtype=torch.float32) * (2.0 * math.pi)
+    elif phase0.shape != magnitudes.shape or phase0.dtype != torch.float32 or phase0.device != dev:
+        raise ValueError("griffin_lim: phase0 must be an fp32 tensor shaped like magnitudes, on their device")
+    n_fft, hop = stft_fn.filter_length, stft_fn.hop_length
+    win, tw = stft_fn.tables(dev)
+    dl = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=dev)
+    # frame-major copies: a workgroup reads one frame's bins, which are then contiguous
+    m = magnitudes.transpose(1, 2).contiguous().transpose(1, 2)
+    p = phase0.transpose(1, 2).contiguous().transpose(1, 2)
+    cur = ops.istft_frames(m, p, dl, n_fft, hop, win, tw)
+    nxt = torch.empty_like(cur)
+    zprev = torch.zeros(Bsz, T, nbins, 2, dtype=torch.float32, device=dev) if momentum > 0 else None
+    for _ in range(int(n_iters)):
+        ops.griffinlim_step(cur, m, dl, n_fft, hop, win, tw, nxt, zprev, float(momentum))
+        cur, nxt = nxt, cur
+    return ops.istft_ola(cur, dl, hop, win)
+
+
+SPEC_FROM_MEL_SCALING = 1000.0      # fs_two/audio/tools.py:22
+
+
+MAX_MELS_TO_SPEC = 1024            # ttsk_mel_to_spec's limit (FastSpeech2 here goes up to n_mel_channels = 1024)
+
+
+def mel_to_spec(mel, _stft):
+    """log-mel (B, n_mel_channels, T) fp32 on the device -> linear magnitudes (B, filter_length/2 + 1, T): the reference's
+    exp(mel)^T @ mel_basis * 1000 (tools.py:20-25: the transposed filterbank, not a pseudo-inverse), one launch on the packed filterbank
+    `_stft.fb` (a `PackedMelFilterbank`: `TacotronSTFT` and `GriffinLimVocoder` both hold one), n_mel_channels <= 1024."""
+    fb = _stft.fb
+    if mel.dim() != 3 or mel.shape[1] != fb.num_mels or mel.dtype != torch.float32:
+        raise ValueError("mel_to_spec: mel must be (B, %d, T) fp32, got %s %s" % (fb.num_mels, tuple(mel.shape), mel.dtype))
+    return ops.mel_to_spec(mel.contiguous(), fb.vals, fb.start, fb.off, fb.nbins, SPEC_FROM_MEL_SCALING)
+
+
+def inv_mel_spec(mel, out_filename, _stft, griffin_iters=60):
+    """Drop-in for fs_two/audio/tools.py:18-34: log-mel (n_mel_channels, T) -> Griffin-Lim audio written to `out_filename` as a float32
+    wav at `_stft.sampling_rate` (and returned, (hop_length * (T - 1),) on the host).  Two slips of the reference are not reproduced:
+    it drops the last frame (`spec_from_mel[:, :, :-1]`), here all T frames are used; and it reads `_stft._stft_fn`, an attribute that
+    does not exist, here `_stft.stft_fn`."""
+    from scipy.io import wavfile
+    mel = mel.to(_stft.device).float()
+    audio = griffin_lim(mel_to_spec(mel.unsqueeze(0), _stft), _stft.stft_fn, griffin_iters)[0]
+    audio = ops.to_host(audio).numpy()
+    wavfile.write(out_filename, int(_stft.sampling_rate), audio)
+    return audio
+
+
 class TacotronSTFT:
-    """Drop-in for fs_two/audio/stft.py:145-193 (constructor arguments and `mel_spectrogram(y) -> (mel, energy)`)."""
+    """Drop-in for fs_two/audio/stft.py:145-193: constructor arguments, `mel_spectrogram(y) -> (mel, energy)` on the conv-GEMM route
+    of `MelExtractor`, and for the way back `stft_fn` (an `STFT`, built on first use: its envelope is narrower than `MelExtractor`'s),
+    `mel_basis` (dense fp32 on the device), `spectral_normalize` and `spectral_de_normalize`."""
 
     def __init__(self, filter_length, hop_length, win_length, n_mel_channels, sampling_rate, mel_fmin, mel_fmax, device="cuda:0"):
         self.n_mel_channels, self.sampling_rate = n_mel_channels, sampling_rate
+        self.device = torch.device(device)
+        self._stft_args = (filter_length, hop_length, win_length)
+        self._mel_args = (sampling_rate, filter_length, n_mel_channels, mel_fmin, mel_fmax)
         self._ex = MelExtractor(filter_length, n_mel_channels, sampling_rate, hop_length, win_length, mel_fmin, mel_fmax,
                                 pad=filter_length // 2, eps=0.0, device=device)
+        self.fb = self._ex.fb
+
+    @property
+    def stft_fn(self):
+        if not hasattr(self, "_stft_fn"):
+            self._stft_fn = STFT(*self._stft_args)
+        return self._stft_fn
+
+    @property
+    def mel_basis(self):
+        if not hasattr(self, "_mel_basis"):
+            self._mel_basis = torch.from_numpy(slaney_mel_filterbank(*self._mel_args)).to(self.device)
+        return self._mel_basis
+
+    def spectral_normalize(self, magnitudes):
+        return torch.log(torch.clamp(magnitudes, min=1e-5))       # audio_processing.py:85-91
+
+    def spectral_de_normalize(self, magnitudes):
+        return torch.exp(magnitudes)                              # audio_processing.py:94-100
 
     def mel_spectrogram(self, y):
         if float(y.min()) < -1.0 or float(y.max()) > 1.0:      # stft.py:185-186
             raise AssertionError("TacotronSTFT.mel_spectrogram: input outside [-1, 1]")
         return self._ex(y)
+
+
+VOCODERS = ("hifigan", "griffin_lim")
+
+
+def vocoder_name(name, default="hifigan"):
+    """`name` (None: `default`) as one of VOCODERS, or ValueError."""
+    name = default if name is None else name
+    if name not in VOCODERS:
+        raise ValueError("vocoder must be one of %s (or None for the configured one), got %r" % (", ".join(repr(v) for v in VOCODERS), name))
+    return name
+
+
+class GriffinLimVocoder:
+    """mel -> waveform without a checkpoint (`mi355x.vocoder: griffin_lim`, or `vocoder="griffin_lim"` on `TTSKing.mel_to_wav` /
+    `speak`), with `HIFIapi`'s four call forms.  STFT and mel parameters come from preprocess_config.preprocessing (`stft`, `mel`,
+    `audio.sampling_rate`).  Accepted: `STFT`'s envelope (filter_length a power of two in 64..2048, hop_length a divisor of it,
+    1 <= win_length <= filter_length), 1 <= n_mel_channels <= 1024 (`ttsk_mel_to_spec`'s limit), any sampling rate, mel_fmin and
+    mel_fmax; anything else is a ValueError at construction that names the config key.  It holds an `STFT` and a
+    `PackedMelFilterbank` and no `MelExtractor`: that one's narrower envelope (n_mel_channels <= 80, hop_length a multiple of 8)
+    and its conv basis belong to the analysis route, which nothing here launches.
+    log-mel -> `mel_to_spec` -> `griffin_lim` from phases drawn per utterance from `seed` (so a batch row
+    equals its solo run) -> every utterance scaled to a peak of PEAK (Griffin-Lim on the transposed filterbank is not calibrated)
+    -> float, or int16 = trunc(y * 32767).  `sample_rate` goes through the polyphase resampler (tts_king_amd/resample.py)."""
+    PEAK = 0.95
+    INT16_SCALE = 32767.0
+
+    def __init__(self, config, device="cuda:0", seed=None):
+        pp = config.preprocess_config["preprocessing"]
+        mi = (config.get("mi355x", None) if hasattr(config, "get") else None) or {}
+        self.cfg = config
+        self.device = torch.device("cuda:0" if device in ("gpu", None) else device)
+        self.sampling_rate = int(pp["audio"]["sampling_rate"])
+        where = "GriffinLimVocoder (mi355x.vocoder: griffin_lim): preprocess_config.preprocessing."
+        n_mels = pp["mel"]["n_mel_channels"]
+        if not isinstance(n_mels, (int, np.integer)) or isinstance(n_mels, bool) or not 1 <= n_mels <= MAX_MELS_TO_SPEC:
+            raise ValueError("%smel.n_mel_channels must be an integer in 1..%d, got %r" % (where, MAX_MELS_TO_SPEC, n_mels))
+        try:
+            self.stft_fn = STFT(pp["stft"]["filter_length"], pp["stft"]["hop_length"], pp["stft"]["win_length"])
+        except ValueError as e:
+            raise ValueError("%sstft is outside the accepted values: %s" % (where, e)) from None
+        self.n_mel_channels = int(n_mels)
+        self.fb = PackedMelFilterbank(self.sampling_rate, self.stft_fn.filter_length, self.n_mel_channels, pp["mel"]["mel_fmin"],
+                                      pp["mel"]["mel_fmax"], self.device)
+        self.hop = self.stft_fn.hop_length
+        self.seed = int(mi.get("seed", 1234) if seed is None else seed)
+        self.momentum = float(mi.get("griffin_momentum", 0.0))
+        self.output_sample_rate = mi.get("output_sample_rate", None)
+
+    def _rate(self, sample_rate):
+        from . import resample
+        rate = self.output_sample_rate if sample_rate is None else sample_rate
+        return None if rate is None or resample.check_rate(rate) == self.sampling_rate else int(rate)
+
+    def _signals(self, mels, griffin_iters):
+        """mels: a list of (n_mels, T_i) fp32 device tensors -> (y (B, hop * (T_max - 1)) with every row at peak PEAK, samples per row)."""
+        for m in mels:
+            if m.dim() != 2 or m.shape[0] != self.n_mel_channels:
+                raise ValueError("GriffinLimVocoder: every mel must have n_mel_channels = %d channels, got %s" % (self.n_mel_channels, tuple(m.shape)))
+        frames = [int(m.shape[1]) for m in mels]
+        Bsz, T = len(mels), max(frames)
+        self.stft_fn.check_frames("GriffinLimVocoder", T, frames)
+        mel = torch.zeros(Bsz, self.n_mel_channels, T, dtype=torch.float32, device=self.device)
+        phase0 = torch.zeros(Bsz, self.stft_fn.nbins, T, dtype=torch.float32, device=self.device)
+        gen = torch.Generator(device=self.device)
+        for b, m in enumerate(mels):
+            mel[b, :, :frames[b]] = m
+            gen.manual_seed(self.seed)
+            phase0[b, :, :frames[b]] = torch.rand(self.stft_fn.nbins, frames[b], generator=gen, device=self.device) * (2.0 * np.pi)
+        y = griffin_lim(mel_to_spec(mel, self), self.stft_fn, griffin_iters, momentum=self.momentum, phase0=phase0,
+                        lens=frames)
+        peak = y.abs().amax(dim=1, keepdim=True)
+        y = y * torch.where(peak > 0, self.PEAK / peak, torch.zeros_like(peak))
+        return y, [self.hop * (t - 1) for t in frames]
+
+    def _finish(self, y, ns, sample_rate, int16):
+        """The rows of y cut to their ns samples, resampled and converted as asked: a list of (1, 1, n) device tensors."""
+        from . import resample
+        rate = self._rate(sample_rate)
+        if rate is None:
+            out = ops.to_int16(y, self.INT16_SCALE) if int16 else y
+            return [out[b, :n].reshape(1, 1, n) for b, n in enumerate(ns)]
+        filt = resample.filter_for(self.sampling_rate, rate, y.device)
+        segs = resample.segments([b * y.shape[1] for b in range(len(ns))], ns, filt.L, filt.M)
+        out = torch.empty(segs.n_dst, dtype=torch.int16 if int16 else torch.float32, device=y.device)
+        ops.resample(y.contiguous().view(-1), torch.from_numpy(segs.table).to(y.device), filt, out=out,
+                     int16_scale=self.INT16_SCALE if int16 else None)
+        return [out[o:o + n].reshape(1, 1, n) for o, n in segs.spans]
+
+    def _list(self, mels, frames_first):
+        out = []
+        for m in mels:
+            m = torch.as_tensor(m).to(self.device).float()
+            m = m[0] if m.dim() == 3 else m
+            out.append(m.transpose(0, 1) if frames_first else m)
+        return out
+
+    def __call__(self, x, sample_rate=None, griffin_iters=60):
+        """mel (B, n_mels, T) -> float waveforms (B, 1, hop * (T - 1)) on the device (at `sample_rate`: ceil of that times L / M)."""
+        with torch.no_grad():
+            rows = self._finish(*self._signals(self._list(list(x), False), griffin_iters), sample_rate, False)
+            return torch.cat(rows, dim=0)
+
+    def generate(self, mel_specs, sample_rate=None, griffin_iters=60):
+        """mel (B, n_mels, T) -> int16 ndarray (B, 1, hop * (T - 1)) on the host."""
+        with torch.no_grad():
+            rows = self._finish(*self._signals(self._list(list(mel_specs), False), griffin_iters), sample_rate, True)
+            return ops.to_host(torch.cat(rows, dim=0)).numpy()
+
+    def call_ragged(self, mels, frames_first=False, sample_rate=None, griffin_iters=60):
+        """A list of mels of any lengths -> a list of float waveforms (1, 1, hop * (T_i - 1)) on the device: one batch with `lens`,
+        each waveform bit for bit what its mel gives alone."""
+        with torch.no_grad():
+            return self._finish(*self._signals(self._list(mels, frames_first), griffin_iters), sample_rate, False)
+
+    def generate_ragged(self, mels, frames_first=False, sample_rate=None, griffin_iters=60):
+        """`call_ragged` as int16 ndarrays on the host."""
+        with torch.no_grad():
+            rows = self._finish(*self._signals(self._list(mels, frames_first), griffin_iters), sample_rate, True)
+            return [ops.to_host(r).numpy() for r in rows]
 
 
 class PitchExtractor:

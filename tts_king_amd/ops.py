@@ -2101,6 +2101,119 @@ def mel_from_spec(spec, Bsz, rows, T, nbins, vals, start, off, nnz, n_mels, eps,
     return mel, energy
 
 
+# ---------------------------------------------------------------------------------------------------- Griffin-Lim
+
+def _gl_f32(what, **tensors):
+    for name, t in tensors.items():
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise L.TtskError("%s: %s must be a contiguous fp32 tensor" % (what, name))
+
+
+def _gl_lens(what, lens, Bsz):
+    if lens is not None and (lens.dtype != torch.int32 or lens.dim() != 1 or lens.numel() != Bsz or not lens.is_contiguous()):
+        raise L.TtskError("%s: lens must be a contiguous int32 tensor of %d entries" % (what, Bsz))
+
+
+def _gl_polar(what, mag, other=None):
+    """(sB, sk, st) of a (B, bins, T) fp32 tensor in any layout; `other` must share shape and strides."""
+    def strides(t):          # the stride of an axis of one element is arbitrary and never used
+        return tuple(s if n > 1 else 0 for s, n in zip(t.stride(), t.shape))
+    if mag.dim() != 3 or mag.dtype != torch.float32 or (other is not None and (other.dtype != torch.float32 or other.shape != mag.shape or
+                                                                                 strides(other) != strides(mag))):
+        raise L.TtskError("%s: needs (B, bins, T) fp32 tensors of one shape and layout" % what)
+    return tuple(max(s, 1) for s in strides(mag))
+
+
+def stft_polar(wav, lens, n_fft, hop, window, twiddle):
+    """wav (B, N) fp32, lens int32 (B,) samples per row or None -> (magnitude, phase) (B, n_fft/2 + 1, 1 + N // hop) (include/ttsk.h)."""
+    _dev(wav, lens, window, twiddle)
+    _gl_f32("stft_polar", wav=wav, window=window, twiddle=twiddle)
+    Bsz, n = wav.shape
+    _gl_lens("stft_polar", lens, Bsz)
+    T = 1 + n // hop
+    mag = torch.empty(Bsz, n_fft // 2 + 1, T, dtype=torch.float32, device=wav.device)
+    phase = torch.empty_like(mag)
+    _count("stft_polar")
+    check(L.load().ttsk_stft_polar(_ptr(wav), _ptr(lens), Bsz, n, n_fft, hop, _ptr(window), _ptr(twiddle), _ptr(mag), _ptr(phase), T, _stream()),
+          "ttsk_stft_polar")
+    return mag, phase
+
+
+def istft_frames(mag, phase, lens, n_fft, hop, window, twiddle):
+    """mag, phase (B, n_fft/2 + 1, T) fp32 in any (shared) layout, lens int32 (B,) frames per row or None -> windowed frames (B, T, n_fft)."""
+    _dev(mag, phase, lens, window, twiddle)
+    sB, sk, st = _gl_polar("istft_frames", mag, phase)
+    Bsz, _, T = mag.shape
+    _gl_lens("istft_frames", lens, Bsz)
+    out = torch.empty(Bsz, T, n_fft, dtype=torch.float32, device=mag.device)
+    _gl_f32("istft_frames", window=window, twiddle=twiddle)
+    _count("istft_frames")
+    check(L.load().ttsk_istft_frames(_ptr(mag), _ptr(phase), sB, sk, st, _ptr(lens), Bsz, T, n_fft, hop, _ptr(window), _ptr(twiddle), _ptr(out),
+                                     _stream()), "ttsk_istft_frames")
+    return out
+
+
+def istft_ola(frames, lens, hop, window):
+    """windowed frames (B, T, n_fft) -> wav (B, hop * (T - 1)): overlap-add as a gather, window-sum division, ends trimmed; zeros past a row."""
+    _dev(frames, lens, window)
+    _gl_f32("istft_ola", frames=frames, window=window)
+    Bsz, T, n_fft = frames.shape
+    _gl_lens("istft_ola", lens, Bsz)
+    wav = torch.empty(Bsz, hop * (T - 1), dtype=torch.float32, device=frames.device)
+    _count("istft_ola")
+    check(L.load().ttsk_istft_ola(_ptr(frames), _ptr(lens), Bsz, T, n_fft, hop, _ptr(window), _ptr(wav), _stream()), "ttsk_istft_ola")
+    return wav
+
+
+def istft(mag, phase, lens, n_fft, hop, window, twiddle):
+    """`istft_frames` then `istft_ola` through ttsk_istft: (B, n_fft/2 + 1, T) -> wav (B, hop * (T - 1))."""
+    _dev(mag, phase, lens, window, twiddle)
+    sB, sk, st = _gl_polar("istft", mag, phase)
+    _gl_f32("istft", window=window, twiddle=twiddle)
+    Bsz, _, T = mag.shape
+    _gl_lens("istft", lens, Bsz)
+    work = torch.empty(Bsz, T, n_fft, dtype=torch.float32, device=mag.device)
+    wav = torch.empty(Bsz, hop * max(T - 1, 0), dtype=torch.float32, device=mag.device)
+    _count("istft")
+    check(L.load().ttsk_istft(_ptr(mag), _ptr(phase), sB, sk, st, _ptr(lens), Bsz, T, n_fft, hop, _ptr(window), _ptr(twiddle), _ptr(work),
+                              _ptr(wav), _stream()), "ttsk_istft")
+    return wav
+
+
+def griffinlim_step(src, mag, lens, n_fft, hop, window, twiddle, out, zprev=None, momentum=0.0):
+    """One Griffin-Lim iteration (include/ttsk.h).  src: the signal (B, >= hop * (T - 1)) or the previous step's frames (B, T, n_fft);
+    mag (B, n_fft/2 + 1, T) in any layout; out: frames (B, T, n_fft), another buffer than src; zprev (B, T, n_fft/2 + 1, 2) with momentum > 0."""
+    _dev(src, mag, lens, window, twiddle, out, zprev)
+    sB, sk, st = _gl_polar("griffinlim_step", mag)
+    Bsz, _, T = mag.shape
+    _gl_lens("griffinlim_step", lens, Bsz)
+    _gl_f32("griffinlim_step", src=src, window=window, twiddle=twiddle, out=out, zprev=zprev)
+    if tuple(out.shape) != (Bsz, T, n_fft) or (zprev is not None and tuple(zprev.shape) != (Bsz, T, n_fft // 2 + 1, 2)):
+        raise L.TtskError("griffinlim_step: out must be (B, T, n_fft) and zprev (B, T, n_fft/2 + 1, 2)")
+    from_frames = src.dim() == 3
+    if (from_frames and src.shape != out.shape) or (not from_frames and (src.dim() != 2 or src.shape[0] != Bsz)):
+        raise L.TtskError("griffinlim_step: src must be frames (B, T, n_fft) or a signal (B, samples)")
+    _count("griffinlim_step")
+    check(L.load().ttsk_griffinlim_step(None if from_frames else _ptr(src), 0 if from_frames else src.shape[1], _ptr(src) if from_frames else None,
+                                        _ptr(mag), sB, sk, st, _ptr(lens), _ptr(zprev), float(momentum), Bsz, T, n_fft, hop, _ptr(window),
+                                        _ptr(twiddle), _ptr(out), _stream()), "ttsk_griffinlim_step")
+    return out
+
+
+def mel_to_spec(mel, vals, start, off, nbins, scale=1000.0):
+    """log-mel (B, n_mels, T) fp32, the packed filterbank of `MelExtractor` -> (B, nbins, T) = scale * exp(mel)^T @ filterbank, transposed."""
+    _dev(mel, vals, start, off)
+    _gl_f32("mel_to_spec", mel=mel, vals=vals)
+    if mel.dim() != 3 or start.dtype != torch.int32 or off.dtype != torch.int32 or off.numel() != mel.shape[1] + 1 or start.numel() != mel.shape[1]:
+        raise L.TtskError("mel_to_spec: mel must be (B, n_mels, T) with int32 tables of n_mels starts and n_mels + 1 offsets")
+    Bsz, n_mels, T = mel.shape
+    spec = torch.empty(Bsz, nbins, T, dtype=torch.float32, device=mel.device)
+    _count("mel_to_spec")
+    check(L.load().ttsk_mel_to_spec(_ptr(mel), _ptr(vals), _ptr(start), _ptr(off), Bsz, n_mels, nbins, T, float(scale), _ptr(spec), _stream()),
+          "ttsk_mel_to_spec")
+    return spec
+
+
 def yin_lags(sr, f0_floor, f0_ceil):
     """(tau_min, tau_max) = (ceil(sr / f0_ceil), floor(sr / f0_floor)): the lags `pitch_yin` scans."""
     import math
