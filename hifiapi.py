@@ -127,3 +127,36 @@ class HIFIapi:
             host = None if flat is None else ops.to_host(flat).numpy()              # one D2H copy; its shape repeats with N
             short = {i: ops.to_host(y).numpy() for i, y in short.items()}
         return resample.split(host, plan, spf, short)
+
+    def output_rate(self, sample_rate=None):
+        """The rate (Hz) of what a call with `sample_rate` returns."""
+        rate = self._rate(sample_rate)
+        return int(self.cfg.hifi.sampling_rate) if rate is None else rate
+
+    def _joined(self, mels, join, frames_first, sample_rate, scale):
+        self.model.eval()
+        rate = self._rate(sample_rate)
+        with torch.no_grad():
+            if self._synth is not None:
+                return self._synth.wav_joined(mels, join, frames_first, scale, rate)
+            return self.model.forward_joined(mels, join, frames_first, scale, rate)
+
+    def call_joined(self, mels, join, frames_first=False, sample_rate=None):
+        """The mels of `call_ragged` as ONE float waveform (1, 1, total) on the device, joined there by `join` (a
+        `tts_king_amd.narrate.Join`: per utterance trim, level, fade, pause; `Generator.forward_joined`, with `hip_graph` part of the
+        ragged graph) -> (waveform, `narrate.Info`: every utterance's kept range, place, peak and gain, read from the device table)."""
+        from tts_king_amd import narrate
+        mels = list(mels)
+        out, info, _ = self._joined(mels, join, frames_first, sample_rate, None)
+        info = narrate.Info(ops.to_host(info).numpy(), len(mels))
+        return out[:info.total].clone().reshape(1, 1, info.total), info
+
+    def generate_joined(self, mels, join, frames_first=False, sample_rate=None):
+        """`call_joined` as an int16 ndarray (1, 1, total) on the host (saturating): the join's launch converts, and the waveform
+        crosses to the host in one copy, the table in another of 32 bytes per utterance."""
+        from tts_king_amd import narrate
+        mels = list(mels)
+        out, info, _ = self._joined(mels, join, frames_first, sample_rate, float(self.cfg.hifi.MAX_WAV_VALUE))
+        host = ops.to_host(out).numpy()
+        info = narrate.Info(ops.to_host(info).numpy(), len(mels))
+        return host[:info.total].reshape(1, 1, info.total), info

@@ -529,6 +529,41 @@ int ttsk_resample_tile(int L, int M, int P);
 int ttsk_resample(const float* src, int64_t n_src, const int32_t* segs, int n_segs, const float* table, int L, int M, int P, int C,
                   void* dst, int64_t n_dst, int to_i16, float scale, void* stream);
 
+/* ------------------------------------------------------------------------------------ utterances joined into one waveform
+ * U utterances that lie in one flat fp32 buffer (what ttsk_wav_stitch or ttsk_resample wrote, or the rows of a padded batch) trimmed,
+ * levelled, faded and laid out behind each other with pauses between, as ONE waveform (tts_king_amd/narrate.py plans it; DESIGN.md
+ * section 22).  Everything that depends on a length or a setting is data: the device-resident join table, (1 + U) rows of
+ * TTSK_JOIN_ROW 32-bit words, 16-byte aligned.  Row 0 holds the settings:
+ *   [0] mode    TTSK_JOIN_GIVEN / _RMS / _PEAK            [1] fade    samples of the linear fade at either end of a kept range
+ *   [2] keep    samples kept outside first / last          [3] lead    zeros before the first utterance
+ *   [4] r       fp32: threshold as a fraction of the peak  [5] floor   fp32: the threshold's lower bound
+ *   [6] target  fp32: RMS aimed at (mode _RMS)             [7] limit   fp32: peak never exceeded (modes _RMS, _PEAK)
+ * and row 1 + u is utterance u:
+ *   [0] src_off first sample in src   [1] src_len samples (0: an empty row, e.g. padding)   [2] pause  zeros behind it
+ *   [3] flags   bit 0: trim           [4] gain    fp32, mode _GIVEN                          [5..7] zero
+ * With x the row's n samples, all in fp32 and in this order: peak = max |x[i]|; with the trim flag thr = max(peak * r, floor), first /
+ * last = the first / last i with |x[i]| >= thr, kept range a = max(0, first - keep), b = min(n, last + 1 + keep), empty (a = b = 0)
+ * when there is no such i or peak == 0; without the flag a = 0, b = n.  ss = sum of x[i]^2 over [a, b), rms = sqrt(ss / (b - a)).
+ * g = the row's gain (_GIVEN), min(target / rms, limit / peak) (_RMS), limit / peak (_PEAK); 1 when the range is empty or peak == 0.
+ * F = min(fade, (b - a) / 2); w(k) = float(2k + 1) / float(2F) over the first F kept samples, mirrored over the last F, 1 between.
+ * o_u = lead + sum over v < u of (b_v - a_v + pause_v);  dst[o_u + k] = (x[a + k] * g) * w(k);  total = o_U.  EVERY sample of dst
+ * is written: zeros in the lead, the pauses and from `total` to n_dst.  Samples that would lie at or past n_dst are dropped.
+ * to_i16 = 0: fp32; 1: int16 = (int)clamp(y * scale, -32768, 32767), ttsk_resample's rule.
+ * Negative fade / keep / lead / pause count as 0; a row that does not fit n_src counts as empty (its pause stays).
+ * info: (U + 1) rows of TTSK_JOIN_ROW 32-bit words, 16-byte aligned, written by the kernels for the host to read with the waveform:
+ *   row u:  [0] a  [1] b  [2] o_u  [3] peak (fp32)  [4] ss (fp32)  [5] g (fp32)  [6..7] zero;     row U:  [0] total, rest zero
+ * (o_u and total saturate at 2^31 - 1).  wav_join_stats: one launch, U workgroups, writes a, b, peak, ss, g.  wav_join: one launch,
+ * one workgroup per tile of dst, reads what wav_join_stats left in `info`, writes o_u, total and dst.  No atomics: the same bits on
+ * every run.  U <= TTSK_JOIN_MAX_ROWS, n_src and n_dst below 2^31. */
+#define TTSK_JOIN_ROW 8
+#define TTSK_JOIN_MAX_ROWS 4096
+#define TTSK_JOIN_GIVEN 0
+#define TTSK_JOIN_RMS 1
+#define TTSK_JOIN_PEAK 2
+int ttsk_wav_join_stats(const float* src, int64_t n_src, const int32_t* join, int U, int32_t* info, void* stream);
+int ttsk_wav_join(const float* src, int64_t n_src, const int32_t* join, int U, int32_t* info, void* dst, int64_t n_dst, int to_i16,
+                  float scale, void* stream);
+
 /* ------------------------------------------------------------------------------------ device-resident training set
  * One launch builds one packed training batch (the buffer of tts_king_amd/dataset.py `packed_layout`: what the DeviceFeeder uploads
  * for the same utterances) from a training set that lives on the device (tts_king_amd/resident.py).  The

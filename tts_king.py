@@ -102,6 +102,48 @@ class TTSKing:
             wav = voc(mels.transpose(1, 2), sample_rate=sample_rate, **extra)
         return (wav, prosody) if return_prosody else wav
 
+    def narrate(self, text, speaker=0, duration_control=1.0, pitch_control=1.0, energy_control=1.0, pauses=None, trim_db=-45.0,
+                trim_keep_ms=15.0, fade_ms=5.0, normalize="rms", target_db=-23.0, peak_limit=0.95, sample_rate=None, vocoder=None,
+                griffin_iters=60, return_timing=False):
+        """A paragraph in one call -> int16 ndarray (1, 1, total): the text cut into sentences (tts_king_amd/narrate.py: at . ? ! … ; :
+        outside {...}, a piece of more than 200 phonemes also at its commas; a list of strings or phoneme-id arrays is taken as
+        already split), the sentences synthesized as batches of at most `mi355x.narrate_batch` (32) through `generate_mel([...])` and
+        the vocoder's ragged route, and joined on the device: per sentence the silence at either end below
+        `trim_db` dB of the sentence's peak is cut but for `trim_keep_ms`, the level is set (`normalize`: "rms" = `target_db` dB RMS
+        re full scale under a peak of `peak_limit`, "peak" = a peak of `peak_limit`, None = left as it is), both cuts get a linear
+        fade of `fade_ms`, and a pause follows: 400 ms after . ? ! …, 250 ms after ; :, 120 ms after a comma cut
+        (`mi355x.narrate_pauses`: {end, half, comma} in ms), or `pauses` = one number of ms or one per sentence.  Pauses and the
+        other times are samples at the OUTPUT rate (`sample_rate`, as in `mel_to_wav`).  `trim_db=None` / `normalize=None` switch
+        those steps off.  `speaker` and the three controls may be lists, one per sentence.  `return_timing`: also a list of
+        (start_sample, end_sample) per sentence, in the order given.  A text that yields no sentence raises ValueError."""
+        from tts_king_amd import batching, narrate
+        mi = self.cfg.get("mi355x", None) or {}
+        voc = self._vocoder(vocoder)
+        extra = dict(griffin_iters=griffin_iters) if isinstance(voc, GriffinLimVocoder) else {}
+        count = lambda piece: int(np.asarray(self.text_preprocess(piece)).size)
+        max_ph = min(narrate.MAX_PHONEMES, int(self.tts.model.max_seq_len))
+        pieces, marks = narrate.split_text(text, max_ph, count)
+        n = len(pieces)
+        if n == 0:
+            raise ValueError("narrate: the text yields no sentence")
+        rate = voc.output_rate(sample_rate)
+        join = narrate.Join(narrate.settings(rate, trim_db, trim_keep_ms, fade_ms, normalize, target_db, peak_limit),
+                            narrate.pause_plan(marks, rate, pauses, mi.get("narrate_pauses", None)))
+        per = lambda v, name: v if np.ndim(v) == 0 else list(batching.per_utterance_names(v, n, name))
+        spk = per(speaker, "speaker")
+        ctl = [per(c, name) for c, name in ((duration_control, "duration_control"), (pitch_control, "pitch_control"),
+                                            (energy_control, "energy_control"))]
+        cut = lambda v, lo, hi: v[lo:hi] if isinstance(v, list) else v
+        wavs, timing, base = [], [], 0
+        for lo, hi in narrate.groups(n, int(mi.get("narrate_batch", narrate.BATCH))):
+            mels = self.generate_mel(pieces[lo:hi], *[cut(c, lo, hi) for c in ctl], speaker=cut(spk, lo, hi))
+            wav, info = voc.generate_joined(mels, join.part(lo, hi), frames_first=True, sample_rate=sample_rate, **extra)
+            wavs.append(wav)
+            timing += [(base + s, base + e) for s, e in info.timing()]
+            base += info.total
+        wav = wavs[0] if len(wavs) == 1 else np.concatenate(wavs, axis=2)
+        return (wav, timing) if return_timing else wav
+
     def _device_features(self):
         import json
         import os

@@ -472,6 +472,48 @@ class GriffinLimVocoder:
             rows = self._finish(*self._signals(self._list(mels, frames_first), griffin_iters), sample_rate, True)
             return [ops.to_host(r).numpy() for r in rows]
 
+    def output_rate(self, sample_rate=None):
+        """The rate (Hz) of what a call with `sample_rate` returns."""
+        rate = self._rate(sample_rate)
+        return self.sampling_rate if rate is None else rate
+
+    def _joined(self, mels, join, frames_first, sample_rate, griffin_iters, int16):
+        """The padded batch of `_signals` (resampled row by row when asked) joined by `join` (`narrate.Join`): (out, info) on the device."""
+        from . import narrate, resample
+        mels = self._list(mels, frames_first)
+        if len(join) != len(mels):
+            raise ValueError("GriffinLimVocoder: the join names %d utterances, the call has %d" % (len(join), len(mels)))
+        y, ns = self._signals(mels, griffin_iters)
+        offs, src = [b * y.shape[1] for b in range(len(ns))], y.contiguous().view(-1)
+        rate = self._rate(sample_rate)
+        if rate is not None:
+            filt = resample.filter_for(self.sampling_rate, rate, y.device)
+            segs = resample.segments(offs, ns, filt.L, filt.M)
+            src = ops.resample(src, torch.from_numpy(segs.table).to(y.device), filt,
+                               out=torch.empty(max(segs.n_dst, 1), dtype=torch.float32, device=y.device))
+            offs, ns = [o for o, _ in segs.spans], [n for _, n in segs.spans]
+        table = join.table(offs, ns)
+        return ops.wav_join(src, torch.from_numpy(table).to(y.device), n_dst=max(narrate.out_bound(table), 1),
+                            int16_scale=self.INT16_SCALE if int16 else None)
+
+    def call_joined(self, mels, join, frames_first=False, sample_rate=None, griffin_iters=60):
+        """The waveforms of `call_ragged` as ONE float waveform (1, 1, total) on the device, joined there by `join` (a `narrate.Join`:
+        per utterance trim, level, fade, pause) -> (waveform, `narrate.Info`)."""
+        from . import narrate
+        with torch.no_grad():
+            out, info = self._joined(mels, join, frames_first, sample_rate, griffin_iters, False)
+            info = narrate.Info(ops.to_host(info).numpy(), len(join))
+            return out[:info.total].reshape(1, 1, info.total), info
+
+    def generate_joined(self, mels, join, frames_first=False, sample_rate=None, griffin_iters=60):
+        """`call_joined` as an int16 ndarray (1, 1, total) on the host, saturating at +-32767 / 32768 of INT16_SCALE."""
+        from . import narrate
+        with torch.no_grad():
+            out, info = self._joined(mels, join, frames_first, sample_rate, griffin_iters, True)
+            host = ops.to_host(out).numpy()
+            info = narrate.Info(ops.to_host(info).numpy(), len(join))
+            return host[:info.total].reshape(1, 1, info.total), info
+
 
 class PitchExtractor:
     """F0 per frame on the device by YIN (`ops.pitch_yin`): frame t is centred on sample t * hop_length, the

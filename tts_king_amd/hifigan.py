@@ -609,3 +609,51 @@ class Generator(nn.Module):
         mels = list(mels)
         flat, plan, spf = self.forward_ragged_flat(mels, frames_first, sample_rate=sample_rate)
         return resample.split(flat, plan, spf, self.forward_short(mels, plan, frames_first, sample_rate=sample_rate))
+
+    @staticmethod
+    def join_spans(plan, spf, flat_samples, short):
+        """Where the call's utterances lie for the join, in the call's order: (offsets, lengths) in samples of the flat buffer followed
+        by the waveforms of `short` = {index: waveform} in the order of their indices (`torch.cat`).  A resampled plan (`plan.segs`)
+        gives its destination columns."""
+        offs, lens = [0] * len(plan.lens), [0] * len(plan.lens)
+        if plan.segs is not None:
+            for i, (o, m) in zip(plan.planned, plan.segs.spans):
+                offs[i], lens[i] = o, m
+        else:
+            for i in plan.planned:
+                offs[i], lens[i] = plan.offsets[i] * spf, plan.lens[i] * spf
+        pos = int(flat_samples)
+        for i in sorted(short):
+            offs[i], lens[i] = pos, int(short[i].numel())
+            pos += lens[i]
+        return offs, lens
+
+    def forward_joined(self, mels, join, frames_first=False, int16_scale=None, sample_rate=None):
+        """The utterances of `forward_ragged` as ONE waveform (tts_king_amd/narrate.py): `forward_ragged_flat` in fp32,
+        then the two join launches on the flat buffer by `join` (a `narrate.Join`: settings, pauses, gains), which trim, level, fade
+        and lay the utterances out behind each other in the call's order.  -> (out, info, bound): `out` the flat waveform, fp32 or
+        with `int16_scale` saturated int16, `bound` = `narrate.out_bound` samples of which the first `info[U, 0]` are the waveform and
+        the rest zeros; `info` the (U + 1, 8) int32 device table (`narrate.Info`).  With `sample_rate` the resampled buffer is joined
+        by the segment table's destination columns.  Utterances that a generator without `short_rows()` vocodes alone are placed
+        behind the flat buffer before the join: the same two launches."""
+        mels = list(mels)
+        if len(join) != len(mels):
+            raise ValueError("forward_joined: the join names %d utterances, the call has %d" % (len(join), len(mels)))
+        flat, plan, spf = self.forward_ragged_flat(mels, frames_first, None, sample_rate)
+        short = {}
+        if any(plan.lens[i] > 0 for i in plan.short):
+            short = self.forward_short(mels, plan, frames_first, None, sample_rate=sample_rate)
+        return self.join_flat(flat, plan, spf, short, join, int16_scale)
+
+    def join_flat(self, flat, plan, spf, short, join, int16_scale=None, rows=None):
+        """The join of `forward_joined` on a flat fp32 buffer that `forward_ragged_flat` (or a replayed graph) left, plus `short`."""
+        from . import narrate
+        dev = self.conv_pre.bias.device
+        offs, lens = self.join_spans(plan, spf, 0 if flat is None else flat.numel(), short)
+        with torch.no_grad():
+            parts = ([] if flat is None else [flat]) + [short[i].reshape(-1) for i in sorted(short)]
+            src = parts[0] if len(parts) == 1 else torch.cat(parts) if parts else torch.zeros(1, dtype=torch.float32, device=dev)
+            table = join.table(offs, lens, rows)
+            bound = narrate.out_bound(table)
+            out, info = ops.wav_join(src, torch.from_numpy(table).to(dev), n_dst=max(bound, 1), int16_scale=int16_scale)
+        return out, info, bound

@@ -1326,6 +1326,56 @@ def resample(x_flat, segs, filt, out=None, int16_scale=None):
     return out
 
 
+def _join_args(what, x_flat, join, info):
+    """The checks `wav_join_stats` and `wav_join` share; returns (U, info), `info` allocated when None."""
+    from .narrate import MAX_ROWS, ROW
+    _dev(x_flat, join, info)
+    if (x_flat.dtype != torch.float32 or not x_flat.is_contiguous() or x_flat.dim() != 1 or join.dtype != torch.int32 or not join.is_contiguous() or
+            join.dim() != 2 or join.shape[1] != ROW or join.shape[0] < 2):
+        raise L.TtskError("%s: needs a contiguous flat fp32 source and a contiguous (1 + rows, %d) int32 join table (narrate.join_table)" % (what, ROW))
+    U = join.shape[0] - 1
+    if U > MAX_ROWS or not 0 < x_flat.numel() < 2 ** 31:
+        raise L.TtskError("%s: %d rows (at most %d) over a source of %d samples (1 .. 2^31 - 1)" % (what, U, MAX_ROWS, x_flat.numel()))
+    if info is None:
+        info = torch.empty(U + 1, ROW, dtype=torch.int32, device=x_flat.device)
+    elif info.dtype != torch.int32 or not info.is_contiguous() or tuple(info.shape) != (U + 1, ROW):
+        raise L.TtskError("%s: `info` must be a contiguous (%d, %d) int32 device tensor" % (what, U + 1, ROW))
+    return U, info
+
+
+def wav_join_stats(x_flat, join, info=None):
+    """The statistics launch of `wav_join` alone: x_flat contiguous fp32 (utterances wherever `join` puts them), join the (1 + U, 8)
+    int32 device table of tts_king_amd/narrate.py (`join_table`: row 0 the settings, then one row per utterance) -> `info`, (U + 1, 8)
+    int32 on the device with every row's kept range [a, b), peak, sum of squares and gain (include/ttsk.h; `narrate.read_info`
+    decodes a host copy).  The layout columns (o_u, total) are written by `wav_join`."""
+    U, info = _join_args("wav_join_stats", x_flat, join, info)
+    _count("wav_join_stats")
+    check(L.load().ttsk_wav_join_stats(_ptr(x_flat), x_flat.numel(), _ptr(join), U, _ptr(info), _stream()), "ttsk_wav_join_stats")
+    return info
+
+
+def wav_join(x_flat, join, n_dst=None, out=None, info=None, int16_scale=None):
+    """The U utterances of `x_flat` that the join table names, trimmed, levelled, faded and laid out behind each other with their pauses
+    as ONE waveform (two launches, no host synchronisation; tts_king_amd/narrate.py) -> (out, info): `out` a flat
+    buffer of `n_dst` samples (or the `out` given), EVERY sample written, zeros from the waveform's end (`info[U, 0]`) on: fp32, or
+    int16 = clamp(y * int16_scale, -32768, 32767) truncated toward zero; `info` as in `wav_join_stats` plus every row's first output
+    sample and the total.  `n_dst` is the caller's bound (`narrate.out_bound`): samples past it are dropped."""
+    U, info = _join_args("wav_join", x_flat, join, info)
+    i16 = int16_scale is not None
+    dt = torch.int16 if i16 else torch.float32
+    if out is None:
+        if n_dst is None or not 0 < int(n_dst) < 2 ** 31:
+            raise L.TtskError("wav_join: needs `out` or its size n_dst (1 .. 2^31 - 1), got %r" % (n_dst,))
+        out = torch.empty(int(n_dst), dtype=dt, device=x_flat.device)
+    elif out.dtype != dt or not out.is_contiguous() or not out.is_cuda or not 0 < out.numel() < 2 ** 31:
+        raise L.TtskError("wav_join: `out` must be a contiguous %s device tensor of 1 .. 2^31 - 1 samples" % dt)
+    wav_join_stats(x_flat, join, info)
+    _count("wav_join")
+    check(L.load().ttsk_wav_join(_ptr(x_flat), x_flat.numel(), _ptr(join), U, _ptr(info), _ptr(out), out.numel(), int(i16),
+                                 float(int16_scale or 0.0), _stream()), "ttsk_wav_join")
+    return out, info
+
+
 def collate_batch(table, n_fields, idx_dev, idx_host, n_utts, out, fl_off=-1, t_true=0, pl_off=-1, l_true=0):
     """One packed training batch gathered from a device-resident set (tts_king_amd/resident.py): `table` = a `lib.CollateField` array of
     `n_fields` rows (include/ttsk.h: where each field's flat array and per-utterance offset / length tables live, and where the field

@@ -227,6 +227,63 @@ class GraphedSynthesizer:
         return resample.split(flat, plan, spf, short)
 
     @torch.no_grad()
+    def wav_joined(self, mels, join, frames_first=False, int16_scale=None, sample_rate=None):
+        """`Generator.forward_joined` on the ragged graph: gather -> generator -> stitch (-> resample) -> the two join launches, with the
+        join table (`narrate.Join.table`, padded to the plan's N rows: an utterance has at least one window) as one more static
+        input.  The key is `wav_ragged_flat`'s (N[, rate]) plus the join flag, the output type and the pause budget: the output
+        buffer holds the flat buffer's samples plus lead and pauses rounded up to a whole number of N seconds, so that sentence
+        lengths, pauses up to a second each, gains and settings are all data and capture nothing.  -> (out, info, bound) as
+        `forward_joined`; after a replay both are the graph's own, valid until the next call with the same key.
+        A call with an utterance outside the windowed batch (a generator without `short_rows()`) launches plainly."""
+        gen = self.vocoder
+        mels = list(mels)
+        if len(join) != len(mels):
+            raise ValueError("wav_joined: the join names %d utterances, the call has %d" % (len(join), len(mels)))
+        m2, lens = gen.ragged_mels(mels, frames_first)
+        plan = gen.plan(lens)
+        if not self.graphs or not plan.planned or plan.short:
+            return gen.forward_joined(mels, join, frames_first, int16_scale, sample_rate)
+        spf = gen.samples_per_frame()
+        rl = plan.has_short_rows
+        sc = None if int16_scale is None else float(int16_scale)
+        filt = gen.resampler(sample_rate)
+        table = torch.from_numpy(plan.table)
+        flat_cap, rate = plan.N * plan.W * spf, int(windows._get(gen.h, "sampling_rate"))
+        extra = []
+        if filt is not None:
+            extra = [torch.from_numpy(gen.plan_resample(plan, filt).table)]
+            flat_cap, rate = resample.out_bound(flat_cap, plan.N, filt.L, filt.M), int(sample_rate)
+        unit = plan.N * rate
+        budget = max(1, -(-join.pause_total() // unit)) * unit
+        cap = flat_cap + budget
+        jt = torch.from_numpy(join.table(*gen.join_spans(plan, spf, 0, {}), rows=plan.N))
+        key = ("rag", plan.N, plan.W, bool(frames_first), None) + (("rows",) if rl else ()) + (("rate", rate) if filt is not None else ())
+        key += ("join", sc, budget)
+        g = self._rag.get(key)
+        if g is None:
+            stage = gen.stage_mels(m2, plan, frames_first)
+            dev = stage.device
+            if filt is None:
+                fn = lambda st, tb, jn: ops.wav_join(gen.forward_windows(st, tb, frames_first, None, rl), jn, n_dst=cap, int16_scale=sc)
+            else:
+                fn = lambda st, tb, sgt, jn: ops.wav_join(gen.forward_windows(st, tb, frames_first, None, rl, sample_rate, sgt), jn, n_dst=cap,
+                                                          int16_scale=sc)
+            inputs = [stage, table.to(dev)] + [t.to(dev) for t in extra] + [jt.to(dev)]
+            if key not in self._seen:                      # first sight: eager (lazy allocations, weight packing)
+                self._seen.add(key)
+                return fn(*inputs) + (cap,)
+            if len(self._rag) >= self.max_graphs:
+                self._rag.pop(next(iter(self._rag)))
+            torch.cuda.synchronize()
+            g = self._rag[key] = _Graph(fn, inputs)
+        else:
+            gen.stage_mels(m2, plan, frames_first, g.static[0])
+            for dst, src in zip(g.static[1:], [table] + extra + [jt]):
+                dst.copy_(src, non_blocking=True)
+        g.graph.replay()
+        return g.out + (cap,)
+
+    @torch.no_grad()
     def wav_ragged_flat(self, mels, frames_first=False, int16_scale=None, sample_rate=None):
         """The windowed part of `wav_ragged`: (flat buffer of N * W * 256 samples or None when no utterance fills a window, plan, samples
         per frame).  After a replay the buffer is the graph's own: valid until the next call with the same N.
