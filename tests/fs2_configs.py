@@ -1,10 +1,10 @@
 """The FastSpeech2 configurations, other than the shipped one, that the suite builds a model for (tests/test_fs2_configs_cpu.py,
 tests/test_fs2_configs_gpu.py, tools/make_goldens.py: g14_fs2_configs), and the configurations the constructor refuses.
 
-Every entry of CONFIGS is a delta over the shipped `model_config` / `preprocess_config` chosen to select a dispatch branch of
-tts_king_amd/fastspeech2.py that the shipped configuration (hidden 256, 2 heads, conv_filter_size 1024, conv_kernel_size [9, 1],
-predictor filter 256 / kernel 3, 80 mels, max_seq_len 1000) never takes.  `selects` says which; tests/test_fs2_configs_gpu.py
-checks that the launches say the same.  Shapes are the smallest that still reach each branch."""
+Every entry of CONFIGS is a delta over the shipped `model_config` / `preprocess_config` chosen to select routes of the kernel plan
+(tts_king_amd/fs2_plan.py: build_plan) that the shipped configuration (hidden 256, 2 heads, conv_filter_size 1024, conv_kernel_size
+[9, 1], predictor filter 256 / kernel 3, 80 mels, max_seq_len 1000) never takes.  `selects` says which; tests/test_fs2_plan_cpu.py
+checks that the plan names them, tests/test_fs2_configs_gpu.py that the launches say the same.  Shapes are the smallest that still reach each branch."""
 import copy
 import json
 import os

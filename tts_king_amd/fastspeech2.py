@@ -12,16 +12,23 @@ flat buffer with a bf16 shadow.  `torch.autograd` only sees one node (`_Bridge`)
 """
 import json
 import os
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
 
+from . import fs2_plan
 from . import ops
 from . import params as P
 from . import switches
 from .ops import bf16
 
 N_VOCAB = 207  # len(symbols) + 1 — reference: fs_two/transformer/Models.py:40, fs_two/text/symbols.py
+
+
+class _Saved(namedtuple("_Saved", "pre x qkv probs o z1 mean1 rstd1 x1 h z2 mean2 rstd2 Bn S lens H p site o32")):
+    """What a block's forward keeps for its backward: twenty fields, and beside them the attribute `plan`, the block's
+    fs2_plan.Block, so that the backward reads which kernels the forward ran instead of guessing it from the tensors."""
 
 
 def sinusoid_table(n_position, d_hid):
@@ -144,14 +151,14 @@ class FastSpeech2(nn.Module):
         self._ctx = None
         self._deferred = None           # the step's ops.DeferQueue: weight-gradient problems and split-K slabs awaiting their launches (backward only)
         self._deferred_fin = None       # gradient column-sum partials awaiting the batched finalize
-        # The FFT blocks' w_1 forward, q|k|v projection, fc and w_2 input gradients, and the PostNet's 512 -> 512 convs (forward and
-        # input gradient) run on the window kernel (csrc/ffn_conv.hip).  It wants the weights in MFMA-fragment order (1 KiB contiguous
-        # per fragment; from the tap-major shadow it is no faster than the implicit GEMM): `_w1_packed` holds such copies — for an input
-        # gradient the transposed, tap-flipped weight — all rewritten by ONE launch whenever the bf16 shadow is (sync_shadow, the
-        # optimizer step).
-        self.window_ffn = switches.get("TTSK_WINDOW_FFN") != "0"
-        self._w1_packed = None
-        self._adam_items = None         # the packed weights the optimizer's Adam launch can write itself (_build_packs)
+        # The five kernel toggles (properties, below the class; DESIGN.md 7.2 says what each decides): which kernel runs which site
+        # follows from them and the dimensions in ONE place, fs2_plan.build_plan; `self.plan` is that record.  The window kernel
+        # (csrc/ffn_conv.hip) wants its weights in MFMA-fragment order: `_w1_packed` holds such copies of the weights the plan routes
+        # there — for an input gradient the transposed, tap-flipped weight — all rewritten by ONE launch whenever the bf16 shadow is.
+        self._toggles = {"window_ffn": switches.get("TTSK_WINDOW_FFN") != "0", "flash_attention": True, "fused_ln": True,
+                         "postnet_ends_win": True, "dwconv": switches.get("TTSK_DWCONV") != "0"}
+        self._dims = fs2_plan.dims_of(model_config, self.n_mel)
+        self._plan_cache = None         # (the packs, their tables and the optimizer's Adam items: _build_packs, at the end of this)
         # Speaker adaptation (set_trainable): the units that are trained, None = all of them
         self._trainable = None
         self._optimizer_built = False
@@ -160,10 +167,6 @@ class FastSpeech2(nn.Module):
         self._optim_tables = None
         self._repack_after_step = False
         self._odd_after_step = None
-        self.flash_attention = True     # attention without the S x S tensors when d_k = 128 (csrc/flash_attn.hip); False / other head sizes: scores GEMM + softmax + P V GEMM
-        self.fused_ln = True            # fc / w_2 + dropout + residual + LayerNorm + PAD zeroing in one kernel when d = 256
-        self._postnet_ends_win = True       # the PostNet's 80 -> 512 / 512 -> 80 convs and their input gradients on the window kernel too (round 5; property below)
-        self.dwconv = switches.get("TTSK_DWCONV") != "0"   # w_1's weight gradient on the tap-sharing kernel (csrc/dwconv.hip), the other 256-multiple ones on dwgemm.hip
         self.group_predictors = not self.use_cwt    # training with targets: the three VariancePredictors run as grouped launches (the CWT
                                                     # branch picks its pitch embedding from the prediction: sequential by construction)
         # The weight-gradient GEMMs of PostNet + decoder (88 % of the step's dW FLOPs) are complete once the decoder's backward is;
@@ -221,10 +224,7 @@ class FastSpeech2(nn.Module):
             assert self._table[va + "pitch_std.flat_one.net.0.weight"].offset - hm[0] == ops.CNNSCALAR_FLOATS
         else:
             assert o[2] - o[1] == self._pred_stride and self._pred_stride % 8 == 0
-        if self.window_ffn and self._shadow.is_cuda:
-            self._build_packs()
-        else:
-            self._build_optim_tables()
+        self._build_packs()
 
     # ------------------------------------------------------------------ parameter plumbing
     def _register(self, en, device):
@@ -312,8 +312,8 @@ class FastSpeech2(nn.Module):
                 par.grad = self._view(self._flat_grad, en) if on else None
 
     def _build_optim_tables(self, adam_writes_packs=True):
-        """The optimizer step's device tables (host -> device copies: at construction, set_trainable, `_apply` and a change of
-        `postnet_ends_win`, never inside a step): the trainable ranges of the flat buffer — everything trained: one range — and the
+        """The optimizer step's device tables (host -> device copies: at construction, set_trainable, `_apply` and a toggle that
+        changes `plan.packs`, never inside a step): the trainable ranges of the flat buffer — everything trained: one range — and the
         trainable packed weights as the Adam launch's items (their packs are written there, the frozen weights' packs are left alone).
         The trainable 80-channel ends, which that launch cannot write, get a pack table of their own.  When the items cannot be used —
         a packed weight that does not tile, one with two packs of a kind, or `adam_writes_packs` False (tests: the same step with
@@ -322,7 +322,7 @@ class FastSpeech2(nn.Module):
         if not self._flat.is_cuda:
             return
         dev, ranges, tables = self._flat.device, self.trainable_ranges(), None
-        packed = self.window_ffn and bool(self._w1_packed)
+        packed = bool(self.plan.packs)
         if packed and adam_writes_packs and self._adam_items is not None:
             tables = ops.optim_tables(ranges, [tuple(v) for k, v in self._adam_items.items() if self._unit_on(P.unit_of(k))], dev)
         if tables is None:
@@ -337,9 +337,8 @@ class FastSpeech2(nn.Module):
 
     def refresh_after_step(self):
         """Behind the optimizer step, which rewrote the bf16 shadow: the window kernels' packs that step did not write itself — every
-        pack when its Adam launch had no items, else the trainable 80-channel ends in one small launch."""
-        if not self.window_ffn:
-            return
+        pack when its Adam launch had no items, else the trainable 80-channel ends in one small launch (_build_optim_tables: neither
+        when the plan has no packs)."""
         if self._repack_after_step:
             self.refresh_packed()
         elif self._odd_after_step is not None:
@@ -362,16 +361,10 @@ class FastSpeech2(nn.Module):
         super()._apply(fn, recurse)
         self._flat, self._flat_grad = flat, grad
         self._shadow = shadow.to(bf16) if shadow.dtype != bf16 else shadow
-        self._w1_packed = None
-        self._adam_items = None
-        self._shadow_version = -1
         self._rng_state = None
         self._dw_side = self._fin_side = self._pred_stream = None
         self._rebind()
-        if self.window_ffn and self._shadow.is_cuda:
-            self._build_packs()
-        else:
-            self._build_optim_tables()
+        self._build_packs()
         return self
 
     def get(self, key):
@@ -454,28 +447,30 @@ class FastSpeech2(nn.Module):
             self.refresh_packed()
 
     @property
-    def postnet_ends_win(self):
-        return self._postnet_ends_win
+    def plan(self):
+        """fs2_plan.build_plan for this model as it is toggled now: rebuilt after a toggle changed, the same object otherwise.  Needs no device."""
+        if self._plan_cache is None:
+            self._plan_cache = fs2_plan.build_plan(self._dims, fs2_plan.Toggles(**self._toggles))
+        return self._plan_cache
 
-    @postnet_ends_win.setter
-    def postnet_ends_win(self, on):
-        """The attribute decides which packs exist, so a change after construction rebuilds them (it was only read in `_build_packs`)."""
-        on = bool(on)
-        if on != self._postnet_ends_win:
-            self._postnet_ends_win = on
-            self._w1_packed = None
-            self._adam_items = None
-            if self.window_ffn and self._shadow.is_cuda:
+    def _set_toggle(self, name, on):
+        """A toggle drops the cached plan; one that changes `plan.packs` rebuilds the packs and the optimizer's tables at once (host ->
+        device copies: a toggle is set between steps, never inside one)."""
+        if bool(on) != self._toggles[name]:
+            self._toggles[name] = bool(on)
+            self._plan_cache = None
+            if self._shadow.is_cuda and self.plan.packs != self._planned_packs:
                 self._build_packs()
+
+    def routes(self):
+        """The plan's route names per site as plain lists (fs2_plan.routes): {"encoder" / "decoder": {site: [per block]}, "postnet":
+        {site: [per layer]}, "mel_linear": {"train", "eval", "dx"}}."""
+        return fs2_plan.routes(self.plan)
 
     def refresh_packed(self):
         """Rewrite the fragment-major weight copies the window conv kernel reads (csrc/ffn_conv.hip) from the bf16 shadow — one launch
         over a device-resident item table.  Called by everything that writes the shadow: `sync_shadow` and
         `ScheduledOptim.step_and_update_lr`."""
-        if not self.window_ffn:
-            return
-        if self._w1_packed is None:
-            self._build_packs()
         if self._pack_table is not None:
             ops.win_conv_pack_run(*self._pack_table)
         if self._odd_pack_table is not None:       # the PostNet's 80-channel ends: one small launch
@@ -483,66 +478,29 @@ class FastSpeech2(nn.Module):
 
     def _build_packs(self):
         """Allocate the packs and their item table (host -> device copy: not capturable, so this runs at construction and after
-        `_apply`, never inside a forward).  Packs: the FFT blocks' w_1 and q|k|v as they are (forward), fc / w_2 / w_1 / q|k|v transposed
-        with flipped taps (input gradients), the PostNet's three 512 -> 512 convs both ways."""
-        d, dec = self.d, ["decoder.layer_stack.%d." % i for i in range(self.n_dec)]
-        enc = ["encoder.layer_stack.%d." % i for i in range(self.n_enc)]
-        # (tag, key, rows of a fused view or None, transpose)
-        want = [("w1", p + "pos_ffn.w_1.weight", None, False) for p in dec + enc] + \
-               [("qkv", p + "slf_attn.w_qs.weight", 3 * d, False) for p in dec + enc] + \
-               [("fcT", p + "slf_attn.fc.weight", None, True) for p in dec + enc] + \
-               [("w2T", p + "pos_ffn.w_2.weight", None, True) for p in dec + enc] + \
-               [("w1T", p + "pos_ffn.w_1.weight", None, True) for p in dec + enc] + \
-               [("fc", p + "slf_attn.fc.weight", None, False) for p in dec + enc] + \
-               [("w2", p + "pos_ffn.w_2.weight", None, False) for p in dec + enc] + \
-               [("qkvT", p + "slf_attn.w_qs.weight", 3 * d, True) for p in dec + enc] + \
-               [("pn", "postnet.convolutions.%d.0.conv.weight" % i, None, False) for i in range(1, 4)] + \
-               [("pnT", "postnet.convolutions.%d.0.conv.weight" % i, None, True) for i in range(1, 4)]
-        # the PostNet's ends (80 -> 512 and 512 -> 80 channels, round 5): packs Adam's tile walk cannot write (80 is neither a multiple of
-        # 32 storage rows nor of 256 storage columns); one small launch of their own behind the optimizer step (refresh_after_step)
-        odd = [(t, "postnet.convolutions.%d.0.conv.weight" % i, None, tr) for t, i, tr in
-               (("pn", 0, False), ("pnT", 0, True), ("pn", 4, False), ("pnT", 4, True))] if self.postnet_ends_win else []
-        if self.postnet_ends_win:            # ... and mel_linear (256 -> 80) both ways
-            odd += [("lin", "mel_linear.weight", None, False), ("linT", "mel_linear.weight", None, True)]
-        items = []
-        for tag, key, fused_rows, tr in want:
-            if key not in self._table:
-                continue
-            W = self._pack_source(key, fused_rows)
-            cs, kk, ds = W.shape
-            cin, cout = (cs, ds) if tr else (ds, cs)
-            split = tag in ("w1T", "qkvT")                 # wide contraction: 256-channel slices into fp32 slabs (ops.win_conv_split)
-            if tag in ("fc", "w2"):                        # the fused projection + LayerNorm kernel's weights (ops.win_ln_fwd)
-                if kk != 1 or not ops.win_ln_supported(cin, cout):
-                    continue
-            elif not ops.win_conv_supported(256 if split else cin, cout, kk) or (split and cin % 256):
-                continue
-            items.append((tag, key, fused_rows, tr, W.numel()))
-        buf = torch.empty(sum(it[4] for it in items), dtype=bf16, device=self._shadow.device)
-        self._w1_packed, self._pack_items, off = {}, [], 0
-        for tag, key, fused_rows, tr, n in items:
-            self._w1_packed[(tag, key)] = buf[off:off + n]
-            self._pack_items.append((key, fused_rows, buf[off:off + n], tr))
+        `_apply` and from a toggle's setter, never inside a forward): exactly `plan.packs`, none on the CPU.  The odd ones -- the PostNet's
+        ends and mel_linear, 80 channels: neither a multiple of 32 storage rows nor of 256 storage columns -- Adam's tile walk cannot
+        write; they get one small launch of their own behind the optimizer step (refresh_after_step).  The packs are empty until the
+        next `sync_shadow`, which this asks for."""
+        dev = self._shadow.device
+        self._planned_packs = self.plan.packs if self._shadow.is_cuda else ()
+        main = [p for p in self._planned_packs if not p.odd]
+        buf = torch.empty(sum(self.pack_numel(p) for p in main), dtype=bf16, device=dev)
+        self._w1_packed, self._pack_items, self._odd_items, off = {} if self._planned_packs else None, [], [], 0
+        for p in main:
+            n = self.pack_numel(p)
+            self._w1_packed[(p.tag, p.key)] = buf[off:off + n]
+            self._pack_items.append((p.key, p.fused_rows, buf[off:off + n], p.transpose))
             off += n
+        for p in self._planned_packs:
+            if p.odd:
+                pk = torch.empty(self.pack_numel(p), dtype=bf16, device=dev)
+                self._w1_packed[(p.tag, p.key)] = pk
+                self._odd_items.append((p.key, self._pack_source(p.key), pk, p.transpose))
         # the shadow views and the packs keep their addresses until _apply: a device-resident item table, one pack launch per step
         self._pack_table = ops.win_conv_pack_table([(self._pack_source(key, fr), out, tr) for key, fr, out, tr in self._pack_items],
-                                                   self._shadow.device) if self._pack_items else None
-        self._odd_pack_table = None
-        odd_items, self._odd_items = [], []
-        for tag, key, _, tr in odd:
-            if key not in self._table:
-                continue
-            W = self._pack_source(key)
-            cs, kk, ds = W.shape
-            cin, cout = (cs, ds) if tr else (ds, cs)
-            if not ops.win_conv_supported(cin, cout, kk):
-                continue
-            pk = torch.empty(ops.win_pack_numel(cs, kk, ds, tr), dtype=bf16, device=self._shadow.device)
-            self._w1_packed[(tag, key)] = pk
-            odd_items.append((W, pk, tr))
-            self._odd_items.append((key, W, pk, tr))
-        if odd_items:
-            self._odd_pack_table = ops.win_conv_pack_table(odd_items, self._shadow.device)
+                                                   dev) if self._pack_items else None
+        self._odd_pack_table = ops.win_conv_pack_table([(W, pk, tr) for _, W, pk, tr in self._odd_items], dev) if self._odd_items else None
         # ... and the items with which the optimizer's Adam launch writes these packs itself (ttsk_optim_step): per weight its flat
         # offset, storage shape and its plain / transposed packs.  A weight with more than one pack of a kind (w_1's transposed pack
         # exists once) leaves `_adam_items` None: every pack is then rewritten behind the step (_build_optim_tables).
@@ -557,11 +515,20 @@ class FastSpeech2(nn.Module):
                 ent[3 if tr else 2] = out
             if ok:
                 self._adam_items = by_key
+        self._shadow_version = -1
         self._build_optim_tables()
 
+    def pack_numel(self, p):
+        """Elements of pack `p` (an fs2_plan.Pack), from the parameter table alone."""
+        en = self._table[p.key]
+        cs, k, ds = en.storage_shape if en.conv else (p.fused_rows or en.shape[0], 1, en.shape[1])
+        return ops.win_pack_numel(cs, k, ds, p.transpose) if p.odd else cs * k * ds
+
     def _pack(self, tag, key):
-        """The window kernel's pack `(tag, key)` of `_build_packs`, or None: no such pack, or no packs at all (TTSK_WINDOW_FFN=0)."""
-        return self._w1_packed.get((tag, key)) if (self.window_ffn and self._w1_packed) else None
+        """The window kernel's pack `(tag, key)`: a route of the plan that reads a pack finds it here, or the packs are not the plan's."""
+        if self._w1_packed is None or (tag, key) not in self._w1_packed:
+            raise ops.L.TtskError("the plan routes %s to the window kernel, but its pack %r is missing" % (key, tag))
+        return self._w1_packed[(tag, key)]
 
     def _pack_source(self, key, fused_rows=None):
         """The tap-major bf16 shadow of `key` as a (Cs, k, Ds) tensor (a Linear weight is k = 1; `fused_rows`: the q|k|v rows as one)."""
@@ -617,24 +584,34 @@ class FastSpeech2(nn.Module):
                 mel, post, pitch, energy, logd = _Bridge.apply(self._anchor, self, mel, post, pitch, energy, logd)
         return (mel, pitch, energy, logd, d_rounded, src_masks, mel_masks, src_lens, mel_lens_out, post, pm, ps)
 
-    def _fft_fwd(self, pre, x, Bn, S, lens, H, p, site, rng, ctx_list, out=None, qkv=None, next_pre=None):
-        """One FFTBlock.  reference: Layers.py:25-34, SubLayers.py:31-65 (MHA), :93-101 (FFN), Modules.py:14-24.
-        `next_pre`: the block that follows in the same stack — its q|k|v projection of this block's output comes out of this
-        block's last kernel (then the return value is (x2, qkv_next), and the caller hands qkv_next to that block as `qkv`)."""
+    def _stack_fwd(self, name, x, Bn, S, lens, p=0.0, site0=None, rng=None, ctx_list=None, out=None):
+        """The FFT blocks of stack `name` ("encoder" / "decoder"), each on the kernels of its plan record.  Dropout sites of block i:
+        site0 + 2 i and + 1 (None, the inference halves: site 0 everywhere).  `out`: where the last block writes its output."""
+        blocks = getattr(self.plan, name)
+        H = self.n_head_enc if name == "encoder" else self.n_head_dec
+        qkv = None
+        for i, B in enumerate(blocks):
+            nxt = "%s.layer_stack.%d." % (name, i + 1) if i + 1 < len(blocks) else None
+            x, qkv = self._fft_fwd(B, "%s.layer_stack.%d." % (name, i), x, Bn, S, lens, H, p, 0 if site0 is None else site0 + 2 * i, rng,
+                                   ctx_list, out=out if nxt is None else None, qkv=qkv, next_pre=nxt)
+        return x
+
+    def _fft_fwd(self, B, pre, x, Bn, S, lens, H, p, site, rng, ctx_list, out=None, qkv=None, next_pre=None):
+        """One FFTBlock on the kernels of `B`, its fs2_plan.Block.  reference: Layers.py:25-34, SubLayers.py:31-65 (MHA), :93-101 (FFN),
+        Modules.py:14-24.  Returns (x2, qkv_next); qkv_next (w2_ln "win_ln_proj"): the q|k|v projection of this block's output for
+        `next_pre`, the block that follows in the stack, out of this block's last kernel -- the caller hands it to that block as `qkv`."""
         d, rows = self.d, Bn * S
         dk = d // H
         a, f = pre + "slf_attn.", pre + "pos_ffn."
         Sp = (S + 7) // 8 * 8
         dev = x.device
         # (1) q|k|v projections as one GEMM into a [rows][3d] buffer: SubLayers.py:41-43
-        pkq = self._pack("qkv", a + "w_qs.weight")
-        if qkv is not None:
-            pass                         # came out of the previous block's last kernel
-        elif pkq is not None and x.dtype == bf16:
-            qkv = ops.win_conv(x.view(Bn, S, d), pkq, 3 * d, 1, bias=self._m(a + "w_qs.bias", 3 * d)).view(rows, 3 * d)   # window kernel, k = 1
-        else:
+        if B.qkv == "win":
+            qkv = ops.win_conv(x.view(Bn, S, d), self._pack("qkv", a + "w_qs.weight"), 3 * d, 1, bias=self._m(a + "w_qs.bias", 3 * d)).view(rows, 3 * d)   # window kernel, k = 1
+        elif B.qkv == "gemm":
             qkv = ops.linear(x, self._w(a + "w_qs.weight", 3 * d), self._m(a + "w_qs.bias", 3 * d))
-        if self.flash_attention and dk == 128:
+        # ("chained": `qkv` came out of the previous block's last kernel)
+        if B.attn == "flash":
             # (2)-(4) one kernel, no S x S tensor: scores, key-padding mask, online softmax, P V, heads merged (Modules.py:15-22,
             # SubLayers.py:57-60); the backward recomputes P from the per-row log-sum-exp kept in `probs`'s slot
             o, probs, o32 = ops.flash_attention_fwd(qkv, lens, Bn, H, S, want_lse=ctx_list is not None)
@@ -650,59 +627,42 @@ class FastSpeech2(nn.Module):
             o = torch.empty(rows, d, dtype=bf16, device=dev)
             ops.gemm(probs, qkv[:, 2 * d:], o, S, dk, S, Sp, 3 * d, d, flags=ops.B_TR, nz1=Bn, nz2=H,
                      sA=(H * S * Sp, S * Sp), sB=(S * 3 * d, dk), sC=(S * d, dk))
-        fuse = self.fused_ln and d == 256
         qkv_next = None
         # (5) fc, dropout, +residual, LayerNorm, zero PAD rows: SubLayers.py:62-63, Layers.py:29 — one kernel when d = 256
-        if fuse:
-            pkl = self._pack("fc", a + "fc.weight")
-            if pkl is not None:
-                x1, z1, mean1, rstd1 = ops.win_ln_fwd(o, pkl, self._m(a + "fc.bias"), x, self._m(a + "layer_norm.weight"),
-                                                      self._m(a + "layer_norm.bias"), lens, S, p_pre=p, site_pre=site, rng=rng,
-                                                      save_z=ctx_list is not None)
-            else:
-                x1, z1, mean1, rstd1 = ops.gemm_ln_fwd(o, self._w(a + "fc.weight"), self._m(a + "fc.bias"), x, self._m(a + "layer_norm.weight"),
-                                                       self._m(a + "layer_norm.bias"), lens, S, p_pre=p, site_pre=site, rng=rng,
-                                                       save_z=ctx_list is not None)
+        ln = (x, self._m(a + "layer_norm.weight"), self._m(a + "layer_norm.bias"), lens, S)
+        kw = dict(p_pre=p, site_pre=site, rng=rng, save_z=ctx_list is not None)
+        if B.fc_ln == "win_ln":
+            x1, z1, mean1, rstd1 = ops.win_ln_fwd(o, self._pack("fc", a + "fc.weight"), self._m(a + "fc.bias"), *ln, **kw)
+        elif B.fc_ln == "gemm_ln":
+            x1, z1, mean1, rstd1 = ops.gemm_ln_fwd(o, self._w(a + "fc.weight"), self._m(a + "fc.bias"), *ln, **kw)
         else:
             y = ops.linear(o, self._w(a + "fc.weight"), self._m(a + "fc.bias"))
-            x1, z1, mean1, rstd1, _ = ops.layernorm_fwd(y, x, self._m(a + "layer_norm.weight"), self._m(a + "layer_norm.bias"),
-                                                        lens, S, p_pre=p, site_pre=site, rng=rng, save_z=ctx_list is not None)
+            x1, z1, mean1, rstd1, _ = ops.layernorm_fwd(y, *ln, **kw)
         # (6) FFN: Conv1d(k=9)+ReLU, Conv1d(k=1), dropout, +residual, LayerNorm, zero PAD rows: SubLayers.py:96-99, Layers.py:32
         W1 = self._w(f + "w_1.weight")
-        pk = self._pack("w1", f + "w_1.weight")
-        if pk is not None and x1.dtype == bf16 and d == 256:
-            h = ops.ffn_conv_fwd(x1.view(Bn, S, d), W1, self._m(f + "w_1.bias"), relu=True, packed=pk)      # window kernel (csrc/ffn_conv.hip)
-        elif pk is not None and x1.dtype == bf16:
+        if B.w1 == "ffn":
+            h = ops.ffn_conv_fwd(x1.view(Bn, S, d), W1, self._m(f + "w_1.bias"), relu=True, packed=self._pack("w1", f + "w_1.weight"))      # window kernel (csrc/ffn_conv.hip)
+        elif B.w1 == "win":
             # d = 512: ttsk_ffn_conv_fwd is the 256-channel entry point; the same pack runs on the window kernel's 512-channel instance
-            h = ops.win_conv(x1.view(Bn, S, d), pk, W1.shape[0], self.k1, bias=self._m(f + "w_1.bias"), relu=True)
+            h = ops.win_conv(x1.view(Bn, S, d), self._pack("w1", f + "w_1.weight"), W1.shape[0], self.k1, bias=self._m(f + "w_1.bias"), relu=True)
         else:
             h = ops.conv1d(x1.view(Bn, S, d), W1, self._m(f + "w_1.bias"), flags=ops.RELU)
-        if fuse and self.k2 == 1:
-            pkl = self._pack("w2", f + "w_2.weight")
-            pkn = self._pack("qkv", next_pre + "slf_attn.w_qs.weight") if (next_pre and pkl is not None) else None
-            if pkn is not None:
-                x2, z2, mean2, rstd2, qkv_next = ops.win_ln_fwd(h.view(rows, -1), pkl, self._m(f + "w_2.bias"), x1, self._m(f + "layer_norm.weight"),
-                                                                self._m(f + "layer_norm.bias"), lens, S, p_pre=p, site_pre=site + 1, rng=rng,
-                                                                save_z=ctx_list is not None, out=out,
-                                                                proj=(pkn, self._m(next_pre + "slf_attn.w_qs.bias", 3 * d)))
-            elif pkl is not None:
-                x2, z2, mean2, rstd2 = ops.win_ln_fwd(h.view(rows, -1), pkl, self._m(f + "w_2.bias"), x1, self._m(f + "layer_norm.weight"),
-                                                      self._m(f + "layer_norm.bias"), lens, S, p_pre=p, site_pre=site + 1, rng=rng,
-                                                      save_z=ctx_list is not None, out=out)
-            else:
-                x2, z2, mean2, rstd2 = ops.gemm_ln_fwd(h.view(rows, -1), self._w(f + "w_2.weight"), self._m(f + "w_2.bias"), x1,
-                                                       self._m(f + "layer_norm.weight"), self._m(f + "layer_norm.bias"), lens, S, p_pre=p,
-                                                       site_pre=site + 1, rng=rng, save_z=ctx_list is not None, out=out)
+        ln = (x1, self._m(f + "layer_norm.weight"), self._m(f + "layer_norm.bias"), lens, S)
+        kw.update(site_pre=site + 1, out=out)
+        if B.w2_ln == "win_ln_proj":
+            proj = (self._pack("qkv", next_pre + "slf_attn.w_qs.weight"), self._m(next_pre + "slf_attn.w_qs.bias", 3 * d))
+            x2, z2, mean2, rstd2, qkv_next = ops.win_ln_fwd(h.view(rows, -1), self._pack("w2", f + "w_2.weight"), self._m(f + "w_2.bias"), *ln, proj=proj, **kw)
+        elif B.w2_ln == "win_ln":
+            x2, z2, mean2, rstd2 = ops.win_ln_fwd(h.view(rows, -1), self._pack("w2", f + "w_2.weight"), self._m(f + "w_2.bias"), *ln, **kw)
+        elif B.w2_ln == "gemm_ln":
+            x2, z2, mean2, rstd2 = ops.gemm_ln_fwd(h.view(rows, -1), self._w(f + "w_2.weight"), self._m(f + "w_2.bias"), *ln, **kw)
         else:
             y2 = ops.conv1d(h, self._w(f + "w_2.weight"), self._m(f + "w_2.bias"))
-            x2, z2, mean2, rstd2, _ = ops.layernorm_fwd(y2.view(rows, d), x1, self._m(f + "layer_norm.weight"),
-                                                        self._m(f + "layer_norm.bias"), lens, S, p_pre=p, site_pre=site + 1,
-                                                        rng=rng, save_z=ctx_list is not None, out=out)
+            x2, z2, mean2, rstd2, _ = ops.layernorm_fwd(y2.view(rows, d), *ln, **kw)
         if ctx_list is not None:
-            ctx_list.append((pre, x, qkv, probs, o, z1, mean1, rstd1, x1, h, z2, mean2, rstd2, Bn, S, lens, H, p, site, o32))
-        if next_pre:
-            return x2, qkv_next
-        return x2
+            ctx_list.append(_Saved(pre, x, qkv, probs, o, z1, mean1, rstd1, x1, h, z2, mean2, rstd2, Bn, S, lens, H, p, site, o32))
+            ctx_list[-1].plan = B
+        return x2, qkv_next
 
     def _predictor_fwd(self, pre, x, Bn, Lp, lens, p, site, rng, ctx, hidden_lens=None):
         """VariancePredictor.  reference: model/modules.py:255-309.  `hidden_lens` (batched synthesis): the hidden rows between the two
@@ -839,12 +799,7 @@ class FastSpeech2(nn.Module):
             pe_enc = self.get("encoder.position_enc")[0]
         x = ops.gather_add(None, self._m("encoder.src_word_emb.weight"), texts, pe=pe_enc, pe_mod=Lp, rows=Bn * Lp)
         stack = torch.empty(3, Bn * Lp, d, dtype=bf16, device=dev) if grouped else None
-        qkv = None
-        for i in range(self.n_enc):
-            nxt = "encoder.layer_stack.%d." % (i + 1) if i + 1 < self.n_enc else None
-            x = self._fft_fwd("encoder.layer_stack.%d." % i, x, Bn, Lp, src_lens, self.n_head_enc, p_enc, 2 * i, rng, blocks,
-                              out=stack[0] if (grouped and i == self.n_enc - 1) else None, qkv=qkv, next_pre=nxt)
-            x, qkv = x if nxt else (x, None)
+        x = self._stack_fwd("encoder", x, Bn, Lp, src_lens, p_enc, 0, rng, blocks, out=stack[0] if grouped else None)
         # ---- variance adaptor: modules.py:142-217 (duration BEFORE the speaker embedding; energy sees the pitch embedding)
         va = "variance_adaptor."
         if grouped:
@@ -910,16 +865,12 @@ class FastSpeech2(nn.Module):
         # ---- decoder: Models.py:157-189
         y = dec_in.view(Bn * T, d)
         n_enc_blocks = len(blocks) if train else 0
-        qkv = None
-        for i in range(self.n_dec):
-            nxt = "decoder.layer_stack.%d." % (i + 1) if i + 1 < self.n_dec else None
-            y = self._fft_fwd("decoder.layer_stack.%d." % i, y, Bn, T, mlens, self.n_head_dec, p_dec, 100 + 2 * i, rng, blocks, qkv=qkv, next_pre=nxt)
-            y, qkv = y if nxt else (y, None)
+        y = self._stack_fwd("decoder", y, Bn, T, mlens, p_dec, 100, rng, blocks)
         # ---- mel_linear (fp32 output + bf16 copy for the PostNet): fastspeech2.py:102
         rows = Bn * T
-        pkm = self._pack("lin", "mel_linear.weight")
-        if pkm is not None and y.dtype == bf16:
-            mel, mel16 = ops.win_conv_dual(y.view(Bn, T, d), pkm, self.n_mel, 1, bias=self._m("mel_linear.bias"))      # window kernel, k = 1
+        plan = self.plan
+        if plan.mel_fwd == "win_dual":
+            mel, mel16 = ops.win_conv_dual(y.view(Bn, T, d), self._pack("lin", "mel_linear.weight"), self.n_mel, 1, bias=self._m("mel_linear.bias"))      # window kernel, k = 1
             mel, mel16 = mel.view(rows, self.n_mel), mel16.view(rows, self.n_mel)
         else:
             mel16 = torch.empty(rows, self.n_mel, dtype=bf16, device=dev)
@@ -928,48 +879,13 @@ class FastSpeech2(nn.Module):
         if fl is not None:
             ops.zero_frames_from(mel16, fl)          # the PostNet's first conv sees zero padding past the batch's own length
         # ---- PostNet: Layers.py:133-143, + mel: fastspeech2.py:104
-        pn = []
-        xin = mel16.view(Bn, T, self.n_mel)
-        for i in range(5):
-            pp = "postnet.convolutions.%d." % i
-            # conv output stays fp32: BatchNorm divides by the batch std, which amplifies a bf16 rounding of it
-            pk = self._pack("pn", pp + "0.conv.weight")
-            stats = None
-            if pk is not None and xin.dtype == bf16:
-                cw = self._table[pp + "0.conv.weight"].storage_shape
-                if train and xin.shape[2] in (512, 80) and ops.bn_slab_supported(cw[0]):
-                    # window kernel; the BatchNorm statistics partials of its output come out of its epilogue
-                    yc, stats = ops.win_conv_stats(xin, pk, cw[0], cw[1], bias=self._m(pp + "0.conv.bias"), frame_limit=fl)
-                else:
-                    yc = ops.win_conv(xin, pk, cw[0], cw[1], bias=self._m(pp + "0.conv.bias"), out_dtype=torch.float32)   # window kernel
-            else:
-                yc = ops.conv1d(xin, self._w(pp + "0.conv.weight"), self._m(pp + "0.conv.bias"), out_dtype=torch.float32)
-            C = yc.shape[2]
-            last = i == 4
-            if train and ops.bn_slab_supported(C):
-                # statistics partials, then one kernel that finishes mean / rstd per channel slab and normalises
-                nxt, mean, rstd, keep = ops.bn_train(yc.view(rows, C), self.get(pp + "1.running_mean"), self.get(pp + "1.running_var"),
-                                                     self.get(pp + "1.num_batches_tracked").view(1), self._m(pp + "1.weight"),
-                                                     self._m(pp + "1.bias"), not last, p=p_post, site=300 + i, rng=rng,
-                                                     resid=mel if last else None, out_f32=last, frame_limit=fl, want_keep=True,
-                                                     partials=stats)
-            else:
-                keep = None
-                if train:
-                    mean, rstd = ops.bn_train_stats(yc.view(rows, C), self.get(pp + "1.running_mean"), self.get(pp + "1.running_var"),
-                                                    self.get(pp + "1.num_batches_tracked").view(1), frame_limit=fl)
-                else:
-                    mean, rstd = self.get(pp + "1.running_mean"), ops.rsqrt_eps(self.get(pp + "1.running_var"))
-                nxt = ops.bn_apply(yc.view(rows, C), mean, rstd, self._m(pp + "1.weight"), self._m(pp + "1.bias"), not last,
-                                   p=p_post, site=300 + i, rng=rng, resid=mel if last else None, out_f32=last, frame_limit=fl)
-            pn.append((pp, xin, yc, mean, rstd, keep))
-            xin = nxt.view(Bn, T, C) if not last else nxt
-        post = xin
+        post, pn = self._postnet_fwd(mel, mel16, Bn, T, train, p_post, 300, rng, fl)
         if self._pred_fwd_pending and not defer_pred_join:
             torch.cuda.current_stream().wait_stream(self._pred_stream)
             self._pred_fwd_pending = False
         if train:
             ctx.blocks, ctx.preds, ctx.pn = blocks, preds, pn
+            ctx.plan = plan                 # the backward runs the routes this forward ran, whatever is toggled in between
             ctx.n_enc_blocks = n_enc_blocks
             ctx.dims = (Bn, Lp, T)
             ctx.texts, ctx.speakers, ctx.pidx, ctx.eidx, ctx.cs = texts, speakers, pidx, eidx, cs
@@ -982,6 +898,41 @@ class FastSpeech2(nn.Module):
         if self.use_cwt:
             out = out + (heads,)            # (2, B) fp32: pitch_mean row, pitch_std row
         return out, ctx
+
+    def _postnet_fwd(self, mel, mel16, Bn, T, train=False, p=0.0, site0=None, rng=None, fl=None, lens=None):
+        """PostNet + mel on the plan's routes (Layers.py:133-143, fastspeech2.py:104): the train forward (batch statistics; `fl`: the
+        frame limit of a bucketed batch), the eval forward and the inference halves (running statistics; `lens`, batched synthesis:
+        frames past an utterance's own length come out as zero rows).  Dropout site of layer i: site0 + i (None: 0).  Returns
+        (postnet mel, per layer what the backward needs)."""
+        rows, pn = Bn * T, []
+        xin = mel16.view(Bn, T, self.n_mel)
+        for i, layer in enumerate(self.plan.postnet):
+            pp = "postnet.convolutions.%d." % i
+            route, stats, last = layer.conv if train else layer.conv_eval, None, i == 4
+            C, k, _ = self._table[pp + "0.conv.weight"].storage_shape
+            # conv output stays fp32: BatchNorm divides by the batch std, which amplifies a bf16 rounding of it
+            if route == "gemm":
+                yc = ops.conv1d(xin, self._w(pp + "0.conv.weight"), self._m(pp + "0.conv.bias"), out_dtype=torch.float32)
+            elif route == "win_stats":       # window kernel; the BatchNorm statistics partials of its output come out of its epilogue
+                yc, stats = ops.win_conv_stats(xin, self._pack("pn", pp + "0.conv.weight"), C, k, bias=self._m(pp + "0.conv.bias"), frame_limit=fl)
+            else:
+                yc = ops.win_conv(xin, self._pack("pn", pp + "0.conv.weight"), C, k, bias=self._m(pp + "0.conv.bias"), out_dtype=torch.float32)
+            run = (self.get(pp + "1.running_mean"), self.get(pp + "1.running_var"), self.get(pp + "1.num_batches_tracked").view(1))
+            gb = (self._m(pp + "1.weight"), self._m(pp + "1.bias"), not last)
+            kw = dict(resid=mel if last else None, out_f32=last)
+            site, keep = 0 if site0 is None else site0 + i, None
+            if train and layer.bn == "slab":
+                # statistics partials, then one kernel that finishes mean / rstd per channel slab and normalises
+                nxt, mean, rstd, keep = ops.bn_train(yc.view(rows, C), *run, *gb, p=p, site=site, rng=rng, frame_limit=fl, want_keep=True, partials=stats, **kw)
+            else:
+                mean, rstd = ops.bn_train_stats(yc.view(rows, C), *run, frame_limit=fl) if train else (run[0], ops.rsqrt_eps(run[1]))
+                if lens is not None:
+                    nxt = ops.bn_apply_lens(yc.view(rows, C), mean, rstd, *gb, lens, T, **kw)
+                else:
+                    nxt = ops.bn_apply(yc.view(rows, C), mean, rstd, *gb, p=p, site=site, rng=rng, frame_limit=fl, **kw)
+            pn.append((pp, xin, yc, mean, rstd, keep))
+            xin = nxt.view(Bn, T, C) if not last else nxt
+        return xin, pn
 
     def _cwt_pitch_rows(self, x1, pitch_cwt, Bn, Lp, p_control):
         """get_pitch_embedding_cwt behind the predictor (modules.py:118-129): both CNNscalar heads on (x + speaker, prediction) in one
@@ -1060,11 +1011,7 @@ class FastSpeech2(nn.Module):
         src_masks = None if ragged else ops.length_mask(src_lens, Lp)       # nothing on the device reads the masks
         pe_enc = sinusoid_table(Lp, d).to(self.device) if Lp > self.max_seq_len else self.get("encoder.position_enc")[0]
         x = ops.gather_add(None, self._m("encoder.src_word_emb.weight"), texts, pe=pe_enc, pe_mod=Lp, rows=Bn * Lp)
-        qkv = None
-        for i in range(self.n_enc):
-            nxt = "encoder.layer_stack.%d." % (i + 1) if i + 1 < self.n_enc else None
-            x = self._fft_fwd("encoder.layer_stack.%d." % i, x, Bn, Lp, src_lens, self.n_head_enc, 0.0, 0, None, None, qkv=qkv, next_pre=nxt)
-            x, qkv = x if nxt else (x, None)
+        x = self._stack_fwd("encoder", x, Bn, Lp, src_lens)
         hl = src_lens if ragged else None
         logd = self._predictor_fwd(va + "duration_predictor.", x, Bn, Lp, src_lens, 0.0, 0, None, None, hidden_lens=hl)
         if ragged:
@@ -1110,35 +1057,15 @@ class FastSpeech2(nn.Module):
         pe_dec = sinusoid_table(T, d).to(dev) if T > self.max_seq_len else self.get("decoder.position_enc")[0]
         dec_in, _, _, mel_lens = ops.length_regulator_fwd(x3.view(Bn, Lp, d), dur, T, pe=pe_dec, want_idx=False)
         mel_masks = None if ragged else ops.length_mask(mel_lens, T)
-        y = dec_in.view(Bn * T, d)
-        qkv = None
-        for i in range(self.n_dec):
-            nxt = "decoder.layer_stack.%d." % (i + 1) if i + 1 < self.n_dec else None
-            y = self._fft_fwd("decoder.layer_stack.%d." % i, y, Bn, T, mel_lens, self.n_head_dec, 0.0, 0, None, None, qkv=qkv, next_pre=nxt)
-            y, qkv = y if nxt else (y, None)
+        y = self._stack_fwd("decoder", dec_in.view(Bn * T, d), Bn, T, mel_lens)
         rows = Bn * T
+        # (plan.mel_eval: "gemm" -- the forward's "win_dual" has not been taken here)
         mel16 = torch.empty(rows, self.n_mel, dtype=bf16, device=dev)
         mel = ops.linear(y, self._w("mel_linear.weight"), self._m("mel_linear.bias"), out_dtype=torch.float32, C2=mel16)
         if ragged:
             ops.zero_frames_lens(mel16, mel_lens, T)     # the path's one zero-fill pass: the GEMM's bf16 copy carries the bias in padded frames
-        xin = mel16.view(Bn, T, self.n_mel)
-        for i in range(5):
-            pp = "postnet.convolutions.%d." % i
-            pk = self._pack("pn", pp + "0.conv.weight")
-            if pk is not None and xin.dtype == bf16:
-                cw = self._table[pp + "0.conv.weight"].storage_shape
-                yc = ops.win_conv(xin, pk, cw[0], cw[1], bias=self._m(pp + "0.conv.bias"), out_dtype=torch.float32)   # window kernel
-            else:
-                yc = ops.conv1d(xin, self._w(pp + "0.conv.weight"), self._m(pp + "0.conv.bias"), out_dtype=torch.float32)
-            C = yc.shape[2]
-            last = i == 4
-            bn = (self.get(pp + "1.running_mean"), ops.rsqrt_eps(self.get(pp + "1.running_var")), self._m(pp + "1.weight"), self._m(pp + "1.bias"), not last)
-            if ragged:
-                nxt = ops.bn_apply_lens(yc.view(rows, C), *bn, mel_lens, T, resid=mel if last else None, out_f32=last)
-            else:
-                nxt = ops.bn_apply(yc.view(rows, C), *bn, resid=mel if last else None, out_f32=last)
-            xin = nxt.view(Bn, T, C) if not last else nxt
-        return mel.view(Bn, T, self.n_mel), xin.view(Bn, T, self.n_mel), mel_lens, mel_masks
+        post, _ = self._postnet_fwd(mel, mel16, Bn, T, lens=mel_lens if ragged else None)
+        return mel.view(Bn, T, self.n_mel), post.view(Bn, T, self.n_mel), mel_lens, mel_masks
 
     # ------------------------------------------------------------------ backward
     def _backward_from_autograd(self, ctx, dmel, dpost, dpitch, denergy, dlogd, dpm=None, dps=None):
@@ -1168,40 +1095,36 @@ class FastSpeech2(nn.Module):
         off = self._table[first_key].offset
         ops.colsum_finalize(partials, nblk, ncol, ncol, self._flat_grad[off:off + ncol], accumulate=self._acc, defer=self._deferred_fin)
 
-    def _raw_out_mode(self):
-        """How a block hands its input gradient to the block in front of it (see _fft_bwd): "pre" = not at all — the consumer's first
-        backward kernel (ttsk_layernorm_bwd_proj) computes it from dqkv; True = split-K slabs; the consumer must be that kernel."""
-        if self.window_ffn and self._w1_packed and self.d == 256 and self.k2 == 1 and self.d_ff == 1024:
-            return "pre"
-        return True
-
     def _fft_bwd(self, saved, dx2, rng, raw_out=False, train=True, need_dx=True):
-        """Backward of one FFTBlock.  `dx2`: gradient of the block output — a bf16 tensor, or (Slabs, residual) when the dX GEMM
-        that produced it left its split-K partial tiles un-reduced (the next block's `raw_out`): the LayerNorm backward sums them
-        while it reads its rows, so no reducer launch and no bf16 copy of that gradient exist.  Returns the gradient of the block
-        input in the same two forms.  `train` False (the block is frozen): none of its parameter-gradient work is issued (the
-        LayerNorm / bias partials the fused kernels emit are dropped).  `need_dx` False (nothing in front of the block is trained):
-        the block's input gradient is not computed, the result is None."""
-        (pre, x, qkv, probs, o, z1, mean1, rstd1, x1, h, z2, mean2, rstd2, Bn, S, lens, H, p, site, o32) = saved
+        """Backward of one FFTBlock, on the kernels of `saved.plan` (the forward's fs2_plan.Block).  `dx2`: gradient of the block
+        output as the block behind hands it over (its `qkv_dx`) — a bf16 tensor; (Slabs, residual) when the dX GEMM that produced it
+        left its split-K partial tiles un-reduced: the LayerNorm backward sums them while it reads its rows, so no reducer launch and
+        no bf16 copy of that gradient exist; or ("pre") (dqkv, packed transposed q|k|v weight, residual): this block's first kernel
+        multiplies by the weight itself.  Returns the gradient of the block input in the form its own `qkv_dx` names; `raw_out`: the
+        caller has a block of the stack in front of this one to hand it to (checked against the plan's position).  `train` False
+        (the block is frozen): none of its parameter-gradient work is issued (the LayerNorm / bias partials the fused kernels emit are
+        dropped).  `need_dx` False (nothing in front of the block is trained): the block's input gradient is not computed, the
+        result is None."""
+        pre, x, qkv, probs, o, z1, mean1, rstd1, x1, h, z2, mean2, rstd2, Bn, S, lens, H, p, site, o32 = saved
+        B = saved.plan
+        if bool(raw_out) != (B.qkv_dx in ("pre", "win_split", "gemm_raw")):
+            raise ops.L.TtskError("%s: the plan hands its input gradient over as %r, the caller asked with raw_out=%r" % (pre, B.qkv_dx, raw_out))
         d, rows = self.d, Bn * S
         dk = d // H
-        flash = probs is not None and probs.dim() == 2       # forward was the flash kernel: `probs` holds the row LSE
-        Sp = 0 if flash else probs.shape[2]
         a, f = pre + "slf_attn.", pre + "pos_ffn."
         dev = z2.device
         # ---- FFN tail: LN backward (PAD rows carry no gradient), dropout mask regenerated
-        pk2 = self._pack("w2T", f + "w_2.weight")
         pre2 = None
-        if isinstance(dx2, tuple) and len(dx2) == 3:          # (dqkv, packed transposed q|k|v weight, residual) of the block behind
+        if isinstance(dx2, tuple) and len(dx2) == 3:
+            if B.w2_bwd != "ln_proj":
+                raise ops.L.TtskError("%s: handed a \"pre\" input gradient, which only its \"ln_proj\" route consumes (plan: %r)" % (pre, B.w2_bwd))
             pre2, sl2, r2, dd2 = (dx2[0], dx2[1]), None, dx2[2], None
         else:
             sl2, r2, dd2 = (dx2[0], dx2[1], None) if isinstance(dx2, tuple) else (None, None, dx2)
-        fuse = d == 256 and self.k2 == 1
-        dh = None
-        if fuse and pk2 is not None and h.shape[-1] == 1024:
+        if B.w2_bwd == "ln_proj":
             # (the q|k|v input gradient of the block behind +) LN backward + w_2's dX (ReLU gate on the way out) in one launch
-            dz2, dy2, part, nblk, dh = ops.layernorm_bwd_proj(dd2, z2, mean2, rstd2, self._m(f + "layer_norm.weight"), pk2, h.shape[-1], lens, S,
-                                                              p_pre=p, site_pre=site + 1, rng=rng, slabs=sl2, R=r2, gate=h, pre=pre2)
+            dz2, dy2, part, nblk, dh = ops.layernorm_bwd_proj(dd2, z2, mean2, rstd2, self._m(f + "layer_norm.weight"), self._pack("w2T", f + "w_2.weight"),
+                                                              h.shape[-1], lens, S, p_pre=p, site_pre=site + 1, rng=rng, slabs=sl2, R=r2, gate=h, pre=pre2)
             dh = dh.view(Bn, S, -1)
         else:
             dz2, dy2, part, nblk = ops.layernorm_bwd(dd2, z2, mean2, rstd2, self._m(f + "layer_norm.weight"), self._m(f + "layer_norm.bias"),
@@ -1210,55 +1133,48 @@ class FastSpeech2(nn.Module):
         if train:
             self._finalize_ln(part, nblk, 3 * d, f + "w_2.bias")
             ops.queue_dw(self._deferred, dy2.view(Bn, S, d), h, self._g(f + "w_2.weight"), lens, self._acc, k=self.k2, use_dwgemm=self._use_dwconv)
-        if dh is not None:
-            pass
-        elif pk2 is not None and self.k2 == 1:
-            dh = ops.win_conv(dy2.view(Bn, S, d), pk2, h.shape[-1], 1, gate=h)         # dX as a forward conv on the transposed pack, ReLU gate on the way out
-        else:
+        if B.w2_bwd == "win":
+            dh = ops.win_conv(dy2.view(Bn, S, d), self._pack("w2T", f + "w_2.weight"), h.shape[-1], 1, gate=h)     # dX as a forward conv on the transposed pack, ReLU gate on the way out
+        elif B.w2_bwd == "gemm":
             dh = ops.conv1d_dx(dy2.view(Bn, S, d), self._w(f + "w_2.weight"), G=h)
         # ---- w_1 (k=9): bias, dW, dX + residual gradient; the dX stays in split-K form for the attention LayerNorm's backward
         if train:
             ops.colsum_into(dh.view(rows, -1), self._g(f + "w_1.bias"), defer=self._deferred_fin, accumulate=self._acc)
-            if self._use_dwconv and Bn <= 64 and dh.dtype == bf16 and ops.dwconv_supported(dh.shape[-1], d, self.k1):
+            if B.w1_dw == "dwconv" and self._use_dwconv and Bn <= 64:
                 # the taps share one fetch of dh and one window of x1 (csrc/dwconv.hip); dh is zero at PAD rows (the LayerNorm backward
                 # that produced dy2 gives them no gradient), so only the rows of each utterance's own length are walked
                 self._deferred.dwconv.append((dh, x1.view(Bn, S, d), self._g(f + "w_1.weight"), lens, self._acc))
             else:
                 ops.conv1d_dw(dh, x1.view(Bn, S, d), self._g(f + "w_1.weight"), k=self.k1, defer=self._deferred, accumulate=self._acc)
         # ---- attention tail
-        do = delta = None
-        pk1 = self._pack("w1T", f + "w_1.weight")
-        if pk1 is not None:
-            sl = ops.win_conv_split(dh, pk1, d, self.k1)       # four 256-channel slices of the 1024-channel contraction, one launch
+        if B.w1_dx == "win_split":
+            sl = ops.win_conv_split(dh, self._pack("w1T", f + "w_1.weight"), d, self.k1)       # four 256-channel slices of the 1024-channel contraction, one launch
         else:
             sl = ops.conv1d_dx(dh, self._w(f + "w_1.weight"), raw=True)
-        pkf = self._pack("fcT", a + "fc.weight")
-        if fuse and pkf is not None and lens is not None:
-            # LN backward + fc's dX (+ the attention backward's delta) in one launch
-            if flash and o32 is not None:
-                delta = torch.empty(Bn * H, S, dtype=torch.float32, device=dev)
-            dz1, dy1, part, nblk, do = ops.layernorm_bwd_proj(None, z1, mean1, rstd1, self._m(a + "layer_norm.weight"), pkf, d, lens, S,
-                                                              p_pre=p, site_pre=site, rng=rng, slabs=sl, R=dz2,
-                                                              delta_o32=o32 if delta is not None else None, delta_out=delta)
+        # the attention backward's delta = rowsum(dO o O) per head comes out of the kernel that stores dO (B.fc_delta), given the
+        # forward's fp32 O
+        delta = torch.empty(Bn * H, S, dtype=torch.float32, device=dev) if (B.fc_delta and o32 is not None) else None
+        dkw = dict(delta_o32=o32 if delta is not None else None, delta_out=delta)
+        fc_bwd = "win" if (B.fc_bwd == "ln_proj" and lens is None) else B.fc_bwd
+        if fc_bwd == "ln_proj":
+            # LN backward + fc's dX (+ delta) in one launch
+            dz1, dy1, part, nblk, do = ops.layernorm_bwd_proj(None, z1, mean1, rstd1, self._m(a + "layer_norm.weight"), self._pack("fcT", a + "fc.weight"),
+                                                              d, lens, S, p_pre=p, site_pre=site, rng=rng, slabs=sl, R=dz2, **dkw)
         else:
             dz1, dy1, part, nblk = ops.layernorm_bwd(None, z1, mean1, rstd1, self._m(a + "layer_norm.weight"), self._m(a + "layer_norm.bias"),
                                                      lens, S, p_pre=p, site_pre=site, rng=rng, slabs=sl, R=dz2)
         if train:
             self._finalize_ln(part, nblk, 3 * d, a + "fc.bias")
             ops.queue_dw(self._deferred, dy1.view(Bn, S, d), o.view(Bn, S, d), self._g(a + "fc.weight"), lens, self._acc, use_dwgemm=self._use_dwconv)
-        if do is not None:
-            pass
-        elif pkf is not None:
-            if flash and o32 is not None:
-                # the attention backward's delta = rowsum(dO o O) per head, written by this conv's epilogue while it stores dO
-                delta = torch.empty(Bn * H, S, dtype=torch.float32, device=dev)
-            do = ops.win_conv(dy1.view(Bn, S, d), pkf, d, 1, delta_o32=o32 if delta is not None else None, delta_out=delta).view(rows, d)
-        else:
+        if fc_bwd == "win":
+            do = ops.win_conv(dy1.view(Bn, S, d), self._pack("fcT", a + "fc.weight"), d, 1, **dkw).view(rows, d)
+        elif fc_bwd == "gemm":
             do = ops.linear_dx(dy1, self._w(a + "fc.weight"))
         # ---- attention core: dP = dO V^T ; dS = softmax'(P, dP)/sqrt(dk) ; dQ = dS K ; dK = dS^T Q ; dV = P^T dO
-        if flash:
+        if B.attn == "flash":
             dqkv = ops.flash_attention_bwd(qkv, o, do, probs, lens, Bn, H, S, o32=o32, delta=delta)      # P recomputed per tile; dQ, dK, dV in two launches
         else:
+            Sp = probs.shape[2]
             dqkv = torch.empty(rows, 3 * d, dtype=bf16, device=dev)
             dP = torch.empty(Bn * H, S, Sp, dtype=torch.float32, device=dev)
             ops.gemm(do, qkv[:, 2 * d:], dP, S, S, dk, d, 3 * d, Sp, nz1=Bn, nz2=H, sA=(S * d, dk), sB=(S * 3 * d, dk),
@@ -1279,15 +1195,14 @@ class FastSpeech2(nn.Module):
                          self._acc, use_dwgemm=self._use_dwconv)
         if not need_dx:
             return None
-        pkq = self._pack("qkvT", a + "w_qs.weight")
-        if raw_out:
-            if pkq is not None and raw_out == "pre" and d == 256:
-                return (dqkv, pkq, dz1)          # the consumer (the next block's first backward kernel) multiplies by the weight itself
-            if pkq is not None:
-                return (ops.win_conv_split(dqkv.view(Bn, S, 3 * d), pkq, d, 1), dz1)
+        if B.qkv_dx == "pre":
+            return (dqkv, self._pack("qkvT", a + "w_qs.weight"), dz1)     # the consumer (the block in front's first backward kernel) multiplies by the weight itself
+        if B.qkv_dx == "win_split":
+            return (ops.win_conv_split(dqkv.view(Bn, S, 3 * d), self._pack("qkvT", a + "w_qs.weight"), d, 1), dz1)
+        if B.qkv_dx == "gemm_raw":
             return (ops.linear_dx(dqkv, self._w(a + "w_qs.weight", 3 * d), raw=True), dz1)
-        if pkq is not None and d == 256 and dqkv.shape[1] == 768:
-            return ops.qkv_dx(dqkv, pkq, R=dz1)       # the first block of the stack: the same 32-row product as a kernel of its own
+        if B.qkv_dx == "qkv_dx":
+            return ops.qkv_dx(dqkv, self._pack("qkvT", a + "w_qs.weight"), R=dz1)       # the first block of the stack: the same 32-row product as a kernel of its own
         return ops.linear_dx(dqkv, self._w(a + "w_qs.weight", 3 * d), R=dz1)
 
     def _predictor_bwd(self, pre, saved, dout, rng, R, train=True, need_dx=True):
@@ -1521,12 +1436,14 @@ class FastSpeech2(nn.Module):
                 # (no `lens`: the PostNet's BatchNorm runs over the PAD rows too, Layers.py:133-143 — its gradients there are not zero)
                 ops.queue_dw(self._deferred, dy.view(Bn, T, C), xin, self._g(pp + "0.conv.weight"), None, self._acc, k=5,
                              use_dwgemm=self._use_dwconv)
-            pkt = self._pack("pnT", pp + "0.conv.weight")
-            if i > 0 and pkt is not None:
-                cw = self._table[pp + "0.conv.weight"].storage_shape
+            route = ctx.plan.postnet[i].dx
+            cw = self._table[pp + "0.conv.weight"].storage_shape
+            if route == "gemm" and i > 0:
+                dout = ops.conv1d_dx(dy.view(Bn, T, C), self._w(pp + "0.conv.weight")).view(rows, -1)
+            elif i > 0:
+                pkt = self._pack("pnT", pp + "0.conv.weight")
                 pb, _, ycb, meanb, rstdb, keepb = ctx.pn[i - 1]
-                if (C in (512, 80) and cw[2] == 512 and ycb.dtype == torch.float32 and ops.bn_slab_supported(cw[2])
-                        and (keepb is not None or self.p_post == 0.0)):
+                if route == "win_bnb" and (keepb is not None or self.p_post == 0.0):
                     # ... which also sums the BatchNorm-backward statistics of the layer below over its output tile
                     dout, bn_partials = ops.win_conv_bnb(dy.view(Bn, T, C), pkt, cw[2], cw[1], ycb.view(rows, cw[2]), meanb, rstdb,
                                                          self._m(pb + "1.weight"), self._m(pb + "1.bias"), True, p=self.p_post, keep=keepb,
@@ -1534,12 +1451,9 @@ class FastSpeech2(nn.Module):
                     dout = dout.view(rows, -1)
                 else:
                     dout = ops.win_conv(dy.view(Bn, T, C), pkt, cw[2], cw[1]).view(rows, -1)   # dX as a forward conv on the transposed pack
-            elif i > 0:
-                dout = ops.conv1d_dx(dy.view(Bn, T, C), self._w(pp + "0.conv.weight")).view(rows, -1)
             elif need_mel:
-                if pkt is not None:          # the first conv's input gradient (512 -> 80) + the mel terms' own gradient, on the window kernel
-                    cw = self._table[pp + "0.conv.weight"].storage_shape
-                    dmel_tot = ops.win_conv_resid(dy.view(Bn, T, C), pkt, dmel_sum.view(Bn, T, nm), cw[2], cw[1]).view(rows, nm)
+                if route == "win_resid":     # the first conv's input gradient (512 -> 80) + the mel terms' own gradient, on the window kernel
+                    dmel_tot = ops.win_conv_resid(dy.view(Bn, T, C), self._pack("pnT", pp + "0.conv.weight"), dmel_sum.view(Bn, T, nm), cw[2], cw[1]).view(rows, nm)
                 else:
                     dmel_tot = ops.conv1d_dx(dy.view(Bn, T, C), self._w(pp + "0.conv.weight"), R=dmel_sum.view(Bn, T, nm)).view(rows, nm)
                 if ctx.frame_limit is not None:
@@ -1552,16 +1466,14 @@ class FastSpeech2(nn.Module):
             ops.linear_dw(dmel_tot, ctx.dec_out, self._g("mel_linear.weight"), defer=self._deferred, accumulate=self._acc)
         dx = None
         if need_dec:
-            pkm = self._pack("linT", "mel_linear.weight")
-            if pkm is not None and dmel_tot.dtype == bf16:
-                dx = ops.win_conv(dmel_tot.view(Bn, T, nm), pkm, d, 1).view(rows, d)      # mel_linear's input gradient: a k = 1 conv on the transposed pack
+            if ctx.plan.mel_dx == "win":
+                dx = ops.win_conv(dmel_tot.view(Bn, T, nm), self._pack("linT", "mel_linear.weight"), d, 1).view(rows, d)      # mel_linear's input gradient: a k = 1 conv on the transposed pack
             else:
                 dx = ops.linear_dx(dmel_tot, self._w("mel_linear.weight"))
         notify("mel_linear")
         # ---- decoder: down to the lowest block whose gradient anything wants
         for i in range(self.n_dec - 1, dec_stop - 1, -1):
-            dx = self._fft_bwd(ctx.blocks[ctx.n_enc_blocks + i], dx, rng, raw_out=self._raw_out_mode() if i > 0 else False,
-                               **bkw(dec_on[i], need_below or i > dec_stop))
+            dx = self._fft_bwd(ctx.blocks[ctx.n_enc_blocks + i], dx, rng, raw_out=i > 0, **bkw(dec_on[i], need_below or i > dec_stop))
             notify("decoder.%d" % i)
         ops.stamp("bwd.decoder_done")
         if pred_dxin is not None:
@@ -1612,8 +1524,7 @@ class FastSpeech2(nn.Module):
         if need_enc:
             dx = dxe.view(Bn * Lp, d)
             for i in range(self.n_enc - 1, enc_stop - 1, -1):
-                dx = self._fft_bwd(ctx.blocks[i], dx, rng, raw_out=self._raw_out_mode() if i > 0 else False,
-                                   **bkw(enc_on[i], emb_on or i > enc_stop))
+                dx = self._fft_bwd(ctx.blocks[i], dx, rng, raw_out=i > 0, **bkw(enc_on[i], emb_on or i > enc_stop))
                 notify("encoder.%d" % i)
             if emb_on:
                 ops.scatter_sum(dx, ctx.texts.view(-1), self._g("encoder.src_word_emb.weight"), skip_row=0, defer=self._deferred_fin, accumulate=self._acc)   # padding_idx=0
@@ -1627,3 +1538,7 @@ class FastSpeech2(nn.Module):
             self._dp_marks = []
         self._finalize_loss()       # (a schedule without the second stream: here, where this stream has seen both halves of the loss)
         self._ctx = None
+
+
+for _name in fs2_plan.TOGGLES:          # window_ffn, flash_attention, fused_ln, postnet_ends_win, dwconv
+    setattr(FastSpeech2, _name, property(lambda self, n=_name: self._toggles[n], lambda self, on, n=_name: self._set_toggle(n, on)))
