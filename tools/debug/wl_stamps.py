@@ -24,7 +24,8 @@ for name, B, S, K, proj in (("encoder w_2 + LN + q|k|v", 16, 64, 1024, True), ("
     gamma, beta = (1 + 0.1 * torch.randn(d, generator=g)).to(DEV), (0.1 * torch.randn(d, generator=g)).to(DEV)
     pw, pq = (torch.empty(w.numel(), dtype=torch.bfloat16, device=DEV) for w in (W, Wq))
     ops.win_conv_pack_items([(W, pw, False), (Wq, pq, False)])
-    fn = lambda: ops.win_ln_fwd(x, pw, bias, res, gamma, beta, proj=(pq, bq) if proj else None)
+    rng = ops.rng_of(ops.optim_state(DEV, seed=3))
+    fn = lambda: ops.win_ln_fwd(x, pw, bias, res, gamma, beta, p_pre=0.1, site_pre=1, rng=rng, proj=(pq, bq) if proj else None)    # dropout on, as in the train step
     nwg = (rows + 31) // 32
     for _ in range(3):
         fn()

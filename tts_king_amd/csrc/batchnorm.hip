@@ -25,7 +25,7 @@ struct BnCommon {
   const int* frame_limit;
   int seg_len;
   // Dropout keep bits of the forward, one byte per (row, channel quad), bit e = channel c4 + e kept (may be null).  The slab
-  // forward writes them and the slab backward kernels read them: Philox costs 40 quarter-rate integer multiplies per quad, and
+  // forward writes them and the slab backward kernels read them: Philox costs ~250 cycles of a wave per quad, and
   // regenerating the mask twice in the backward made those kernels VALU-bound.
   uint8_t* keep;
   // Per-utterance frame limit of the batched synthesis (bn_apply only): frames t >= lens[u], clamped to [0, seg_len], are written
@@ -55,9 +55,9 @@ __device__ __forceinline__ void ldx4(const void* x, int x_f32, int64_t off, floa
     ld4((const bf16_t*)x + off, v);
   }
 }
-__device__ __forceinline__ uint4 bits4(const uint64_t* rng, unsigned site, unsigned e4) {
-  const uint64_t seed = rng[0], step = rng[1];
-  return Philox::gen(make_uint2((unsigned)seed, (unsigned)(seed >> 32)), make_uint4(e4, site, (unsigned)step, (unsigned)(step >> 32)));
+// keep bits of channel quad e4 of the layer's [rows][C] tensor (common.h keep4; the same nibble the forward stores in `keep`)
+__device__ __forceinline__ unsigned bn_keep4(const uint64_t* rng, unsigned site, unsigned e4, unsigned thr) {
+  return keep4(rng[0], rng[1], site, e4, thr);
 }
 
 // ---- pass 1: per-column sum and sum of squares -> partials[blk][2C]
@@ -173,11 +173,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const BnCommon a, const f
       v[e] = (v[e] - m[e]) * rs[e] * g[e] + b[e];
       if (a.use_tanh) v[e] = tanh_fast(v[e]);
     }
-    if (a.p > 0.f) {
-      const uint4 bb = bits4(a.rng, a.site, (unsigned)i);
-      v[0] = bb.x >= thr ? v[0] * scale : 0.f; v[1] = bb.y >= thr ? v[1] * scale : 0.f;
-      v[2] = bb.z >= thr ? v[2] * scale : 0.f; v[3] = bb.w >= thr ? v[3] * scale : 0.f;
-    }
+    if (a.p > 0.f) drop4(v, bn_keep4(a.rng, a.site, (unsigned)i, thr), scale);
     if (resid) {
       const f32x4 rr = *(const f32x4*)(resid + (int64_t)r * a.C + c4);
 #pragma unroll
@@ -201,16 +197,10 @@ __device__ __forceinline__ void bn_dy(const BnCommon& a, const void* dout, int d
   } else {
     ld4((const bf16_t*)dout + (int64_t)r * a.C + c4, dy);
   }
+  // the forward's keep byte, or the same bits drawn again (they need no data: behind the requests above, before their first use)
   if (a.p > 0.f) {
-    if (a.keep) {
-      const unsigned kb = a.keep[i];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dy[e] = ((kb >> e) & 1u) ? dy[e] * scale : 0.f;
-    } else {
-      const uint4 bb = bits4(a.rng, a.site, (unsigned)i);
-      dy[0] = bb.x >= thr ? dy[0] * scale : 0.f; dy[1] = bb.y >= thr ? dy[1] * scale : 0.f;
-      dy[2] = bb.z >= thr ? dy[2] * scale : 0.f; dy[3] = bb.w >= thr ? dy[3] * scale : 0.f;
-    }
+    if (a.keep) drop4(dy, a.keep[i], scale);
+    else drop4(dy, bn_keep4(a.rng, a.site, (unsigned)i, thr), scale);
   }
 #pragma unroll
   for (int e = 0; e < 4; ++e) xh[e] = (v[e] - m[e]) * rs[e];
@@ -444,6 +434,8 @@ __global__ __launch_bounds__(256, RESID ? 3 : 4) void bn_apply2_kernel(const BnC
   }
   __syncthreads();
   if (!act) return;
+  // (the keep bits are drawn here, where they are applied: drawn under the wait for the partial rows — sixteen 16-byte loads in flight
+  // in a kernel held to 128 registers — the kernel traced 0.3-1.1 us SLOWER)
   const unsigned thr = keep_threshold(a.p);
   const float scale = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
 #pragma unroll
@@ -463,11 +455,9 @@ __global__ __launch_bounds__(256, RESID ? 3 : 4) void bn_apply2_kernel(const BnC
       if (a.use_tanh) v[u][e] = tanh_fast(v[u][e]);
     }
     if (a.p > 0.f) {
-      const uint4 bb = bits4(a.rng, a.site, (unsigned)i);
-      const bool k0 = bb.x >= thr, k1 = bb.y >= thr, k2 = bb.z >= thr, k3 = bb.w >= thr;
-      v[u][0] = k0 ? v[u][0] * scale : 0.f; v[u][1] = k1 ? v[u][1] * scale : 0.f;
-      v[u][2] = k2 ? v[u][2] * scale : 0.f; v[u][3] = k3 ? v[u][3] * scale : 0.f;
-      if (a.keep) a.keep[i] = (uint8_t)((int)k0 | ((int)k1 << 1) | ((int)k2 << 2) | ((int)k3 << 3));
+      const unsigned nib = bn_keep4(a.rng, a.site, (unsigned)i, thr);
+      drop4(v[u], nib, scale);
+      if (a.keep) a.keep[i] = (uint8_t)nib;
     }
     if constexpr (RESID) {
 #pragma unroll

@@ -120,26 +120,36 @@ template <bool F16> __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, 
 
 // Philox4x32-10 counter RNG: dropout masks are regenerated in backward from (seed, site, element index),
 // never stored (reference dropout sites: SubLayers.py:62,99; modules.py:286,298; Layers.py:137-141).
+// The two products of a round are written as ONE 64-bit product each (v_mad_u64_u32: 18 per call) instead of a __umulhi + * pair
+// (18 v_mul_hi_u32 + 18 v_mul_lo_u32): the same words, 0.76 x the cycles per call (tools/debug/philox_rate_micro.hip,
+// profiles/philox_micro.txt).
 struct Philox {
   __device__ static __forceinline__ uint4 gen(uint2 key, uint4 ctr) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
-      unsigned hi0 = __umulhi(0xD2511F53u, ctr.x), lo0 = 0xD2511F53u * ctr.x;
-      unsigned hi1 = __umulhi(0xCD9E8D57u, ctr.z), lo1 = 0xCD9E8D57u * ctr.z;
-      ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
+      const uint64_t p0 = (uint64_t)0xD2511F53u * ctr.x, p1 = (uint64_t)0xCD9E8D57u * ctr.z;
+      ctr = make_uint4((unsigned)(p1 >> 32) ^ ctr.y ^ key.x, (unsigned)p1, (unsigned)(p0 >> 32) ^ ctr.w ^ key.y, (unsigned)p0);
       key.x += 0x9E3779B9u;
       key.y += 0xBB67AE85u;
     }
     return ctr;
   }
 };
-// keep-mask bits for 4 consecutive elements starting at element index e4*4 of dropout site `site`
-__device__ __forceinline__ uint4 dropout_bits(uint64_t seed, unsigned site, unsigned e4) {
-  return Philox::gen(make_uint2((unsigned)seed, (unsigned)(seed >> 32)), make_uint4(e4, site, 0x5eedu, 0u));
-}
 __device__ __forceinline__ unsigned keep_threshold(float p) {  // keep iff bits >= thr  (P(keep) = 1-p)
   double t = (double)p * 4294967296.0;
   return t >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)t;
+}
+// The dropout mask in two steps, the only way any kernel draws or applies it.  keep4: the keep bits of the quad e4 (elements 4 e4 ..
+// 4 e4 + 3 of the site's row-major tensor) as a nibble, bit e = element 4 e4 + e is kept = word e of Philox4x32-10(key = seed,
+// counter = (e4, site, step)) >= thr.  It depends on no data, so a kernel draws it while its loads are in flight and applies it
+// (drop4) where the values exist.
+__device__ __forceinline__ unsigned keep4(uint64_t seed, uint64_t step, unsigned site, unsigned e4, unsigned thr) {
+  const uint4 b = Philox::gen(make_uint2((unsigned)seed, (unsigned)(seed >> 32)), make_uint4(e4, site, (unsigned)step, (unsigned)(step >> 32)));
+  return (unsigned)(b.x >= thr) | ((unsigned)(b.y >= thr) << 1) | ((unsigned)(b.z >= thr) << 2) | ((unsigned)(b.w >= thr) << 3);
+}
+__device__ __forceinline__ void drop4(float v[4], unsigned nib, float scale) {       // kept: scaled; dropped: zero
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = ((nib >> e) & 1u) ? v[e] * scale : 0.f;
 }
 
 // host-side error plumbing

@@ -26,15 +26,6 @@ __device__ __forceinline__ void load4(const bf16_t* p, float v[4]) {
 __device__ __forceinline__ void store4(bf16_t* p, const float v[4]) {
   *(uint2*)p = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
 }
-// the same bits as layernorm.hip draws for (seed, step, site, element / 4)
-__device__ __forceinline__ void drop4(float v[4], uint64_t seed, uint64_t step, unsigned site, unsigned e4, unsigned thr, float scale) {
-  const uint4 b = Philox::gen(make_uint2((unsigned)seed, (unsigned)(seed >> 32)),
-                              make_uint4(e4, site, (unsigned)step, (unsigned)(step >> 32)));
-  v[0] = b.x >= thr ? v[0] * scale : 0.f;
-  v[1] = b.y >= thr ? v[1] * scale : 0.f;
-  v[2] = b.z >= thr ? v[2] * scale : 0.f;
-  v[3] = b.w >= thr ? v[3] * scale : 0.f;
-}
 
 // ------------------------------------------------------------------------------------------ 11-wide predictor head
 struct HeadArgs {
@@ -73,7 +64,7 @@ __global__ __launch_bounds__(256) void ln_head_fwd_kernel(const HeadArgs a) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) o[e] = (z[e] - mean) * rstd * g[e] + bt[e];
   if (a.p_post > 0.f)
-    drop4(o, seed, step, a.site_post, (unsigned)(((int64_t)row * D + c) >> 2), keep_threshold(a.p_post), 1.f / (1.f - a.p_post));
+    drop4(o, keep4(seed, step, a.site_post, (unsigned)(((int64_t)row * D + c) >> 2), keep_threshold(a.p_post)), 1.f / (1.f - a.p_post));
 #pragma unroll
   for (int k = 0; k < NH; ++k) {
     const f32x4 w = *(const f32x4*)(a.head_w + k * D + c);
@@ -122,8 +113,9 @@ __global__ __launch_bounds__(HB_WAVES * 64) void ln_head_bwd_kernel(const HeadBw
     float xh[4], o[4], d[4] = {0, 0, 0, 0};
 #pragma unroll
     for (int e = 0; e < 4; ++e) { xh[e] = (zz[e] - mean) * rstd; o[e] = xh[e] * gm[e] + bt[e]; }
-    if (a.p_post > 0.f)
-      drop4(o, seed, step, a.site_post, (unsigned)(((int64_t)row * D + c) >> 2), keep_threshold(a.p_post), 1.f / (1.f - a.p_post));
+    // the row's keep bits once, for the recomputed output and for its gradient
+    const unsigned kpost = a.p_post > 0.f ? keep4(seed, step, a.site_post, (unsigned)(((int64_t)row * D + c) >> 2), keep_threshold(a.p_post)) : 0u;
+    if (a.p_post > 0.f) drop4(o, kpost, 1.f / (1.f - a.p_post));
 #pragma unroll
     for (int k = 0; k < NH; ++k) {
       const float dh = masked ? 0.f : a.dhead[(int64_t)row * NH + k];
@@ -132,8 +124,7 @@ __global__ __launch_bounds__(HB_WAVES * 64) void ln_head_bwd_kernel(const HeadBw
       for (int e = 0; e < 4; ++e) { d[e] += dh * w[e]; dhw[k][e] += dh * o[e]; }
       dhb[k] += dh;           // every lane carries the same sum; lane 0's is used
     }
-    if (a.p_post > 0.f)
-      drop4(d, seed, step, a.site_post, (unsigned)(((int64_t)row * D + c) >> 2), keep_threshold(a.p_post), 1.f / (1.f - a.p_post));
+    if (a.p_post > 0.f) drop4(d, kpost, 1.f / (1.f - a.p_post));
     float g[4], c1 = 0.f, c2 = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {

@@ -62,26 +62,53 @@ struct GemmLnArgs {
 #define WL_STAMP(i) do {} while (0)        // the product library carries no stamp code and no global state for it
 #endif
 
-__device__ __forceinline__ void drop4(float v[4], uint64_t seed, uint64_t step, unsigned site, unsigned e4, unsigned thr, float scale) {
-  const uint4 b = Philox::gen(make_uint2((unsigned)seed, (unsigned)(seed >> 32)),
-                              make_uint4(e4, site, (unsigned)step, (unsigned)(step >> 32)));
-  v[0] = b.x >= thr ? v[0] * scale : 0.f;
-  v[1] = b.y >= thr ? v[1] * scale : 0.f;
-  v[2] = b.z >= thr ? v[2] * scale : 0.f;
-  v[3] = b.w >= thr ? v[3] * scale : 0.f;
+struct uint2x64 { uint64_t seed, step; };
+// The keep bits of this wave's RW epilogue rows (common.h keep4: nibble rr = row m0 + wave * RW + rr, columns 4 * lane .. + 3 — ln_fwd_kernel's
+// indexing).  They depend on no data: the kernels draw them right behind their global loads, under the wait for those, and ln_rows_epilogue
+// applies them.  Without dropout: 0, no Philox code runs and rng is not read.  The kernels read {seed, step} (ln_rng) as their first
+// instruction: a scalar load there, long back by the time the bits are drawn (behind the kernel's own requests it would be a vector
+// load that waits for all of them).
+__device__ __forceinline__ uint2x64 ln_rng(const GemmLnArgs& a) {
+  uint2x64 r = {0, 0};
+  if (a.p_pre > 0.f) { r.seed = a.rng[0]; r.step = a.rng[1]; }
+  return r;
+}
+// The residual rows of this wave's RW epilogue rows, requested with no branch around the loads (a branch's join copies the loaded
+// registers, and the wait for them — for every older request as well — lands there, in front of the K loop): a row past M reads
+// row M - 1, a null residual reads gamma (1 KiB that exists), and ln_rows_epilogue counts both as zero.
+template <int RW>
+__device__ __forceinline__ void ln_rows_res(const GemmLnArgs& a, int m0, int wave, int lane, uint2 (&resv)[RW]) {
+  const bf16_t* src = a.res ? a.res : (const bf16_t*)a.gamma;
+#pragma unroll
+  for (int rr = 0; rr < RW; ++rr) {
+    const int row = min(m0 + wave * RW + rr, a.M - 1);
+    resv[rr] = *(const uint2*)(src + (a.res ? (int64_t)row * BN : 0) + lane * 4);
+  }
+}
+template <int RW>
+__device__ __forceinline__ unsigned ln_rows_keep(const GemmLnArgs& a, uint2x64 rng, int m0, int wave, int lane) {
+  static_assert(RW <= 8, "one nibble per row in 32 bits");
+  unsigned kb = 0;
+  if (a.p_pre > 0.f) {
+    const uint64_t seed = rng.seed, step = rng.step;
+    const unsigned thr = keep_threshold(a.p_pre);
+#pragma unroll
+    for (int rr = 0; rr < RW; ++rr)
+      kb |= keep4(seed, step, a.site_pre, (unsigned)(((int64_t)(m0 + wave * RW + rr) * BN + lane * 4) >> 2), thr) << (4 * rr);
+  }
+  return kb;
 }
 
 // The LayerNorm rows of a 32 x 256 fp32 tile `cs` (leading dimension CS_LD): one wave per row, RW rows per wave, lane owns columns
 // 4*lane .. 4*lane+3 (ln_fwd_kernel's row code: same Philox indexing, so ln_bwd_kernel regenerates the same dropout mask).
+// kb: ln_rows_keep's bits, drawn by the caller ahead of its K loop.  resv: ln_rows_res's raw rows.
 // xs2 (may be null): LDS tile [32][P32_RS] that receives the output rows as well (zero rows past M), proj32.h's B operand.
 template <int RW>
-__device__ __forceinline__ void ln_rows_epilogue(const GemmLnArgs& a, const float* cs, int m0, int wave, int lane, const uint2 (&resv)[RW],
+__device__ __forceinline__ void ln_rows_epilogue(const GemmLnArgs& a, const float* cs, int m0, int wave, int lane, const uint2 (&resv)[RW], unsigned kb,
                                                  unsigned char* xs2 = nullptr, bool write = true /* false: the rows go to xs2 only (win_ln_kernel's SPLIT parts > 0) */) {
   const int M = a.M, c = lane * 4;
-  const uint64_t seed = a.rng ? a.rng[0] : 0, step = a.rng ? a.rng[1] : 0;
   const f32x4 bi = *(const f32x4*)(a.bias + c);
   const f32x4 g = *(const f32x4*)(a.gamma + c), bt = *(const f32x4*)(a.beta + c);
-  const unsigned thr = keep_threshold(a.p_pre);
   const float scale = 1.f / (1.f - a.p_pre);
   float z[RW][4];
   float s[RW];
@@ -93,9 +120,10 @@ __device__ __forceinline__ void ln_rows_epilogue(const GemmLnArgs& a, const floa
     const f32x4 v = *(const f32x4*)(cs + lr * CS_LD + c);
 #pragma unroll
     for (int e = 0; e < 4; ++e) z[rr][e] = v[e] + bi[e];
-    if (a.p_pre > 0.f) drop4(z[rr], seed, step, a.site_pre, (unsigned)(((int64_t)row * BN + c) >> 2), thr, scale);
-    z[rr][0] += __uint_as_float(resv[rr].x << 16); z[rr][1] += __uint_as_float(resv[rr].x & 0xFFFF0000u);
-    z[rr][2] += __uint_as_float(resv[rr].y << 16); z[rr][3] += __uint_as_float(resv[rr].y & 0xFFFF0000u);
+    if (a.p_pre > 0.f) drop4(z[rr], kb >> (4 * rr), scale);
+    const uint2 rv = (a.res && live) ? resv[rr] : make_uint2(0u, 0u);
+    z[rr][0] += __uint_as_float(rv.x << 16); z[rr][1] += __uint_as_float(rv.x & 0xFFFF0000u);
+    z[rr][2] += __uint_as_float(rv.y << 16); z[rr][3] += __uint_as_float(rv.y & 0xFFFF0000u);
     if (a.z_save && live && write) *(uint2*)(a.z_save + (int64_t)row * BN + c) = make_uint2(pack_bf2(z[rr][0], z[rr][1]), pack_bf2(z[rr][2], z[rr][3]));
     s[rr] = z[rr][0] + z[rr][1] + z[rr][2] + z[rr][3];
   }
@@ -148,6 +176,7 @@ __global__ __launch_bounds__(NW * 64, 1) void gemm_ln_kernel(const GemmLnArgs a)
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, lg = lane >> 4;
+  const uint2x64 rng = ln_rng(a);
   const int m0 = blockIdx.x * BM;
   const int M = a.M, K = a.K;
   const int K8 = (K + 7) & ~7;
@@ -158,11 +187,7 @@ __global__ __launch_bounds__(NW * 64, 1) void gemm_ln_kernel(const GemmLnArgs a)
 
   // ---- residual rows of this wave's eight epilogue rows: in flight during the whole K loop
   uint2 resv[RW];
-#pragma unroll
-  for (int rr = 0; rr < RW; ++rr) {
-    const int row = m0 + wave * RW + rr;
-    resv[rr] = (a.res && row < M) ? *(const uint2*)(a.res + (int64_t)row * BN + c) : make_uint2(0u, 0u);
-  }
+  ln_rows_res<RW>(a, m0, wave, lane, resv);
 
   // ---- LDS-DMA source coordinates.  A piece = 1 KiB of the LDS image = 8 tile rows x 128 B; lane -> tile row 8p + lane/8,
   // physical 16-byte chunk lane%8, which must hold logical chunk (lane%8) ^ (row & 7): the XOR swizzle of the fragment reads
@@ -197,6 +222,10 @@ __global__ __launch_bounds__(NW * 64, 1) void gemm_ln_kernel(const GemmLnArgs a)
 #pragma unroll
   for (int t = 0; t < NSTAGE - 1; ++t)
     if (t < nk) issue_tile(t);
+  // the epilogue rows' dropout bits, under the wait for the first tile (nothing of it is inside the K loop)
+  __builtin_amdgcn_sched_barrier(0);
+  const unsigned kb = ln_rows_keep<RW>(a, rng, m0, wave, lane);
+  __builtin_amdgcn_sched_barrier(0);
 
   for (int kt = 0; kt < nk; ++kt) {
     // this wave's pieces of tile kt have landed when at most the pieces of the (up to two) younger tiles are outstanding
@@ -243,7 +272,7 @@ __global__ __launch_bounds__(NW * 64, 1) void gemm_ln_kernel(const GemmLnArgs a)
       for (int r = 0; r < 4; ++r) cs[(i * 16 + lg * 4 + r) * CS_LD + wave * WC + j * 16 + l15] = acc[i][j][r];
   __syncthreads();
 
-  ln_rows_epilogue<RW>(a, cs, m0, wave, lane, resv);
+  ln_rows_epilogue<RW>(a, cs, m0, wave, lane, resv, kb);
 }
 
 
@@ -267,6 +296,7 @@ __global__ __launch_bounds__(512, (CIN == 256 && !PROJ) ? 2 : 1) void win_ln_ker
   const int part = SPLIT > 1 ? (int)blockIdx.x % SPLIT : 0;
   const int m0 = (SPLIT > 1 ? (int)blockIdx.x / SPLIT : (int)blockIdx.x) * BM;
   const int M = a.M;
+  const uint2x64 rng = ln_rng(a);
   WL_STAMP(0);
   // weight fragments by buffer loads, activation fragments a step ahead of their MFMAs (tapring.h)
   const __amdgpu_buffer_rsrc_t wres = weights_rsrc(a.W, CIN * BN * 2);
@@ -275,31 +305,33 @@ __global__ __launch_bounds__(512, (CIN == 256 && !PROJ) ? 2 : 1) void win_ln_ker
   bf16x8 wa[KH][CT], wb[KH][CT], wc[KH][CT];
   auto load_w = [&](int g, bf16x8 (&w)[KH][CT]) __attribute__((always_inline)) { frags_load<KH, CT>(w, wres, wlane, g * KH * kstep_bytes, kstep_bytes); };
   uint2 resv[RW];
+  unsigned kb;
   {
     // request order = arrival order: the rows of A (nothing starts before they are in LDS), the first three steps' weight fragments,
-    // the residual rows (read in the epilogue)
+    // the residual rows (read in the epilogue).  Then, with every request out and the vector ALU otherwise idle until the rows of A
+    // arrive, the epilogue rows' dropout bits.  No branch around any request (ln_rows_res says why: with the branches, the rows of A
+    // were waited for before the weights were even asked for): a row of A past M reads row M - 1 and goes to LDS as zeros.
     constexpr int NCH = (TT * CH8 + NT - 1) / NT;
     uint4 xv[NCH];
 #pragma unroll
     for (int it = 0; it < NCH; ++it) {
       const int idx = it * NT + tid;
       const int row = idx / CH8, ch = idx - row * CH8;
-      xv[it] = make_uint4(0, 0, 0, 0);
-      if (idx < TT * CH8 && m0 + row < M) xv[it] = *(const uint4*)(a.A + (int64_t)(m0 + row) * a.lda + ch * 8);
+      static_assert((TT * CH8) % NT == 0, "every thread has a chunk in every pass");
+      xv[it] = *(const uint4*)(a.A + (int64_t)min(m0 + row, M - 1) * a.lda + ch * 8);
     }
     load_w(0, wa);
     if (1 < NS) load_w(1, wb);
     if (2 < NS) load_w(2, wc);
-#pragma unroll
-    for (int rr = 0; rr < RW; ++rr) {
-      const int row = m0 + wave * RW + rr;
-      resv[rr] = (a.res && row < M) ? *(const uint2*)(a.res + (int64_t)row * BN + lane * 4) : make_uint2(0u, 0u);
-    }
+    ln_rows_res<RW>(a, m0, wave, lane, resv);
+    __builtin_amdgcn_sched_barrier(0);
+    kb = ln_rows_keep<RW>(a, rng, m0, wave, lane);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int it = 0; it < NCH; ++it) {
       const int idx = it * NT + tid;
       const int row = idx / CH8, ch = idx - row * CH8;
-      if (idx < TT * CH8) *(uint4*)(smem + row * RS + ch * 16) = xv[it];
+      *(uint4*)(smem + row * RS + ch * 16) = m0 + row < M ? xv[it] : make_uint4(0, 0, 0, 0);
     }
   }
   WL_STAMP(1);
@@ -350,7 +382,7 @@ __global__ __launch_bounds__(512, (CIN == 256 && !PROJ) ? 2 : 1) void win_ln_ker
 #pragma unroll
     for (int cc = 0; cc < CT; ++cc) *(f32x4*)(cs + (i * 16 + l15) * CS_LD + (wave * CT + cc) * 16 + q * 4) = acc[cc][i];
   __syncthreads();
-  ln_rows_epilogue<RW>(a, cs, m0, wave, lane, resv, PROJ ? ptile : nullptr, part == 0);
+  ln_rows_epilogue<RW>(a, cs, m0, wave, lane, resv, kb, PROJ ? ptile : nullptr, part == 0);
   WL_STAMP(5);
   if (PROJ) {
     __syncthreads();

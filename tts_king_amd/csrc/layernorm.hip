@@ -42,14 +42,6 @@ __device__ __forceinline__ void load4(const bf16_t* p, float v[4]) {
 __device__ __forceinline__ void store4(bf16_t* p, const float v[4]) {
   *(uint2*)p = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
 }
-__device__ __forceinline__ void drop4(float v[4], uint64_t seed, uint64_t step, unsigned site, unsigned e4, unsigned thr, float scale) {
-  const uint4 b = Philox::gen(make_uint2((unsigned)seed, (unsigned)(seed >> 32)),
-                              make_uint4(e4, site, (unsigned)step, (unsigned)(step >> 32)));
-  v[0] = b.x >= thr ? v[0] * scale : 0.f;
-  v[1] = b.y >= thr ? v[1] * scale : 0.f;
-  v[2] = b.z >= thr ? v[2] * scale : 0.f;
-  v[3] = b.w >= thr ? v[3] * scale : 0.f;
-}
 
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnArgs a) {
   const int lane = threadIdx.x & 63;
@@ -70,7 +62,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnArgs a) {
       const int c = j * 256 + lane * 4;
       load4(a.y + (int64_t)row * D + c, z[j]);
       if (a.p_pre > 0.f)
-        drop4(z[j], seed, step, site_pre, (unsigned)(((int64_t)lrow * D + c) >> 2), keep_threshold(a.p_pre), 1.f / (1.f - a.p_pre));
+        drop4(z[j], keep4(seed, step, site_pre, (unsigned)(((int64_t)lrow * D + c) >> 2), keep_threshold(a.p_pre)), 1.f / (1.f - a.p_pre));
       if (a.res) {
         float r[4];
         load4(a.res + (int64_t)row * D + c, r);
@@ -104,7 +96,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnArgs a) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = (z[j][e] - mean) * rstd * g[e] + bt[e];
       if (a.p_post > 0.f)
-        drop4(o, seed, step, site_post, (unsigned)(((int64_t)lrow * D + c) >> 2), keep_threshold(a.p_post), 1.f / (1.f - a.p_post));
+        drop4(o, keep4(seed, step, site_post, (unsigned)(((int64_t)lrow * D + c) >> 2), keep_threshold(a.p_post)), 1.f / (1.f - a.p_post));
       if (masked) o[0] = o[1] = o[2] = o[3] = 0.f;
       if (a.out) store4(a.out + (int64_t)row * D + c, o);
       if (a.head_w) {
@@ -226,6 +218,9 @@ __global__ __launch_bounds__(LNB_WAVES * 64) void ln_bwd_kernel(const LnBwdArgs 
                              __uint_as_float(cur.z[j].y << 16), __uint_as_float(cur.z[j].y & 0xFFFF0000u)};
         float d[4] = {cur.d[j][0], cur.d[j][1], cur.d[j][2], cur.d[j][3]};
         const f32x4 gm = *(const f32x4*)(gamma + c);
+        // the post-dropout keep bits of the quad, once for the recomputed output (head mode) and for its gradient.  (Drawn where they
+        // are applied: this kernel's rows are one iteration ahead of their use already, drawing earlier traced -0.2 / +0.8 us.)
+        const unsigned kpost = a.p_post > 0.f ? keep4(seed, step, site_post, (unsigned)(((int64_t)lrow * D + c) >> 2), keep_threshold(a.p_post)) : 0u;
 #pragma unroll
         for (int e = 0; e < 4; ++e) xh[j][e] = (zz[e] - mean) * rstd;
         if (head) {
@@ -233,13 +228,11 @@ __global__ __launch_bounds__(LNB_WAVES * 64) void ln_bwd_kernel(const LnBwdArgs 
           float o[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) { o[e] = xh[j][e] * gm[e] + bt[e]; d[e] += dh * w[e]; }
-          if (a.p_post > 0.f)
-            drop4(o, seed, step, site_post, (unsigned)(((int64_t)lrow * D + c) >> 2), keep_threshold(a.p_post), 1.f / (1.f - a.p_post));
+          if (a.p_post > 0.f) drop4(o, kpost, 1.f / (1.f - a.p_post));
 #pragma unroll
           for (int e = 0; e < 4; ++e) dhw[j][e] += dh * o[e];
         }
-        if (a.p_post > 0.f)
-          drop4(d, seed, step, site_post, (unsigned)(((int64_t)lrow * D + c) >> 2), keep_threshold(a.p_post), 1.f / (1.f - a.p_post));
+        if (a.p_post > 0.f) drop4(d, kpost, 1.f / (1.f - a.p_post));
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           dg[j][e] += d[e] * xh[j][e];
@@ -268,7 +261,7 @@ __global__ __launch_bounds__(LNB_WAVES * 64) void ln_bwd_kernel(const LnBwdArgs 
         }
         if (a.dz) store4(a.dz + (int64_t)row * D + c, dzv);
         if (a.p_pre > 0.f) {
-          drop4(dzv, seed, step, site_pre, (unsigned)(((int64_t)lrow * D + c) >> 2), keep_threshold(a.p_pre), 1.f / (1.f - a.p_pre));
+          drop4(dzv, keep4(seed, step, site_pre, (unsigned)(((int64_t)lrow * D + c) >> 2), keep_threshold(a.p_pre)), 1.f / (1.f - a.p_pre));
           if (a.dy) store4(a.dy + (int64_t)row * D + c, dzv);
         }
 #pragma unroll
@@ -325,6 +318,11 @@ __device__ __forceinline__ void unpack8(uint4 u, float* v) {
 __device__ __forceinline__ uint4 pack8f(const float* v) {
   return make_uint4(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7]));
 }
+// A loaded value stays raw up to here: without it the compiler folds the unpacking into the branch that holds the load, and the wait
+// for the data lands there, in front of whatever was meant to run under it.
+__device__ __forceinline__ void hold(uint4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
+__device__ __forceinline__ void hold(f32x4& v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ void hold(float& v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ float group16_sum(float v) { return quad16_sum(v); }     // DPP, no LDS round trips (common.h)
 
 // One row of the D = 256 backward for a 16-lane group (lane l of the group owns columns c0 = 16 l .. + 15): the row's contributions
@@ -340,40 +338,66 @@ __device__ __forceinline__ void lnb256_row(const LnBwdArgs& a, int row, int c0, 
   float zz[16], d[16];
 #pragma unroll
   for (int e = 0; e < 16; ++e) { zz[e] = 0.f; d[e] = 0.f; }
-  float mean = 0.f, rstd = 0.f;
-  if (live) {
-    const bf16_t* zp = a.z + (int64_t)row * D + c0;
-    unpack8(*(const uint4*)zp, zz); unpack8(*(const uint4*)(zp + 8), zz + 8);
-    mean = a.mean[row]; rstd = a.rstd[row];
-    if (!masked) {
-      if (dl || a.slabs) {
-        if (dl) {
+  // The row's requests first, raw and with no branch around them (a branch's join copies the loaded registers, and the wait for the
+  // data lands there): z, the statistics, and the upstream gradient (the LDS tile, or slab 0 and R, or dout).  A row past the end
+  // reads the last row, a PAD row its own, and both discard what they read.  Then the keep bits of the lane's 16 columns (nibble i:
+  // columns c0 + 4 i .. + 3), which need none of it and are drawn under that wait; nothing is unpacked before.  Slabs 1 .. nsplit - 1
+  // follow as before, one batch per slab.
+  const bool slabbed = dl || a.slabs, use = live && !masked;
+  const int64_t ro = (int64_t)(live ? row : a.rows - 1) * D + c0;
+  uint4 zr[2] = {*(const uint4*)(a.z + ro), *(const uint4*)(a.z + ro + 8)};
+  float mean = a.mean[live ? row : a.rows - 1], rstd = a.rstd[live ? row : a.rows - 1];
+  const float* sp = a.slabs ? a.slabs + ro : nullptr;
+  const bool slab0 = !dl && a.slabs && a.nsplit > 0;
+  f32x4 s0[4];
+  if (dl) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s0[i] = *(const f32x4*)(dl + c0 + 4 * i);
+  } else {
+    const float* s0p = slab0 ? sp : a.gamma + c0;       // (no slab: 64 bytes that exist, unused)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s0[i] = *(const f32x4*)(s0p + 4 * i);
+  }
+  const bf16_t* up = slabbed ? (a.R ? a.R : a.z) : a.dout;      // (no R: z once more, unused)
+  uint4 ur[2] = {*(const uint4*)(up + ro), *(const uint4*)(up + ro + 8)};
+  __builtin_amdgcn_sched_barrier(0);
+  unsigned kb = 0;
+  if (a.p_pre > 0.f) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) kb |= keep4(seed, step, a.site_pre, (unsigned)(((int64_t)row * D + c0 + 4 * i) >> 2), thr) << (4 * i);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  hold(zr[0]); hold(zr[1]); hold(mean); hold(rstd); hold(ur[0]); hold(ur[1]);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) hold(s0[i]);
+  if (!live) { mean = 0.f; rstd = 0.f; }
+  if (live) { unpack8(zr[0], zz); unpack8(zr[1], zz + 8); }
+  if (use) {
+    if (slabbed) {
+      if (dl) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { d[4 * i] = s0[i][0]; d[4 * i + 1] = s0[i][1]; d[4 * i + 2] = s0[i][2]; d[4 * i + 3] = s0[i][3]; }
+      } else {
+        if (slab0) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) { d[4 * i] += s0[i][0]; d[4 * i + 1] += s0[i][1]; d[4 * i + 2] += s0[i][2]; d[4 * i + 3] += s0[i][3]; }
+        }
+        for (int q = 1; q < a.nsplit; ++q) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            const f32x4 t = *(const f32x4*)(dl + c0 + 4 * i);
-            d[4 * i] = t[0]; d[4 * i + 1] = t[1]; d[4 * i + 2] = t[2]; d[4 * i + 3] = t[3];
-          }
-        } else {
-          const float* sp = a.slabs + (int64_t)row * D + c0;
-          for (int q = 0; q < a.nsplit; ++q) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const f32x4 t = *(const f32x4*)(sp + q * a.slab_stride + 4 * i);
-              d[4 * i] += t[0]; d[4 * i + 1] += t[1]; d[4 * i + 2] += t[2]; d[4 * i + 3] += t[3];
-            }
+            const f32x4 t = *(const f32x4*)(sp + q * a.slab_stride + 4 * i);
+            d[4 * i] += t[0]; d[4 * i + 1] += t[1]; d[4 * i + 2] += t[2]; d[4 * i + 3] += t[3];
           }
         }
-        if (a.R) {
-          float r[16];
-          const bf16_t* rp = a.R + (int64_t)row * D + c0;
-          unpack8(*(const uint4*)rp, r); unpack8(*(const uint4*)(rp + 8), r + 8);
-#pragma unroll
-          for (int e = 0; e < 16; ++e) d[e] += r[e];
-        }
-      } else {
-        const bf16_t* dp = a.dout + (int64_t)row * D + c0;
-        unpack8(*(const uint4*)dp, d); unpack8(*(const uint4*)(dp + 8), d + 8);
       }
+      if (a.R) {
+        float r[16];
+        unpack8(ur[0], r); unpack8(ur[1], r + 8);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) d[e] += r[e];
+      }
+    } else {
+      unpack8(ur[0], d); unpack8(ur[1], d + 8);
     }
   }
   // explicit roundings (no contraction left to the compiler): this function is inlined into two kernels, which must agree bit for bit
@@ -397,7 +421,7 @@ __device__ __forceinline__ void lnb256_row(const LnBwdArgs& a, int row, int c0, 
   }
   if (a.p_pre > 0.f) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) drop4(dzv + 4 * i, seed, step, a.site_pre, (unsigned)(((int64_t)row * D + c0 + 4 * i) >> 2), thr, dscale);
+    for (int i = 0; i < 4; ++i) drop4(dzv + 4 * i, kb >> (4 * i), dscale);
     if (live && a.dy) {
       bf16_t* op = a.dy + (int64_t)row * D + c0;
       *(uint4*)op = pack8f(dzv); *(uint4*)(op + 8) = pack8f(dzv + 8);
@@ -628,11 +652,12 @@ __global__ __launch_bounds__(LNB_WAVES * 64, 1) void ln_bwd256_proj_kernel(const
   const int grp = lane >> 4, l = lane & 15, c0 = l * 16;
   const int m0 = tile * P32_TT;
   Proj32W W;
+  // {seed, step} first: a scalar load here, back long before the rows' keep bits are drawn under the wait for the rows (lnb256_row)
+  const uint64_t seed = a.rng ? a.rng[0] : 0, step = a.rng ? a.rng[1] : 0;
   LNB_STAMP(0);
   if (PRE) pre768_gemm(p.pre_x, p.pre_w, m0, a.rows, smem, dtile);
   LNB_STAMP(1);
   {
-    const uint64_t seed = a.rng ? a.rng[0] : 0, step = a.rng ? a.rng[1] : 0;
     const unsigned thr = keep_threshold(a.p_pre);
     const float dscale = a.p_pre > 0.f ? 1.f / (1.f - a.p_pre) : 1.f;
     float gam[16];

@@ -782,8 +782,8 @@ __global__ __launch_bounds__(256) void dropout_keep_mask_kernel(const uint64_t* 
   const uint64_t seed = rng[0], step = rng[1];
   const unsigned thr = keep_threshold(p);
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    const uint4 b = Philox::gen(make_uint2((unsigned)seed, (unsigned)(seed >> 32)), make_uint4((unsigned)i, site, (unsigned)step, (unsigned)(step >> 32)));
-    *(uchar4*)(keep + i * 4) = make_uchar4(b.x >= thr, b.y >= thr, b.z >= thr, b.w >= thr);
+    const unsigned nib = keep4(seed, step, site, (unsigned)i, thr);
+    *(uchar4*)(keep + i * 4) = make_uchar4(nib & 1u, (nib >> 1) & 1u, (nib >> 2) & 1u, (nib >> 3) & 1u);
   }
 }
 }  // namespace
