@@ -31,7 +31,24 @@ struct BnCommon {
   // Per-utterance frame limit of the batched synthesis (bn_apply only): frames t >= lens[u], clamped to [0, seg_len], are written
   // as zero rows -- the next convolution's zero padding in a solo run of utterance u.  null = none.
   const long long* lens;
+#ifdef TTSK_STAMPS
+  unsigned long long* stamps;   // diagnostic build only (make stamps; ttsk_bn_set_stamps): 8 x s_memrealtime per workgroup
+#endif
 };
+#ifdef TTSK_STAMPS
+// [0] start, [1] rows requested, [2] requested rows and partial rows arrived (the stamp waits for them), [3] totals done, [4] mean / rstd
+// (or the two sums) published, [5] arithmetic done, [6] stores issued, [7] stores acknowledged.  Thread 0's view of its workgroup.
+#define BN_STAMP(st, i)                                                                                                    \
+  do {                                                                                                                     \
+    if ((st) && threadIdx.x == 0) (st)[(int64_t)(blockIdx.y * gridDim.x + blockIdx.x) * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); \
+  } while (0)
+#define BN_STAMP_WAIT(st, i) do { if (st) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); BN_STAMP(st, i); } while (0)
+#define BN_STAMPS_OF(a) ((a).stamps)
+#else
+#define BN_STAMP(st, i) do {} while (0)         // the product library carries no stamp code and no global state for it
+#define BN_STAMP_WAIT(st, i) do {} while (0)
+#define BN_STAMPS_OF(a) nullptr
+#endif
 // tanh = 1 - 2 / (exp(2x) + 1) on the hardware exp and reciprocal: absolute error ~1e-7 (the result is stored as bf16, or multiplies
 // a bf16 gradient); libm's tanhf is ~4x the instructions, and these kernels are VALU-bound
 __device__ __forceinline__ float tanh_fast(float x) { return 1.f - 2.f * __frcp_rn(__expf(2.f * x) + 1.f); }
@@ -186,33 +203,68 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const BnCommon a, const f
 
 // gradient wrt the BN output y (before tanh/dropout) for 4 channels of one row.  No branch around the loads (a row past the frame
 // limit is real memory, its results are zeroed at the end), so that the loads of several rows of an unrolled loop go out together.
-__device__ __forceinline__ void bn_dy(const BnCommon& a, const void* dout, int dout_f32, int r, int c4, int64_t i, unsigned thr,
-                                      float scale, float xh[4], float dy[4]) {
-  float v[4];
-  ldx4(a.x, a.x_f32, (int64_t)r * a.C + c4, v);
-  const f32x4 m = *(const f32x4*)(a.mean + c4), rs = *(const f32x4*)(a.rstd + c4);
+// In two halves, so that a kernel can put other requests between them: bn_dy_load requests what is per row (x, dout, the forward's keep
+// byte), bn_dy_math loads what is per channel and does the arithmetic.  `live`: whether row r is a frame of the batch (the slab kernels
+// read the frame limit once and pass it in).
+// x_f32, dout_f32 and drop (how the dropout mask comes: BN_DROP_*) are compile-time constants in the slab kernels: a run-time choice
+// between two loads is a branch, and the compiler ends each such branch with a wait for everything in flight.
+enum { BN_DROP_NONE = 0, BN_DROP_KEEP = 1, BN_DROP_RNG = 2 };
+__device__ __forceinline__ int bn_drop_mode(const BnCommon& a) { return a.p > 0.f ? (a.keep ? BN_DROP_KEEP : BN_DROP_RNG) : BN_DROP_NONE; }
+struct BnRowIn {
+  float v[4], dy[4];
+  unsigned keep;
+};
+__device__ __forceinline__ void bn_dy_load(const BnCommon& a, int x_f32, const void* dout, int dout_f32, int drop, int r, int c4, int64_t i,
+                                           BnRowIn& in) {
+  ldx4(a.x, x_f32, (int64_t)r * a.C + c4, in.v);
   if (dout_f32) {
     const f32x4 d = *(const f32x4*)((const float*)dout + (int64_t)r * a.C + c4);
-    dy[0] = d[0]; dy[1] = d[1]; dy[2] = d[2]; dy[3] = d[3];
+    in.dy[0] = d[0]; in.dy[1] = d[1]; in.dy[2] = d[2]; in.dy[3] = d[3];
   } else {
-    ld4((const bf16_t*)dout + (int64_t)r * a.C + c4, dy);
+    ld4((const bf16_t*)dout + (int64_t)r * a.C + c4, in.dy);
   }
-  // the forward's keep byte, or the same bits drawn again (they need no data: behind the requests above, before their first use)
-  if (a.p > 0.f) {
-    if (a.keep) drop4(dy, a.keep[i], scale);
-    else drop4(dy, bn_keep4(a.rng, a.site, (unsigned)i, thr), scale);
-  }
+  in.keep = drop == BN_DROP_KEEP ? a.keep[i] : 0u;
+}
+struct BnChan {
+  f32x4 m, rs, g, b;
+};
+// (all four unconditionally: gamma and beta used to be loaded inside the tanh branch, once per row, each time behind a full wait)
+__device__ __forceinline__ void bn_chan_load(const BnCommon& a, int c4, BnChan& ch) {
+  ch.m = *(const f32x4*)(a.mean + c4); ch.rs = *(const f32x4*)(a.rstd + c4);
+  ch.g = *(const f32x4*)(a.gamma + c4); ch.b = *(const f32x4*)(a.beta + c4);
+}
+__device__ __forceinline__ void bn_dy_math(const BnCommon& a, const BnChan& ch, int drop, int64_t i, unsigned thr, float scale, bool live,
+                                           const BnRowIn& in, float xh[4], float dy[4]) {
+  const f32x4 m = ch.m, rs = ch.rs;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) xh[e] = (v[e] - m[e]) * rs[e];
+  for (int e = 0; e < 4; ++e) dy[e] = in.dy[e];
+  // the forward's keep byte, or the same bits drawn again (they need no data: behind the requests above, before their first use)
+  if (drop == BN_DROP_KEEP) drop4(dy, in.keep, scale);
+  else if (drop == BN_DROP_RNG) drop4(dy, bn_keep4(a.rng, a.site, (unsigned)i, thr), scale);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) xh[e] = (in.v[e] - m[e]) * rs[e];
   if (a.use_tanh) {
-    const f32x4 g = *(const f32x4*)(a.gamma + c4), b = *(const f32x4*)(a.beta + c4);
+    const f32x4 g = ch.g, b = ch.b;
 #pragma unroll
     for (int e = 0; e < 4; ++e) { const float t = tanh_fast(xh[e] * g[e] + b[e]); dy[e] *= 1.f - t * t; }
   }
-  if (!bn_live(a.frame_limit, a.seg_len, r)) {       // no such frame in the reference's batch: no gradient, no statistics
+  if (!live) {       // no such frame in the reference's batch: no gradient, no statistics
 #pragma unroll
     for (int e = 0; e < 4; ++e) { xh[e] = 0.f; dy[e] = 0.f; }
   }
+}
+__device__ __forceinline__ void bn_dy_row(const BnCommon& a, const void* dout, int dout_f32, int r, int c4, int64_t i, unsigned thr,
+                                          float scale, bool live, float xh[4], float dy[4]) {
+  BnRowIn in;
+  const int drop = bn_drop_mode(a);
+  BnChan ch;
+  bn_dy_load(a, a.x_f32, dout, dout_f32, drop, r, c4, i, in);
+  bn_chan_load(a, c4, ch);
+  bn_dy_math(a, ch, drop, i, thr, scale, live, in, xh, dy);
+}
+__device__ __forceinline__ void bn_dy(const BnCommon& a, const void* dout, int dout_f32, int r, int c4, int64_t i, unsigned thr,
+                                      float scale, float xh[4], float dy[4]) {
+  bn_dy_row(a, dout, dout_f32, r, c4, i, thr, scale, bn_live(a.frame_limit, a.seg_len, r), xh, dy);
 }
 
 // ---- backward pass 1: Σ dy and Σ dy·xhat per column -> partials[blk][2C]
@@ -314,43 +366,72 @@ __device__ __forceinline__ void bn_slab_store(const BnSlab& g, int C, const floa
   }
 }
 
-// tot[v], v < 2*slab: the column sums of the partial rows for this workgroup's slab (sum | second sum), double, fixed order.
-// A thread owns four columns and every (256 / (slab/2))-th partial row: with <= 64 partial rows that is at most eight 16-byte loads,
-// all in flight at once (the partial rows come from another XCD's kernel: each dependent batch of loads costs ~2 us here).
-constexpr int BN_TOT = 256 + 1024;
-__device__ __forceinline__ void bn_slab_totals(const float* __restrict__ partials, int nblk, int C, int c0, int slab, double* tot /* [BN_TOT] */) {
-  const int nq = slab >> 1, groups = 256 / nq;          // column quads of (sum | second sum); row groups
-  const int t = threadIdx.x;
-  if (t < groups * nq) {
-    const int q = t % nq, g0 = t / nq;
-    const int v0 = q * 4;
-    const int col = v0 < slab ? c0 + v0 : C + c0 + (v0 - slab);
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    // sixteen loads in flight: the 112 partial rows the PostNet's convs emit (16 utterances x 7 tiles) are one batch, not two
-    for (int b = g0; b < nblk; b += 16 * groups) {
-      f32x4 f[16];
+// The column sums of the partial rows for a workgroup's slab (sum | second sum), double, in a fixed order: thread (q, g) owns the four
+// columns of quad q and the partial rows g, g + G, g + 2G, ... (G = 256 / (slab/2) row groups), adds them in ascending order, and the G
+// group sums of a column are added in ascending g (bn_slab_total).  Every workgroup of a slab computes bit-identical statistics.
+//   bn_totals_request  the first sixteen loads of the thread, all in flight at once (the 112 partial rows the PostNet's convs emit are
+//                      one batch; they come from another XCD's kernel, each dependent batch of loads costs ~2 us here).  Called FIRST in
+//                      a kernel, in front of its row loads: loads return in order, so the sums below wait for the partial rows only
+//                      and run while the (cold, fifteen times larger) rows are still arriving.
+//   bn_totals_sum      adds them (and any further batches, of eight: more than 16 G partial rows), group sums -> gs
+//   bn_slab_total      after a barrier: the total of one column
+// gs is laid out [e][g][q] (element e of quad q, group g): thread t writes doubles e * 256 + t and a reader's lanes walk q — both
+// consecutive, where the former [t][e] layout put a wave's 8-byte accesses 32 bytes apart.
+constexpr int BN_GS = 1024;
+template <int NB>
+struct BnTotals {
+  f32x4 f[NB];      // NB: loads of the first batch (16; 12 where a kernel's own rows leave no room: 12 G >= the 64 rows bn_chunks allows)
+  int q, g0, col, nq, groups;
+  bool on;
+};
+template <int N, int NB>
+__device__ __forceinline__ void bn_totals_batch(BnTotals<NB>& w, const float* __restrict__ partials, int nblk, int C, int b) {
 #pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const int bb = b + u * groups;
-        f[u] = *(const f32x4*)(partials + (int64_t)min(bb, nblk - 1) * 2 * C + col);
-        if (bb >= nblk) f[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int u = 0; u < 16; ++u)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) a[e] += f[u][e];
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) tot[256 + t * 4 + e] = a[e];
+  for (int u = 0; u < N; ++u) {
+    const int bb = b + u * w.groups;
+    w.f[u] = *(const f32x4*)(partials + ((unsigned)min(bb, nblk - 1) * (unsigned)(2 * C) + (unsigned)w.col));     // (32-bit: one register per address)
   }
-  __syncthreads();
-  if (t < 2 * slab) {
-    double sum = 0.0;
-    for (int k = 0; k < groups; ++k) sum += tot[256 + (k * nq + (t >> 2)) * 4 + (t & 3)];
-    tot[t] = sum;
-  }
-  __syncthreads();
 }
+template <int N, int NB>
+__device__ __forceinline__ void bn_totals_add(const BnTotals<NB>& w, int nblk, int b, double a[4]) {
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    const bool in = b + u * w.groups < nblk;            // past the table: + 0, as ever (the clamped load is dropped)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a[e] += in ? w.f[u][e] : 0.f;
+  }
+}
+template <int NB>
+__device__ __forceinline__ void bn_totals_request(BnTotals<NB>& w, const float* __restrict__ partials, int nblk, int C, int c0, int slab) {
+  w.nq = slab >> 1; w.groups = 256 / w.nq;              // column quads of (sum | second sum); row groups
+  const int t = threadIdx.x;
+  w.on = t < w.groups * w.nq;
+  w.q = t % w.nq; w.g0 = min(t / w.nq, w.groups - 1);   // (a thread past the last group loads the last group's rows and adds nothing)
+  const int v0 = w.q * 4;
+  w.col = v0 < slab ? c0 + v0 : C + c0 + (v0 - slab);
+  bn_totals_batch<NB>(w, partials, nblk, C, w.g0);
+}
+template <int NB>
+__device__ __forceinline__ void bn_totals_sum(BnTotals<NB>& w, const float* __restrict__ partials, int nblk, int C, double* gs /* [BN_GS] */) {
+  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  bn_totals_add<NB>(w, nblk, w.g0, a);
+  // (further batches, eight loads each)
+  for (int b = w.g0 + NB * w.groups; b < nblk; b += 8 * w.groups) {
+    bn_totals_batch<8>(w, partials, nblk, C, b);
+    bn_totals_add<8>(w, nblk, b, a);
+  }
+  if (w.on) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) gs[e * w.groups * w.nq + threadIdx.x] = a[e];
+  }
+}
+__device__ __forceinline__ double bn_slab_total(const double* gs, int groups, int nq, int quad, int e) {
+  double sum = 0.0;
+  for (int k = 0; k < groups; ++k) sum += gs[(e * groups + k) * nq + quad];
+  return sum;
+}
+// the frame limit, read once per kernel (the rows' liveness and the row count both follow from it)
+__device__ __forceinline__ int bn_limit(const int* frame_limit) { return frame_limit ? frame_limit[0] : 0x7fffffff; }
 
 __global__ __launch_bounds__(256) void bn_stats2_kernel(const void* __restrict__ x, int x_f32, int rows, int C, float* __restrict__ partials,
                                                         const int* __restrict__ frame_limit, int seg_len) {
@@ -386,39 +467,76 @@ struct BnTrain {
   long long* nbt;
 };
 
+// y = tanh?(gamma * xhat + beta) for one element (the arithmetic of bn_apply_kernel)
+__device__ __forceinline__ float bn_norm(float v, float m, float r, float g, float b, int use_tanh) {
+  v = (v - m) * r * g + b;
+  if (use_tanh) v = tanh_fast(v);
+  return v;
+}
+// The keep nibbles of four neighbouring channel quads of one row as ONE 32-bit store from the first of their four lanes (byte j = the
+// nibble of lane j of the DPP quad): the layout is the byte-per-quad one, [rows][C/4].
+__device__ __forceinline__ unsigned bn_quad_word(unsigned nib) {
+  const int v = (int)nib;
+  const unsigned b0 = (unsigned)__builtin_amdgcn_update_dpp(0, v, 0x00, 0xf, 0xf, true), b1 = (unsigned)__builtin_amdgcn_update_dpp(0, v, 0x55, 0xf, 0xf, true);
+  const unsigned b2 = (unsigned)__builtin_amdgcn_update_dpp(0, v, 0xaa, 0xf, 0xf, true), b3 = (unsigned)__builtin_amdgcn_update_dpp(0, v, 0xff, 0xf, 0xf, true);
+  return b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+}
+
 // mean / rstd of the slab from the partial rows (the row-chunk-0 workgroups also publish them and update the running statistics),
-// then y = tanh?(gamma * xhat + beta) -> dropout -> (+ residual) -> out for the workgroup's rows
+// then y = tanh?(gamma * xhat + beta) -> dropout -> (+ residual) -> out for the workgroup's rows.
+// One batch of requests: the frame limit is read once, the partial rows are requested first, then the workgroup's (at most four) rows,
+// gamma and beta, all unconditionally at clamped addresses (what a thread without a row, or a row past the frame limit, loads is
+// dropped later).  The keep bits need no data: they are drawn behind the requests, under the wait for them.
 // (Held to 128 registers: the training shape's 848 workgroups then fit the chip's 1,024 slots in ONE round — at the 130-136 the compiler took
 // unbounded, 768 slots left 80 workgroups for a second round of the same length.  RESID: the residual rows' 16 registers only where there
 // is a residual, the PostNet's last layer.)
-template <bool RESID>
+template <bool RESID, bool X32>
 __global__ __launch_bounds__(256, RESID ? 3 : 4) void bn_apply2_kernel(const BnCommon a, const BnTrain t, const float* __restrict__ resid,
                                                         bf16_t* __restrict__ out16, float* __restrict__ out32) {
-  __shared__ double tot[BN_TOT];
+  __shared__ double gs[BN_GS];
   __shared__ float ms[128], rs[128];
   const BnSlab g(a.C, a.rows);
   const int cl = g.cq * 4, c4 = g.c0 + cl, tprC = a.C >> 2;
   const bool act = g.r_in < g.rpi;
-  // the workgroup's (at most four) rows are fetched before the partial rows are summed: one memory latency, not two
+  BN_STAMP(BN_STAMPS_OF(a), 0);
+  const int lim = bn_limit(a.frame_limit);
+  uint64_t seed = 0, step = 0;
+  if (a.p > 0.f) { seed = a.rng[0]; step = a.rng[1]; }
+  BnTotals<16> w;
+  bn_totals_request(w, t.partials, t.nblk, a.C, g.c0, g.slab);
   float v[4][4], rr[RESID ? 4 : 1][4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int rc = max(min(g.rb + g.r_in + u * g.rpi, g.re - 1), 0);
+    ldx4(a.x, X32, (int64_t)rc * a.C + c4, v[u]);
+    if constexpr (RESID) { const f32x4 q = *(const f32x4*)(resid + (int64_t)rc * a.C + c4); rr[u][0] = q[0]; rr[u][1] = q[1]; rr[u][2] = q[2]; rr[u][3] = q[3]; }
+  }
+  BN_STAMP(BN_STAMPS_OF(a), 1);
+  __builtin_amdgcn_sched_barrier(0);      // every request above is out before the draws and the first wait below
+  const unsigned thr = keep_threshold(a.p);
+  const float scale = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
+  unsigned nib[4];
   bool live[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
-    const int r = g.rb + g.r_in + u * g.rpi, rc = max(min(r, g.re - 1), 0);
-    live[u] = act && r < g.re && bn_live(a.frame_limit, a.seg_len, r);
-    if (act) {
-      ldx4(a.x, a.x_f32, (int64_t)rc * a.C + c4, v[u]);
-      if constexpr (RESID) { const f32x4 q = *(const f32x4*)(resid + (int64_t)rc * a.C + c4); rr[u][0] = q[0]; rr[u][1] = q[1]; rr[u][2] = q[2]; rr[u][3] = q[3]; }
-    }
+    const int r = g.rb + g.r_in + u * g.rpi;
+    live[u] = !a.frame_limit || (r % a.seg_len) < lim;
+    nib[u] = 0xfu;
+    if (a.p > 0.f) nib[u] = keep4(seed, step, a.site, (unsigned)((int64_t)r * tprC + (c4 >> 2)), thr);
+    if (!live[u]) nib[u] = 0u;
+    __builtin_amdgcn_sched_barrier(0);    // one draw at a time: four interleaved took forty registers this kernel does not have
   }
-  f32x4 gm = f32x4{0.f, 0.f, 0.f, 0.f}, bt = gm;
-  if (act) { gm = *(const f32x4*)(a.gamma + c4); bt = *(const f32x4*)(a.beta + c4); }
-  bn_slab_totals(t.partials, t.nblk, a.C, g.c0, g.slab, tot);
+  bn_totals_sum(w, t.partials, t.nblk, a.C, gs);
+  BN_STAMP_WAIT(BN_STAMPS_OF(a), 2);
+  // (what is per channel is requested only now, when the partial rows' sixty-four registers are free: this kernel is held to 128)
+  const f32x4 gm = *(const f32x4*)(a.gamma + c4), bt = *(const f32x4*)(a.beta + c4);
+  __syncthreads();
   if ((int)threadIdx.x < g.slab) {
-    const int c = threadIdx.x;
-    const int n = bn_rows(a.frame_limit, a.seg_len, a.rows);
-    const double m = tot[c] / n;
-    double var = tot[g.slab + c] / n - m * m;
+    // thread j: channel c = 4 (j % tpr) + j / tpr of the slab, so that a wave's lanes read consecutive doubles of gs
+    const int e = threadIdx.x / g.tpr, qd = threadIdx.x % g.tpr, c = qd * 4 + e;
+    const int n = a.frame_limit ? (a.rows / a.seg_len) * lim : a.rows;
+    const double m = bn_slab_total(gs, w.groups, w.nq, qd, e) / n;
+    double var = bn_slab_total(gs, w.groups, w.nq, g.tpr + qd, e) / n - m * m;
     if (var < 0.0) var = 0.0;
     ms[c] = (float)m;
     rs[c] = (float)(1.0 / sqrt(var + (double)t.eps));
@@ -432,57 +550,67 @@ __global__ __launch_bounds__(256, RESID ? 3 : 4) void bn_apply2_kernel(const BnC
       if (blockIdx.x == 0 && c == 0 && t.nbt) t.nbt[0] += 1;
     }
   }
+  BN_STAMP(BN_STAMPS_OF(a), 3);
   __syncthreads();
-  if (!act) return;
-  // (the keep bits are drawn here, where they are applied: drawn under the wait for the partial rows — sixteen 16-byte loads in flight
-  // in a kernel held to 128 registers — the kernel traced 0.3-1.1 us SLOWER)
-  const unsigned thr = keep_threshold(a.p);
-  const float scale = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
+  BN_STAMP(BN_STAMPS_OF(a), 4);
+  float m4[4], r4[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { m4[e] = ms[cl + e]; r4[e] = rs[cl + e]; }
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
-    const int r = g.rb + g.r_in + u * g.rpi;
-    if (r >= g.re) break;
-    const int64_t i = (int64_t)r * tprC + (c4 >> 2);
-    if (!live[u]) {     // a frame past the batch's own length: a zero row (the next conv's padding)
-      if (out16) *(uint2*)(out16 + (int64_t)r * a.C + c4) = make_uint2(0u, 0u);
-      if (out32) *(f32x4*)(out32 + (int64_t)r * a.C + c4) = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (a.keep) a.keep[i] = 0;
-      continue;
-    }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      v[u][e] = (v[u][e] - ms[cl + e]) * rs[cl + e] * gm[e] + bt[e];
-      if (a.use_tanh) v[u][e] = tanh_fast(v[u][e]);
-    }
-    if (a.p > 0.f) {
-      const unsigned nib = bn_keep4(a.rng, a.site, (unsigned)i, thr);
-      drop4(v[u], nib, scale);
-      if (a.keep) a.keep[i] = (uint8_t)nib;
-    }
+    for (int e = 0; e < 4; ++e) v[u][e] = bn_norm(v[u][e], m4[e], r4[e], gm[e], bt[e], a.use_tanh);
+    if (a.p > 0.f) drop4(v[u], nib[u], scale);
     if constexpr (RESID) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[u][e] += rr[u][e];
     }
+    if (!live[u]) v[u][0] = v[u][1] = v[u][2] = v[u][3] = 0.f;     // a frame past the batch's own length: a zero row (the next conv's padding)
+  }
+  BN_STAMP(BN_STAMPS_OF(a), 5);
+  const bool words = (g.tpr & 3) == 0 && ((uintptr_t)a.keep & 3) == 0;      // a DPP quad is four quads of ONE row, and its keep bytes are one aligned word
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int r = g.rb + g.r_in + u * g.rpi;
+    if (!act || r >= g.re) break;
+    const int64_t i = (int64_t)r * tprC + (c4 >> 2);
     if (out16) *(uint2*)(out16 + (int64_t)r * a.C + c4) = make_uint2(pack_bf2(v[u][0], v[u][1]), pack_bf2(v[u][2], v[u][3]));
     if (out32) *(f32x4*)(out32 + (int64_t)r * a.C + c4) = f32x4{v[u][0], v[u][1], v[u][2], v[u][3]};
+    if (a.keep && (a.p > 0.f || !live[u])) {
+      if (words) {
+        const unsigned kw = bn_quad_word(nib[u]);
+        if ((threadIdx.x & 3) == 0) *(unsigned*)(a.keep + i) = kw;
+      } else {
+        a.keep[i] = (uint8_t)nib[u];
+      }
+    }
   }
+  BN_STAMP(BN_STAMPS_OF(a), 6);
+  BN_STAMP_WAIT(BN_STAMPS_OF(a), 7);
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_stats2_kernel(const BnCommon a, const void* __restrict__ dout, int dout_f32,
-                                                            float* __restrict__ partials) {
+template <bool X32, bool D32, int DROP>
+__global__ __launch_bounds__(256) void bn_bwd_stats2_kernel(const BnCommon a, const void* __restrict__ dout, float* __restrict__ partials) {
   extern __shared__ float red[];
   const BnSlab g(a.C, a.rows);
   const int c4 = g.c0 + g.cq * 4, tprC = a.C >> 2;
   const unsigned thr = keep_threshold(a.p);
   const float scale = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
   float s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
+  BN_STAMP(BN_STAMPS_OF(a), 0);
+  const int lim = bn_limit(a.frame_limit);      // read once, not per row behind the row's loads
+  BnChan ch;
+  bn_chan_load(a, c4, ch);
   if (g.r_in < g.rpi)
     for (int r0 = g.rb + g.r_in; r0 < g.re; r0 += 8 * g.rpi) {
       float xh[8][4], dy[8][4];
 #pragma unroll
       for (int u = 0; u < 8; ++u) {            // eight independent rows in flight (a chunk of a full-size batch is seven)
         const int r = r0 + u * g.rpi, rc = min(r, g.re - 1);
-        bn_dy(a, dout, dout_f32, rc, c4, (int64_t)rc * tprC + (c4 >> 2), thr, scale, xh[u], dy[u]);
+        BnRowIn in;
+        const int64_t i = (int64_t)rc * tprC + (c4 >> 2);
+        bn_dy_load(a, X32, dout, D32, DROP, rc, c4, i, in);
+        bn_dy_math(a, ch, DROP, i, thr, scale, !a.frame_limit || (rc % a.seg_len) < lim, in, xh[u], dy[u]);
         if (r >= g.re) { xh[u][0] = xh[u][1] = xh[u][2] = xh[u][3] = 0.f; dy[u][0] = dy[u][1] = dy[u][2] = dy[u][3] = 0.f; }
       }
 #pragma unroll
@@ -490,53 +618,84 @@ __global__ __launch_bounds__(256) void bn_bwd_stats2_kernel(const BnCommon a, co
 #pragma unroll
         for (int e = 0; e < 4; ++e) { s[e] += dy[u][e]; q[e] += dy[u][e] * xh[u][e]; }
     }
+  BN_STAMP(BN_STAMPS_OF(a), 5);
   bn_slab_store(g, a.C, s, q, red, partials);
+  BN_STAMP(BN_STAMPS_OF(a), 6);
+  BN_STAMP_WAIT(BN_STAMPS_OF(a), 7);
 }
 
 // dx = gamma * rstd * (dy − mean(dy) − xhat * mean(dy·xhat)) with the two sums taken from the partial rows; the row-chunk-0
-// workgroups add them to dbeta / dgamma
-__global__ __launch_bounds__(256, 4) void bn_bwd_apply2_kernel(const BnCommon a, const void* __restrict__ dout, int dout_f32,
+// workgroups add them to dbeta / dgamma.  The requests as in bn_apply2_kernel: partial rows first, then everything dy and xhat of the
+// workgroup's (at most four) rows need, unconditionally (they used to go out only after dy had been computed: a second memory latency).
+template <bool X32, bool D32, int DROP>
+__global__ __launch_bounds__(256, 4) void bn_bwd_apply2_kernel(const BnCommon a, const void* __restrict__ dout,
                                                             const float* __restrict__ partials, int nblk, bf16_t* __restrict__ dx,
                                                             float* __restrict__ dgamma, float* __restrict__ dbeta, int accumulate) {
-  __shared__ double tot[BN_TOT];
+  __shared__ double gs[BN_GS];
   __shared__ float s1s[128], s2s[128];
   const BnSlab g(a.C, a.rows);
   const int cl = g.cq * 4, c4 = g.c0 + cl, tprC = a.C >> 2;
   const bool act = g.r_in < g.rpi;
   const unsigned thr = keep_threshold(a.p);
   const float scale = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
-  // dy and xhat of the workgroup's (at most four) rows need nothing from the partial rows: computed first, so that their loads
-  // are in flight while the partial rows are summed
-  float xh[4][4], dy[4][4];
+  BN_STAMP(BN_STAMPS_OF(a), 0);
+  const int lim = bn_limit(a.frame_limit);
+  BnTotals<(X32 && D32) ? 12 : 16> w;      // (fp32 x and fp32 dout: 32 registers of rows in flight beside the partial rows)
+  bn_totals_request(w, partials, nblk, a.C, g.c0, g.slab);
+  BnRowIn in[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int rc = max(min(g.rb + g.r_in + u * g.rpi, g.re - 1), 0);
-    if (act) bn_dy(a, dout, dout_f32, rc, c4, (int64_t)rc * tprC + (c4 >> 2), thr, scale, xh[u], dy[u]);
+    bn_dy_load(a, X32, dout, D32, DROP, rc, c4, (int64_t)rc * tprC + (c4 >> 2), in[u]);
   }
-  bn_slab_totals(partials, nblk, a.C, g.c0, g.slab, tot);
+  BN_STAMP(BN_STAMPS_OF(a), 1);
+  __builtin_amdgcn_sched_barrier(0);      // every request above is out before the first wait below
+  bn_totals_sum(w, partials, nblk, a.C, gs);
+  BN_STAMP_WAIT(BN_STAMPS_OF(a), 2);
+  // (what is per channel is requested only now, when the partial rows' sixty-four registers are free: this kernel is held to 128)
+  BnChan ch;
+  bn_chan_load(a, c4, ch);
+  const f32x4 gm = ch.g, rsd = ch.rs;
+  float xh[4][4], dy[4][4];
+  bool live[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int r = g.rb + g.r_in + u * g.rpi, rc = max(min(r, g.re - 1), 0);
+    live[u] = !a.frame_limit || (r % a.seg_len) < lim;
+    bn_dy_math(a, ch, DROP, (int64_t)rc * tprC + (c4 >> 2), thr, scale, live[u], in[u], xh[u], dy[u]);
+  }
+  __syncthreads();
   if ((int)threadIdx.x < g.slab) {
-    const int c = threadIdx.x;
-    s1s[c] = (float)tot[c];
-    s2s[c] = (float)tot[g.slab + c];
+    const int e = threadIdx.x / g.tpr, qd = threadIdx.x % g.tpr, c = qd * 4 + e;       // as in bn_apply2_kernel
+    s1s[c] = (float)bn_slab_total(gs, w.groups, w.nq, qd, e);
+    s2s[c] = (float)bn_slab_total(gs, w.groups, w.nq, g.tpr + qd, e);
     if (blockIdx.y == 0 && dgamma) {
       dbeta[g.c0 + c] = accumulate ? dbeta[g.c0 + c] + s1s[c] : s1s[c];
       dgamma[g.c0 + c] = accumulate ? dgamma[g.c0 + c] + s2s[c] : s2s[c];
     }
   }
+  BN_STAMP(BN_STAMPS_OF(a), 3);
   __syncthreads();
-  if (!act) return;
-  const float inv_n = 1.f / bn_rows(a.frame_limit, a.seg_len, a.rows);
-  const f32x4 gm = *(const f32x4*)(a.gamma + c4), rsd = *(const f32x4*)(a.rstd + c4);
+  BN_STAMP(BN_STAMPS_OF(a), 4);
+  const float inv_n = 1.f / (a.frame_limit ? (a.rows / a.seg_len) * lim : a.rows);
+  unsigned o2[4][2];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
-    const int r = g.rb + g.r_in + u * g.rpi;
-    if (r >= g.re) break;
     float o[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = gm[e] * rsd[e] * (dy[u][e] - s1s[cl + e] * inv_n - xh[u][e] * s2s[cl + e] * inv_n);
-    if (!bn_live(a.frame_limit, a.seg_len, r)) o[0] = o[1] = o[2] = o[3] = 0.f;
-    *(uint2*)(dx + (int64_t)r * a.C + c4) = make_uint2(pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]));
+    if (!live[u]) o[0] = o[1] = o[2] = o[3] = 0.f;
+    o2[u][0] = pack_bf2(o[0], o[1]); o2[u][1] = pack_bf2(o[2], o[3]);
   }
+  BN_STAMP(BN_STAMPS_OF(a), 5);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int r = g.rb + g.r_in + u * g.rpi;
+    if (!act || r >= g.re) break;
+    *(uint2*)(dx + (int64_t)r * a.C + c4) = make_uint2(o2[u][0], o2[u][1]);
+  }
+  BN_STAMP(BN_STAMPS_OF(a), 6);
+  BN_STAMP_WAIT(BN_STAMPS_OF(a), 7);
 }
 
 inline int bn_chunks(int rows) { int n = (rows + 15) / 16; return n > BN_MAX_CHUNKS ? BN_MAX_CHUNKS : (n < 1 ? 1 : n); }
@@ -656,6 +815,31 @@ extern "C" int ttsk_bn_bwd_apply(const void* dout, int dout_is_f32, const void* 
 }
 
 // ---- the two-launch training path
+#ifdef TTSK_STAMPS
+static unsigned long long* g_bn_stamps = nullptr;
+// diagnostic build only (`make stamps`, tools/debug/bn_stamps.py; not declared in ttsk.h, not in the product library): device buffer of
+// 8 x uint64 per workgroup for the slab launches that follow; null switches the stamps off again
+extern "C" int ttsk_bn_set_stamps(void* dev_buffer) {
+  g_bn_stamps = (unsigned long long*)dev_buffer;
+  return TTSK_OK;
+}
+#define BN_SET_STAMPS(a) (a).stamps = g_bn_stamps
+#else
+#define BN_SET_STAMPS(a) do {} while (0)
+#endif
+// the backward slab kernels' instances: (x fp32?, dout fp32?, where the dropout mask comes from); BN_LAUNCH is defined at the use
+static int bn_drop_of(float p, const void* keep) { return p > 0.f ? (keep ? BN_DROP_KEEP : BN_DROP_RNG) : BN_DROP_NONE; }
+#define BN_BWD_DISPATCH3(X32, D32, drop)                                                       \
+  do {                                                                                         \
+    if ((drop) == BN_DROP_KEEP) BN_LAUNCH(X32, D32, BN_DROP_KEEP);                             \
+    else if ((drop) == BN_DROP_RNG) BN_LAUNCH(X32, D32, BN_DROP_RNG);                          \
+    else BN_LAUNCH(X32, D32, BN_DROP_NONE);                                                    \
+  } while (0)
+#define BN_BWD_DISPATCH(x32, d32, drop)                                                        \
+  do {                                                                                         \
+    if (x32) { if (d32) BN_BWD_DISPATCH3(true, true, drop); else BN_BWD_DISPATCH3(true, false, drop); } \
+    else { if (d32) BN_BWD_DISPATCH3(false, true, drop); else BN_BWD_DISPATCH3(false, false, drop); }   \
+  } while (0)
 static int bn2_check(int rows, int C) {
   if (int rc = bn_check(rows, C)) return rc;
   TTSK_REQUIRE(C % 64 == 0 || C <= 128, "batchnorm (slab path): C must be a multiple of 64 or <= 128 (got %d)", C);
@@ -687,10 +871,13 @@ extern "C" int ttsk_bn_train_apply(const void* x, int x_is_f32, const float* par
   TTSK_REQUIRE(p == 0.f || rng, "bn_train_apply: dropout needs rng");
   if (int rc = bn2_check(rows, C)) return rc;
   BnCommon a{x, nullptr, nullptr, gamma, beta, rng, rows, C, use_tanh, p, site, x_is_f32, frame_limit, seg_len > 0 ? seg_len : 1, keep_out};
+  BN_SET_STAMPS(a);
   BnTrain t{partials, nblk, eps, momentum, mean, rstd, running_mean, running_var, (long long*)num_batches_tracked};
   const dim3 grid(C / bn_slab(C), bn_apply_chunks(rows, C));
-  if (resid_f32) hipLaunchKernelGGL(bn_apply2_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a, t, resid_f32, (bf16_t*)out_bf16, out_f32);
-  else hipLaunchKernelGGL(bn_apply2_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a, t, resid_f32, (bf16_t*)out_bf16, out_f32);
+#define BN_APPLY2(RESID, X32) hipLaunchKernelGGL((bn_apply2_kernel<RESID, X32>), grid, dim3(256), 0, (hipStream_t)stream, a, t, resid_f32, (bf16_t*)out_bf16, out_f32)
+  if (resid_f32) { if (x_is_f32) BN_APPLY2(true, true); else BN_APPLY2(true, false); }
+  else { if (x_is_f32) BN_APPLY2(false, true); else BN_APPLY2(false, false); }
+#undef BN_APPLY2
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
 }
@@ -704,9 +891,13 @@ extern "C" int ttsk_bn_bwd_stats_slab(const void* dout, int dout_is_f32, const v
   TTSK_REQUIRE(p == 0.f || rng || keep, "bn_bwd_stats_slab: dropout needs rng or the forward's keep bits");
   if (int rc = bn2_check(rows, C)) return rc;
   BnCommon a{x, mean, rstd, gamma, beta, rng, rows, C, use_tanh, p, site, x_is_f32, frame_limit, seg_len > 0 ? seg_len : 1, (uint8_t*)keep};
+  BN_SET_STAMPS(a);
   const int slab = bn_slab(C), rpi = 256 / (slab >> 2);
-  hipLaunchKernelGGL(bn_bwd_stats2_kernel, dim3(C / slab, bn_chunks(rows)), dim3(256), 2 * rpi * slab * sizeof(float), (hipStream_t)stream,
-                     a, dout, dout_is_f32, partials);
+#define BN_LAUNCH(X32, D32, DROP)                                                                                                            \
+  hipLaunchKernelGGL((bn_bwd_stats2_kernel<X32, D32, DROP>), dim3(C / slab, bn_chunks(rows)), dim3(256), 2 * rpi * slab * sizeof(float), \
+                     (hipStream_t)stream, a, dout, partials)
+  BN_BWD_DISPATCH(x_is_f32, dout_is_f32, bn_drop_of(p, keep));
+#undef BN_LAUNCH
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
 }
@@ -721,8 +912,12 @@ extern "C" int ttsk_bn_bwd_apply_slab(const void* dout, int dout_is_f32, const v
   TTSK_REQUIRE(p == 0.f || rng || keep, "bn_bwd_apply_slab: dropout needs rng or the forward's keep bits");
   if (int rc = bn2_check(rows, C)) return rc;
   BnCommon a{x, mean, rstd, gamma, beta, rng, rows, C, use_tanh, p, site, x_is_f32, frame_limit, seg_len > 0 ? seg_len : 1, (uint8_t*)keep};
-  hipLaunchKernelGGL(bn_bwd_apply2_kernel, dim3(C / bn_slab(C), bn_apply_chunks(rows, C)), dim3(256), 0, (hipStream_t)stream, a, dout,
-                     dout_is_f32, partials, nblk, (bf16_t*)dx_bf16, dgamma, dbeta, accumulate);
+  BN_SET_STAMPS(a);
+#define BN_LAUNCH(X32, D32, DROP)                                                                                                      \
+  hipLaunchKernelGGL((bn_bwd_apply2_kernel<X32, D32, DROP>), dim3(C / bn_slab(C), bn_apply_chunks(rows, C)), dim3(256), 0, (hipStream_t)stream, \
+                     a, dout, partials, nblk, (bf16_t*)dx_bf16, dgamma, dbeta, accumulate)
+  BN_BWD_DISPATCH(x_is_f32, dout_is_f32, bn_drop_of(p, keep));
+#undef BN_LAUNCH
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
 }
