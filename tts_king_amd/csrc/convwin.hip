@@ -7,9 +7,9 @@
 // 256x128x64 step moves 48 KiB per 4.2 MFLOP and both tile configurations are bound by the CU's operand fetch rate,
 // 25-28 % MFMA utilisation).  Here a workgroup loads its frames x channels ONCE and per tap only the weights (fragment-major
 // pack, coalesced).  D[cout][frame] orientation, fragment layouts and padding are those of resblock.hip.
-#include <type_traits>
+// The pair kernels are written on the shared stages of pairparts.h: here stand their geometry and their tap schedules.
 #include "common.h"
-#include "rowlens.h"
+#include "pairparts.h"
 #include "tapring.h"
 #include <cstdlib>
 
@@ -204,7 +204,7 @@ struct PairArgs {
 
 template <bool F16, typename A = PairArgs>
 __global__ __launch_bounds__(C2_NT, 2) void conv_pair_kernel(const A a) {
-  constexpr int C = CW_C, TT = CP_TT, RS = CW_RS, NC = CW_NC, KS = CW_KS, NT = C2_NT, CH8 = C / 8, CT = C2_CT;
+  constexpr int C = CW_C, TT = CP_TT, RS = CW_RS, NC = CW_NC, KS = CW_KS, NT = C2_NT, CT = C2_CT;
   constexpr int NF1 = CP_TROWS / 16, NF2 = TT / 16;
   __shared__ __attribute__((aligned(16))) unsigned char smem[CP_SMEM];
   unsigned char* XW = smem;
@@ -221,18 +221,13 @@ __global__ __launch_bounds__(C2_NT, 2) void conv_pair_kernel(const A a) {
   const int HK = (K - 1) / 2;
   const bf16_t* __restrict__ xb = a.x + (int64_t)bi * slen * C;
 
-  // The wave's 32 output channels, rows of the A operand PERMUTED (round 6, as csrc/pairws.hip): row l15 of tile cc is channel
-  // 32 * wave + 8 * (l15 >> 2) + 4 * cc + (l15 & 3), so that a lane's 4 + 4 accumulator rows of the two tiles are 8 CONSECUTIVE channels of
-  // one frame — one 16-byte LDS / global store per frame tile and lane instead of two 8-byte ones (whose rows collided four ways in LDS:
-  // 17 % of the kernel's LDS cycles), and the output needs no staging tile, barrier and copy-out.  Same products, same order: bit-identical.
+  // the wave's 32 output channels, rows of the A operand permuted (pairparts.h).  (woff[] is filled by a loop HERE in both kernels: filled
+  // inside a helper, conv_pair256_kernel — 3 registers under its limit — spilt 49: profiles/pair_parts_occupancy.txt)
   bf16x8 wa[KS][CT], wb[KS][CT];
   int woff[CT];
 #pragma unroll
-  for (int cc = 0; cc < CT; ++cc) {
-    const int co = 32 * wave + 8 * (l15 >> 2) + 4 * cc + (l15 & 3);
-    woff[cc] = (co >> 4) * 1024 + ((co & 15) + 16 * q) * 16;
-  }
-  const int co8 = 32 * wave + 8 * q;          // this lane's 8 output channels
+  for (int cc = 0; cc < CT; ++cc) woff[cc] = perm_woff(wave, l15, q, cc);
+  const int co8 = perm_co8(wave, q);
   auto load_w = [&](int g, bf16x8 (&w)[KS][CT]) __attribute__((always_inline)) {      // tap g of the 2K-tap sequence c1 | c2
     const unsigned char* src = (const unsigned char*)(g < K ? a.w1 : a.w2) + (int64_t)(g < K ? g : g - K) * CW_WTAP;
 #pragma unroll
@@ -242,30 +237,13 @@ __global__ __launch_bounds__(C2_NT, 2) void conv_pair_kernel(const A a) {
   };
   TTSK_STAMP(0);
 
-  {  // ---- x window: lrelu(x) rows t0 - 33 .. t0 + 129, zeros outside the utterance.  The window is sized for dilation 5 (c1 reaches 25
-     // rows beyond the 112 it computes); a smaller dilation reads HK * d rows either side only — the others are never fetched (they
-     // stay zero, nobody reads them): 122 / 142 / 162 rows for d = 1 / 3 / 5 at k = 11.
-    constexpr int NCH = (CP_XROWS * CH8 + NT - 1) / NT;     // 11
-    const int xlo = CP_XH - CP_TH - HK * d, xhi = CP_XH - CP_TH + CP_TROWS + HK * d;
-    uint4 xv[NCH];
-#pragma unroll
-    for (int it = 0; it < NCH; ++it) {
-      const int idx = it * NT + tid;
-      const int row = idx / CH8, ch = idx - row * CH8;
-      const int t = t0 - CP_XH + row;
-      xv[it] = make_uint4(0, 0, 0, 0);
-      if (idx < CP_XROWS * CH8 && t >= 0 && t < len && row >= xlo && row < xhi) xv[it] = *(const uint4*)(xb + (int64_t)t * C + ch * 8);
-    }
-    // the weight fragments are requested BEHIND the window: loads return in order, and nothing starts before the window is in LDS
-    load_w(0, wa);
-    load_w(1, wb);
-#pragma unroll
-    for (int it = 0; it < NCH; ++it) {
-      const int idx = it * NT + tid;
-      const int row = idx / CH8, ch = idx - row * CH8;
-      if (idx < CP_XROWS * CH8) *(uint4*)(XW + row * RS + ch * 16) = lrelu8_fast<F16>(xv[it], a.slope);
-    }
-  }
+  // ---- x window: lrelu(x) rows t0 - 33 .. t0 + 129.  Sized for dilation 5 (c1 reaches 25 rows beyond the 112 it computes); a smaller
+  // dilation fetches HK * d rows either side only: 122 / 142 / 162 rows for d = 1 / 3 / 5 at k = 11.
+  uint4 xv[x_window_chunks<C, CP_XROWS, NT>()];
+  x_window_request<C, CP_XROWS, NT>(xv, xb, t0 - CP_XH, len, CP_XH - CP_TH - HK * d, CP_XH - CP_TH + CP_TROWS + HK * d, tid);
+  load_w(0, wa);
+  load_w(1, wb);
+  x_window_store<F16, C, CP_XROWS, NT, RS>(XW, xv, a.slope, tid);
   f32x4 bv1[CT], bv2[CT];
 #pragma unroll
   for (int cc = 0; cc < CT; ++cc) {
@@ -280,70 +258,29 @@ __global__ __launch_bounds__(C2_NT, 2) void conv_pair_kernel(const A a) {
   // (round 6: the accumulators are not zeroed — 104 x 4 v_mov per wave and workgroup, and every VALU instruction costs a quarter of an MFMA here,
   // DESIGN.md 8.2 — the first tap's first k-step multiplies onto the constant 0 instead: same sums, bit for bit)
   f32x4 acc[CT][NF1];
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   {
     const unsigned char* inl = XW + (l15 + CP_XH - CP_TH) * RS + q * 16;      // t-window row r <-> x-window row r + 25
-    auto tap1 = [&](auto firstc, int g, const bf16x8 (&w)[KS][CT]) __attribute__((always_inline)) {
-      const unsigned char* inp = inl + (g - HK) * d * RS;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-        for (int i = 0; i < NF1; ++i) {
-          const bf16x8 Bf = *(const bf16x8*)(inp + i * 16 * RS + ks * 64);
-#pragma unroll
-          for (int cc = 0; cc < CT; ++cc) acc[cc][i] = mfma16<F16>(w[ks][cc], Bf, (decltype(firstc)::value && ks == 0) ? zero4 : acc[cc][i]);
-        }
-      }
+    auto tap1 = [&](int g, const bf16x8 (&w)[KS][CT]) __attribute__((always_inline)) {
+      tap_plain<F16, KS, CT, NF1, RS>(acc, w, inl + (g - HK) * d * RS);
     };
     // K is odd and >= 3: taps 0 .. K-2 in pairs (the first pair peeled: its first tap starts the sums), then tap K-1 on set a (c2 starts on set b)
-    tap1(std::true_type{}, 0, wa);
+    tap_plain<F16, KS, CT, NF1, RS, true>(acc, wa, inl - HK * d * RS);
     load_w(2, wa);
-    tap1(std::false_type{}, 1, wb);
+    tap1(1, wb);
     load_w(3, wb);
 #pragma unroll 1
     for (int g = 2; g + 1 < K; g += 2) {
-      tap1(std::false_type{}, g, wa);
+      tap1(g, wa);
       load_w(g + 2, wa);
-      tap1(std::false_type{}, g + 1, wb);
+      tap1(g + 1, wb);
       load_w(g + 3, wb);
     }
-    tap1(std::false_type{}, K - 1, wa);
+    tap1(K - 1, wa);
     load_w(K + 1, wa);
   }
   TTSK_STAMP(3);
-  // t = lrelu(c1 + b1) as fp16 rows of the t window; frames outside [0, len) are c2's zero padding
-  // (a tile whose t window lies inside the utterance has no zero padding to write: no compare, no select — and the conversions pack in pairs)
-  if (t0 - CP_TH >= 0 && t0 - CP_TH + CP_TROWS <= len) {
-#pragma unroll
-    for (int i = 0; i < NF1; ++i) {
-      unsigned o[4];
-#pragma unroll
-      for (int cc = 0; cc < CT; ++cc) {
-        f32x4 v = acc[cc][i] + bv1[cc];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], v[e] * a.slope);
-        o[cc * 2] = pack2<F16>(v[0], v[1]);
-        o[cc * 2 + 1] = pack2<F16>(v[2], v[3]);
-      }
-      *(uint4*)(TW + (i * 16 + l15) * RS + co8 * 2) = make_uint4(o[0], o[1], o[2], o[3]);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < NF1; ++i) {
-      const int t = t0 - CP_TH + i * 16 + l15;
-      const bool live = t >= 0 && t < len;
-      unsigned o[4];
-#pragma unroll
-      for (int cc = 0; cc < CT; ++cc) {
-        f32x4 v = acc[cc][i] + bv1[cc];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = live ? fmaxf(v[e], v[e] * a.slope) : 0.f;
-        o[cc * 2] = pack2<F16>(v[0], v[1]);
-        o[cc * 2 + 1] = pack2<F16>(v[2], v[3]);
-      }
-      *(uint4*)(TW + (i * 16 + l15) * RS + co8 * 2) = make_uint4(o[0], o[1], o[2], o[3]);
-    }
-  }
+  // t = lrelu(c1 + b1) as 16-bit rows of the t window; frames outside [0, len) are c2's zero padding
+  store_t_rows<F16, NF1, RS>(TW, acc, bv1, a.slope, t0 - CP_TH, len, l15, co8);
   __syncthreads();
 
   TTSK_STAMP(4);
@@ -362,30 +299,21 @@ __global__ __launch_bounds__(C2_NT, 2) void conv_pair_kernel(const A a) {
   f32x4 acc2[CT][NF2];
   {
     const unsigned char* inl = TW + (l15 + CP_TH) * RS + q * 16;
-    auto tap2 = [&](auto firstc, int g, const bf16x8 (&w)[KS][CT]) __attribute__((always_inline)) {
-      const unsigned char* inp = inl + (g - HK) * RS;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-        for (int i = 0; i < NF2; ++i) {
-          const bf16x8 Bf = *(const bf16x8*)(inp + i * 16 * RS + ks * 64);
-#pragma unroll
-          for (int cc = 0; cc < CT; ++cc) acc2[cc][i] = mfma16<F16>(w[ks][cc], Bf, (decltype(firstc)::value && ks == 0) ? zero4 : acc2[cc][i]);
-        }
-      }
+    auto tap2 = [&](int g, const bf16x8 (&w)[KS][CT]) __attribute__((always_inline)) {
+      tap_plain<F16, KS, CT, NF2, RS>(acc2, w, inl + (g - HK) * RS);
     };
-    tap2(std::true_type{}, 0, wb);
+    tap_plain<F16, KS, CT, NF2, RS, true>(acc2, wb, inl - HK * RS);
     load_w(K + 2, wb);
-    tap2(std::false_type{}, 1, wa);
+    tap2(1, wa);
     if (3 < K) load_w(K + 3, wa);
 #pragma unroll 1
     for (int g = 2; g + 1 < K; g += 2) {
-      tap2(std::false_type{}, g, wb);
+      tap2(g, wb);
       if (g + 2 < K) load_w(K + g + 2, wb);
-      tap2(std::false_type{}, g + 1, wa);
+      tap2(g + 1, wa);
       if (g + 3 < K) load_w(K + g + 3, wa);
     }
-    tap2(std::false_type{}, K - 1, wb);
+    tap2(K - 1, wb);
   }
 
   TTSK_STAMP(5);
@@ -394,31 +322,8 @@ __global__ __launch_bounds__(C2_NT, 2) void conv_pair_kernel(const A a) {
 #pragma unroll
   for (int i = 0; i < NF2; ++i) {
     const int t = t0 + i * 16 + l15;
-    const unsigned rw[4] = {rres[i].x, rres[i].y, rres[i].z, rres[i].w}, ow[4] = {rout[i].x, rout[i].y, rout[i].z, rout[i].w};
-    unsigned o[4];
-#pragma unroll
-    for (int cc = 0; cc < CT; ++cc) {
-      f32x4 v = acc2[cc][i] + bv2[cc];
-      {
-        float r0, r1, r2, r3;
-        unpack2<F16>(rw[cc * 2], r0, r1); unpack2<F16>(rw[cc * 2 + 1], r2, r3);
-        v += f32x4{r0, r1, r2, r3};
-      }
-      if (a.mode) {
-        {
-          float o0, o1, o2, o3;
-          unpack2<F16>(ow[cc * 2], o0, o1); unpack2<F16>(ow[cc * 2 + 1], o2, o3);
-          v += f32x4{o0, o1, o2, o3};
-        }
-        if (a.mode == 2) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { v[e] *= a.scale; v[e] = fmaxf(v[e], v[e] * a.final_slope); }
-        }
-      }
-      o[cc * 2] = pack2<F16>(v[0], v[1]);
-      o[cc * 2 + 1] = pack2<F16>(v[2], v[3]);
-    }
-    if (t < len) *(uint4*)(ob + (int64_t)t * C + co8) = make_uint4(o[0], o[1], o[2], o[3]);
+    const uint4 o = mrf_finish8<F16>(acc2[0][i] + bv2[0], acc2[1][i] + bv2[1], rres[i], rout[i], a.mode, a.scale, a.final_slope);
+    if (t < len) *(uint4*)(ob + (int64_t)t * C + co8) = o;
   }
   TTSK_STAMP(6);
   TTSK_STAMP(7);
@@ -438,7 +343,7 @@ constexpr int C256_SMEM = (CP_XROWS + CP_TROWS) * C256_RS;           // 149,056 
 
 template <bool F16, typename A = PairArgs>
 __global__ __launch_bounds__(C256_NT, 1) void conv_pair256_kernel(const A a) {
-  constexpr int C = C256, TT = CP_TT, RS = C256_RS, NC = C256_NC, KH = C256_KH, NT = C256_NT, CH8 = C / 8, CT = 2;
+  constexpr int C = C256, TT = CP_TT, RS = C256_RS, NC = C256_NC, KH = C256_KH, NT = C256_NT, CT = 2;
   constexpr int NF1 = CP_TROWS / 16, NF2 = TT / 16;
   __shared__ __attribute__((aligned(16))) unsigned char smem[C256_SMEM];
   unsigned char* XW = smem;
@@ -460,11 +365,8 @@ __global__ __launch_bounds__(C256_NT, 1) void conv_pair256_kernel(const A a) {
   // (the A operand's rows permuted as in conv_pair_kernel: a lane's accumulator rows of its two tiles are 8 consecutive channels of one frame)
   int woff[CT];
 #pragma unroll
-  for (int cc = 0; cc < CT; ++cc) {
-    const int co = 32 * wave + 8 * (l15 >> 2) + 4 * cc + (l15 & 3);
-    woff[cc] = (co >> 4) * 1024 + ((co & 15) + 16 * q) * 16;
-  }
-  const int co8 = 32 * wave + 8 * q;
+  for (int cc = 0; cc < CT; ++cc) woff[cc] = perm_woff(wave, l15, q, cc);
+  const int co8 = perm_co8(wave, q);
   auto load_w = [&](int g, bf16x8 (&w)[KH][CT]) __attribute__((always_inline)) {
     const int gl = g < K2 ? g : g - K2;
     const unsigned char* src = (const unsigned char*)(g < K2 ? a.w1 : a.w2) + (int64_t)(gl >> 1) * C256_TAP + (gl & 1) * (KH * NC * 1024);
@@ -474,30 +376,12 @@ __global__ __launch_bounds__(C256_NT, 1) void conv_pair256_kernel(const A a) {
       for (int cc = 0; cc < CT; ++cc) w[ks][cc] = *(const bf16x8*)(src + ks * NC * 1024 + woff[cc]);
   };
 
-  {  // ---- x window: lrelu(x) rows t0 - 33 .. t0 + 129, zeros outside the utterance.  The window is sized for dilation 5 (c1 reaches 25
-     // rows beyond the 112 it computes); a smaller dilation reads HK * d rows either side only — the others are never fetched (they
-     // stay zero, nobody reads them): 122 / 142 / 162 rows for d = 1 / 3 / 5 at k = 11.
-    constexpr int NCH = (CP_XROWS * CH8 + NT - 1) / NT;     // 11
-    const int xlo = CP_XH - CP_TH - HK * d, xhi = CP_XH - CP_TH + CP_TROWS + HK * d;
-    uint4 xv[NCH];
-#pragma unroll
-    for (int it = 0; it < NCH; ++it) {
-      const int idx = it * NT + tid;
-      const int row = idx / CH8, ch = idx - row * CH8;
-      const int t = t0 - CP_XH + row;
-      xv[it] = make_uint4(0, 0, 0, 0);
-      if (idx < CP_XROWS * CH8 && t >= 0 && t < len && row >= xlo && row < xhi) xv[it] = *(const uint4*)(xb + (int64_t)t * C + ch * 8);
-    }
-    // the weight fragments are requested BEHIND the window: loads return in order, and nothing starts before the window is in LDS
-    load_w(0, wa);
-    load_w(1, wb);
-#pragma unroll
-    for (int it = 0; it < NCH; ++it) {
-      const int idx = it * NT + tid;
-      const int row = idx / CH8, ch = idx - row * CH8;
-      if (idx < CP_XROWS * CH8) *(uint4*)(XW + row * RS + ch * 16) = lrelu8_fast<F16>(xv[it], a.slope);
-    }
-  }
+  // ---- x window: the rows of conv_pair_kernel's, twice as wide
+  uint4 xv[x_window_chunks<C, CP_XROWS, NT>()];
+  x_window_request<C, CP_XROWS, NT>(xv, xb, t0 - CP_XH, len, CP_XH - CP_TH - HK * d, CP_XH - CP_TH + CP_TROWS + HK * d, tid);
+  load_w(0, wa);
+  load_w(1, wb);
+  x_window_store<F16, C, CP_XROWS, NT, RS>(XW, xv, a.slope, tid);
   f32x4 bv1[CT], bv2[CT];
 #pragma unroll
   for (int cc = 0; cc < CT; ++cc) {
@@ -530,37 +414,7 @@ __global__ __launch_bounds__(C256_NT, 1) void conv_pair256_kernel(const A a) {
       load_w(g + 3, wb);
     }
   }
-  if (t0 - CP_TH >= 0 && t0 - CP_TH + CP_TROWS <= len) {      // (the t window inside the utterance: no zero padding to write, no compare, no select)
-#pragma unroll
-    for (int i = 0; i < NF1; ++i) {
-      unsigned o[4];
-#pragma unroll
-      for (int cc = 0; cc < CT; ++cc) {
-        f32x4 v = acc[cc][i] + bv1[cc];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], v[e] * a.slope);
-        o[cc * 2] = pack2<F16>(v[0], v[1]);
-        o[cc * 2 + 1] = pack2<F16>(v[2], v[3]);
-      }
-      *(uint4*)(TW + (i * 16 + l15) * RS + co8 * 2) = make_uint4(o[0], o[1], o[2], o[3]);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < NF1; ++i) {
-      const int t = t0 - CP_TH + i * 16 + l15;
-      const bool live = t >= 0 && t < len;
-      unsigned o[4];
-#pragma unroll
-      for (int cc = 0; cc < CT; ++cc) {
-        f32x4 v = acc[cc][i] + bv1[cc];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = live ? fmaxf(v[e], v[e] * a.slope) : 0.f;
-        o[cc * 2] = pack2<F16>(v[0], v[1]);
-        o[cc * 2 + 1] = pack2<F16>(v[2], v[3]);
-      }
-      *(uint4*)(TW + (i * 16 + l15) * RS + co8 * 2) = make_uint4(o[0], o[1], o[2], o[3]);
-    }
-  }
+  store_t_rows<F16, NF1, RS>(TW, acc, bv1, a.slope, t0 - CP_TH, len, l15, co8);
   __syncthreads();
 
   // raw x (residual): requested now, consumed after c2's taps (the accumulate operand of modes 1 / 2 is read in the epilogue:
@@ -599,36 +453,10 @@ __global__ __launch_bounds__(C256_NT, 1) void conv_pair256_kernel(const A a) {
 #pragma unroll
   for (int i = 0; i < NF2; ++i) {
     const int t = t0 + i * 16 + l15;
-    const unsigned rw[4] = {rres[i].x, rres[i].y, rres[i].z, rres[i].w};
-    unsigned ow[4] = {0u, 0u, 0u, 0u};
-    if (a.mode && t < len) {
-      const uint4 ov = *(const uint4*)(ob + (int64_t)t * C + co8);
-      ow[0] = ov.x; ow[1] = ov.y; ow[2] = ov.z; ow[3] = ov.w;
-    }
-    unsigned o[4];
-#pragma unroll
-    for (int cc = 0; cc < CT; ++cc) {
-      f32x4 v = acc2[cc][i] + bv2[cc];
-      {
-        float r0, r1, r2, r3;
-        unpack2<F16>(rw[cc * 2], r0, r1); unpack2<F16>(rw[cc * 2 + 1], r2, r3);
-        v += f32x4{r0, r1, r2, r3};
-      }
-      if (a.mode) {
-        {
-          float o0, o1, o2, o3;
-          unpack2<F16>(ow[cc * 2], o0, o1); unpack2<F16>(ow[cc * 2 + 1], o2, o3);
-          v += f32x4{o0, o1, o2, o3};
-        }
-        if (a.mode == 2) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { v[e] *= a.scale; v[e] = fmaxf(v[e], v[e] * a.final_slope); }
-        }
-      }
-      o[cc * 2] = pack2<F16>(v[0], v[1]);
-      o[cc * 2 + 1] = pack2<F16>(v[2], v[3]);
-    }
-    if (t < len) *(uint4*)(ob + (int64_t)t * C + co8) = make_uint4(o[0], o[1], o[2], o[3]);
+    uint4 ov = make_uint4(0u, 0u, 0u, 0u);
+    if (a.mode && t < len) ov = *(const uint4*)(ob + (int64_t)t * C + co8);
+    const uint4 o = mrf_finish8<F16>(acc2[0][i] + bv2[0], acc2[1][i] + bv2[1], rres[i], ov, a.mode, a.scale, a.final_slope);
+    if (t < len) *(uint4*)(ob + (int64_t)t * C + co8) = o;
   }
 }
 
@@ -658,7 +486,7 @@ template <int C, int NW_> struct FsGeom {
   // kernel's LDS cycles (profiles/r03_mfma_util.json).  A stride of 2 mod 4 units sends q-even chunks to even units and q-odd ones to
   // odd units, 8 rows each over the 8 units of a parity: conflict-free at every tap shift.
   static constexpr int RS = C * 2 + 32;
-  static constexpr int NC = C / 16, KS = C / 32, CH8 = C / 8;
+  static constexpr int NC = C / 16, KS = C / 32;
   static constexpr int TAP = NC * KS * 1024;
   static constexpr int SMEM = (XROWS + TROWS) * RS;     // 72,000 B (C = 64, 4 waves: two workgroups per CU) / 43,200 B (C = 32)
   static constexpr int OCC = SMEM <= 80 * 1024 ? 2 : 1; // workgroups per CU the LDS allows (at most two are asked for)
@@ -668,7 +496,7 @@ template <int C, int NW, bool F16, typename A = PairArgs>
 __global__ __launch_bounds__(NW * 64, (FsGeom<C, NW>::OCC * NW) / 4) void conv_pair_fs_kernel(const A a) {
   using Gm = FsGeom<C, NW>;
   constexpr int NT = Gm::NT, FW = Gm::FW, NF = Gm::NF, GU = Gm::GU, TT = Gm::TT, XROWS = Gm::XROWS, RS = Gm::RS, NC = Gm::NC, KS = Gm::KS,
-                CH8 = Gm::CH8, TAP = Gm::TAP, XH = GU + 25, CG = Gm::CG, CT = NC / CG;
+                TAP = Gm::TAP, XH = GU + 25, CG = Gm::CG, CT = NC / CG;
   __shared__ __attribute__((aligned(16))) unsigned char smem[Gm::SMEM];
   unsigned char* XW = smem;
   unsigned char* TW = smem + XROWS * RS;
@@ -687,35 +515,15 @@ __global__ __launch_bounds__(NW * 64, (FsGeom<C, NW>::OCC * NW) / 4) void conv_p
 
   bf16x8 wa[KS][CT], wb[KS][CT];
   auto load_w = [&](int g, bf16x8 (&w)[KS][CT]) __attribute__((always_inline)) {      // tap g of the 2K-tap sequence c1 | c2
-    const unsigned char* src = (const unsigned char*)(g < K ? a.w1 : a.w2) + (int64_t)(g < K ? g : g - K) * TAP + (cgi * CT) * 1024 + lane * 16;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int c = 0; c < CT; ++c) w[ks][c] = *(const bf16x8*)(src + (ks * NC + c) * 1024);
+    load_taps_cg<KS, CT, NC>(w, a.w1, a.w2, K, TAP, cgi, lane, g);
   };
 
-  {  // ---- x window: lrelu(x) rows t0 - 33 .. t0 + 209, zeros outside the utterance
-    constexpr int NCH = (XROWS * CH8 + NT - 1) / NT;
-    const int xlo = 25 - HK * d, xhi = 25 + Gm::CROWS + HK * d;      // the rows c1 reads at this dilation (the window is sized for d = 5)
-    uint4 xv[NCH];
-#pragma unroll
-    for (int it = 0; it < NCH; ++it) {
-      const int idx = it * NT + tid;
-      const int row = idx / CH8, ch = idx - row * CH8;
-      const int t = t0 - XH + row;
-      xv[it] = make_uint4(0, 0, 0, 0);
-      if (idx < XROWS * CH8 && t >= 0 && t < len && row >= xlo && row < xhi) xv[it] = *(const uint4*)(xb + (int64_t)t * C + ch * 8);
-    }
-    // the weight fragments are requested BEHIND the window: loads return in order, and nothing starts before the window is in LDS
-    load_w(0, wa);
-    load_w(1, wb);
-#pragma unroll
-    for (int it = 0; it < NCH; ++it) {
-      const int idx = it * NT + tid;
-      const int row = idx / CH8, ch = idx - row * CH8;
-      if (idx < XROWS * CH8) *(uint4*)(XW + row * RS + ch * 16) = lrelu8_fast<F16>(xv[it], a.slope);
-    }
-  }
+  // ---- x window: lrelu(x) rows t0 - 33 .. t0 + 209; fetched: the rows c1 reads at this dilation (the window is sized for d = 5)
+  uint4 xv[x_window_chunks<C, XROWS, NT>()];
+  x_window_request<C, XROWS, NT>(xv, xb, t0 - XH, len, 25 - HK * d, 25 + Gm::CROWS + HK * d, tid);
+  load_w(0, wa);
+  load_w(1, wb);
+  x_window_store<F16, C, XROWS, NT, RS>(XW, xv, a.slope, tid);
   f32x4 bv1[CT], bv2[CT];
 #pragma unroll
   for (int c = 0; c < CT; ++c) {
@@ -725,27 +533,13 @@ __global__ __launch_bounds__(NW * 64, (FsGeom<C, NW>::OCC * NW) / 4) void conv_p
   __syncthreads();
 
   f32x4 acc[CT][NF];
-  auto zero_acc = [&]() __attribute__((always_inline)) {
-#pragma unroll
-    for (int c = 0; c < CT; ++c)
-#pragma unroll
-      for (int i = 0; i < NF; ++i) acc[c][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  };
-  // one tap of either conv: `inl` = this lane's fragment address at shift 0, rows advance by `step` rows per tap offset
+  // one tap of either conv at `inp`, this lane's fragment address at the tap's shift
   auto tap = [&](const unsigned char* inp, const bf16x8 (&w)[KS][CT]) __attribute__((always_inline)) {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-      for (int i = 0; i < NF; ++i) {
-        const bf16x8 Bf = *(const bf16x8*)(inp + i * 16 * RS + ks * 64);
-#pragma unroll
-        for (int c = 0; c < CT; ++c) acc[c][i] = mfma16<F16>(w[ks][c], Bf, acc[c][i]);
-      }
-    }
+    tap_plain<F16, KS, CT, NF, RS>(acc, w, inp);
   };
 
   // ---- c1: computed row r = wave*48 + i*16 + l15 <-> frame t0 - 8 + r <-> x-window row r + 25
-  zero_acc();
+  zero_acc(acc);
   {
     const unsigned char* inl = XW + (fg * FW + l15 + 25) * RS + q * 16;
 #pragma unroll 1
@@ -790,7 +584,7 @@ __global__ __launch_bounds__(NW * 64, (FsGeom<C, NW>::OCC * NW) / 4) void conv_p
     }
   }
   // ---- c2 on the same rows (the 8 at either end read guard rows and are dropped)
-  zero_acc();
+  zero_acc(acc);
   {
     const unsigned char* inl = TW + (fg * FW + l15 + GU) * RS + q * 16;
 #pragma unroll 1
@@ -812,36 +606,12 @@ __global__ __launch_bounds__(NW * 64, (FsGeom<C, NW>::OCC * NW) / 4) void conv_p
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
       const int co = (cgi * CT + c) * 16 + q * 4;
-      f32x4 v = acc[c][i] + bv2[c];
-      {
-        float r0, r1, r2, r3;
-        unpack2<F16>(rres[c][i].x, r0, r1); unpack2<F16>(rres[c][i].y, r2, r3);
-        v += f32x4{r0, r1, r2, r3};
-      }
-      if (a.mode) {
-        {
-          float o0, o1, o2, o3;
-          unpack2<F16>(rout[c][i].x, o0, o1); unpack2<F16>(rout[c][i].y, o2, o3);
-          v += f32x4{o0, o1, o2, o3};
-        }
-        if (a.mode == 2) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { v[e] *= a.scale; v[e] = fmaxf(v[e], v[e] * a.final_slope); }
-        }
-      }
-      if (r >= GU && r < GU + TT) *(uint2*)(XW + (r - GU) * RS + co * 2) = make_uint2(pack2<F16>(v[0], v[1]), pack2<F16>(v[2], v[3]));
+      const uint2 o = mrf_finish<F16>(acc[c][i] + bv2[c], rres[c][i].x, rres[c][i].y, rout[c][i].x, rout[c][i].y, a.mode, a.scale, a.final_slope);
+      if (r >= GU && r < GU + TT) *(uint2*)(XW + (r - GU) * RS + co * 2) = o;
     }
   }
   __syncthreads();
-  bf16_t* __restrict__ ob = a.out + (int64_t)bi * slen * C;
-  constexpr int NCO = (TT * CH8 + NT - 1) / NT;
-#pragma unroll
-  for (int it = 0; it < NCO; ++it) {
-    const int idx = it * NT + tid;
-    const int rr = idx / CH8, ch = idx - rr * CH8;
-    const int t = t0 + rr;
-    if (idx < TT * CH8 && t < len) *(uint4*)(ob + (int64_t)t * C + ch * 8) = *(const uint4*)(XW + rr * RS + ch * 16);
-  }
+  copy_out_rows<C, TT, NT, RS>(a.out + (int64_t)bi * slen * C, XW, t0, len, tid);
 }
 
 
@@ -908,26 +678,16 @@ static void launch_pair(const A& a, int f16, int B, int len, int C, hipStream_t 
 static int conv_pair_impl(const void* x16, const void* w1_pack, const float* bias1, const void* w2_pack, const float* bias2, void* out16,
                           int f16, int B, int len, int C, int K, int dil, float slope, int mode, float scale, float final_slope,
                           const RowLens* rl, void* stream) {
-  TTSK_REQUIRE(x16 && w1_pack && bias1 && w2_pack && bias2 && out16, "ttsk_hifi_conv_pair: null pointer");
-  TTSK_REQUIRE(B > 0 && len > 0 && B <= 65535 && x16 != out16, "ttsk_hifi_conv_pair: bad sizes / in-place output");
-  TTSK_REQUIRE(ttsk_hifi_conv_pair_supported(C, K, dil), "ttsk_hifi_conv_pair: no instance for C=%d K=%d dil=%d", C, K, dil);
-  TTSK_REQUIRE(mode >= 0 && mode <= 2 && (final_slope > 0.f || mode != 2), "ttsk_hifi_conv_pair: bad mode / final_slope");
-  TTSK_REQUIRE(slope > 0.f && slope < 1.f, "ttsk_hifi_conv_pair: LeakyReLU slope %g outside (0, 1)", slope);
-  TTSK_REQUIRE(((((uintptr_t)x16) | ((uintptr_t)w1_pack) | ((uintptr_t)w2_pack) | ((uintptr_t)bias1) | ((uintptr_t)bias2) | ((uintptr_t)out16)) & 15) == 0,
-               "ttsk_hifi_conv_pair: 16-byte alignment");
+  if (const int rc = pair_args_check("ttsk_hifi_conv_pair", x16, w1_pack, bias1, w2_pack, bias2, out16, B, len, INT_MAX,
+                                     ttsk_hifi_conv_pair_supported(C, K, dil), "ttsk_hifi_conv_pair: no instance for C=%d K=%d dil=%d", C, K,
+                                     dil, 0, slope, mode, final_slope))
+    return rc;
   PairArgs a{(const bf16_t*)x16, (const bf16_t*)w1_pack, (const bf16_t*)w2_pack, bias1, bias2, (bf16_t*)out16, len, K, dil, slope,
              mode, scale, final_slope};
 #ifdef TTSK_STAMPS
   a.stamps = g_pair_stamps;
 #endif
-  if (rl) {
-    WithRows<PairArgs> ar;
-    static_cast<PairArgs&>(ar) = a;
-    ar.rl = *rl;
-    launch_pair(ar, f16, B, len, C, (hipStream_t)stream);
-  } else {
-    launch_pair(a, f16, B, len, C, (hipStream_t)stream);
-  }
+  launch_with_rows(a, rl, [&](const auto& args) { launch_pair(args, f16, B, len, C, (hipStream_t)stream); });
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
 }

@@ -12,8 +12,9 @@
 // frame group), weights streamed L2 -> registers from ttsk_pack_resblock_weight packs as one double-buffered sequence of 2K taps.
 // C = 128: 4 cout groups x 96 frames (64 at the widest halo); C = 64: 2 x 2 x 96 frames; C = 32: 1 x 4 x 48 frames.  conv0 computes EW extra frame tiles
 // per wave (the conv1 halo, G1 = 8 * FG * EW frames either side); an instance is picked per (C, EW) from the halo HK * d1.
+// The stages it shares with them (x window fill, weight addressing, tap nest, MRF finish, copy-out, host checks) are pairparts.h's.
 #include "common.h"
-#include "rowlens.h"
+#include "pairparts.h"
 
 namespace {
 
@@ -35,7 +36,7 @@ constexpr int RB2_H0 = 16;     // conv0 halo the x window carries on top of conv
 template <int C, int EW> struct Rb2Geom {
   static constexpr int NW = 4, NT = NW * 64;
   static constexpr int CG = C >= 64 ? C / 32 : 1, FG = NW / CG;          // cout groups x frame groups
-  static constexpr int NC = C / 16, KS = C / 32, CH8 = C / 8, CT = NC / CG;
+  static constexpr int NC = C / 16, KS = C / 32, CT = NC / CG;
   // conv1 frame tiles per wave; the widest C = 128 halo takes 64-frame tiles (11 conv0 tiles of accumulators next to the residual and
   // the streamed weights went past 256 registers)
   static constexpr int NF2 = C == 32 ? 3 : (C == 128 && EW > 2 ? 4 : 6);
@@ -56,7 +57,7 @@ template <int C, int EW, bool F16, typename A = Rb2Args>
 __global__ __launch_bounds__(256, 2) void resblock2_kernel(const A a) {
   using Gm = Rb2Geom<C, EW>;
   constexpr int NT = Gm::NT, NF1 = Gm::NF1, NF2 = Gm::NF2, TT = Gm::TT, G1 = Gm::G1, TROWS = Gm::TROWS, XROWS = Gm::XROWS,
-                RS = Gm::RS, NC = Gm::NC, KS = Gm::KS, CH8 = Gm::CH8, CT = Gm::CT, CG = Gm::CG, TAP = Gm::TAP, H0M = RB2_H0;
+                RS = Gm::RS, NC = Gm::NC, KS = Gm::KS, CT = Gm::CT, CG = Gm::CG, TAP = Gm::TAP, H0M = RB2_H0;
   __shared__ __attribute__((aligned(16))) unsigned char smem[Gm::SMEM];
   unsigned char* XW = smem;                       // lrelu(x) rows t0 - G1 - 16 .. t0 + TT + G1 + 16 (conv0 only)
   unsigned char* TW = smem;                       // lrelu(x1) rows t0 - G1 .. t0 + TT + G1 (after conv0)
@@ -76,35 +77,15 @@ __global__ __launch_bounds__(256, 2) void resblock2_kernel(const A a) {
 
   bf16x8 wa[KS][CT], wb[KS][CT];
   auto load_w = [&](int g, bf16x8 (&w)[KS][CT]) __attribute__((always_inline)) {      // tap g of the 2K-tap sequence conv0 | conv1
-    const unsigned char* src = (const unsigned char*)(g < K ? a.w0 : a.w1) + (int64_t)(g < K ? g : g - K) * TAP + (cgi * CT) * 1024 + lane * 16;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int c = 0; c < CT; ++c) w[ks][c] = *(const bf16x8*)(src + (ks * NC + c) * 1024);
+    load_taps_cg<KS, CT, NC>(w, a.w0, a.w1, K, TAP, cgi, lane, g);
   };
 
-  {  // ---- x window: lrelu(x), zeros outside the utterance; only the rows conv0 reads at this dilation are fetched
-    constexpr int NCH = (XROWS * CH8 + NT - 1) / NT;
-    const int xlo = H0M - HK * d0, xhi = H0M + TROWS + HK * d0;
-    uint4 xv[NCH];
-#pragma unroll
-    for (int it = 0; it < NCH; ++it) {
-      const int idx = it * NT + tid;
-      const int row = idx / CH8, ch = idx - row * CH8;
-      const int t = t0 - G1 - H0M + row;
-      xv[it] = make_uint4(0, 0, 0, 0);
-      if (idx < XROWS * CH8 && t >= 0 && t < len && row >= xlo && row < xhi) xv[it] = *(const uint4*)(xb + (int64_t)t * C + ch * 8);
-    }
-    // the weight fragments are requested BEHIND the window: loads return in order, and nothing starts before the window is in LDS
-    load_w(0, wa);
-    load_w(1, wb);
-#pragma unroll
-    for (int it = 0; it < NCH; ++it) {
-      const int idx = it * NT + tid;
-      const int row = idx / CH8, ch = idx - row * CH8;
-      if (idx < XROWS * CH8) *(uint4*)(XW + row * RS + ch * 16) = lrelu8_fast<F16>(xv[it], a.slope);
-    }
-  }
+  // ---- x window: lrelu(x), zeros outside the utterance; only the rows conv0 reads at this dilation are fetched
+  uint4 xv[x_window_chunks<C, XROWS, NT>()];
+  x_window_request<C, XROWS, NT>(xv, xb, t0 - G1 - H0M, len, H0M - HK * d0, H0M + TROWS + HK * d0, tid);
+  load_w(0, wa);
+  load_w(1, wb);
+  x_window_store<F16, C, XROWS, NT, RS>(XW, xv, a.slope, tid);
   f32x4 bv0[CT], bv1[CT];
 #pragma unroll
   for (int c = 0; c < CT; ++c) {
@@ -115,20 +96,9 @@ __global__ __launch_bounds__(256, 2) void resblock2_kernel(const A a) {
 
   // ---- conv0: row r = fg * NF1 * 16 + i * 16 + l15 <-> frame t0 - G1 + r <-> x-window row r + 16
   f32x4 acc[CT][NF1];
-#pragma unroll
-  for (int c = 0; c < CT; ++c)
-#pragma unroll
-    for (int i = 0; i < NF1; ++i) acc[c][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   auto tap0 = [&](const unsigned char* inp, const bf16x8 (&w)[KS][CT]) __attribute__((always_inline)) {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-      for (int i = 0; i < NF1; ++i) {
-        const bf16x8 Bf = *(const bf16x8*)(inp + i * 16 * RS + ks * 64);
-#pragma unroll
-        for (int c = 0; c < CT; ++c) acc[c][i] = mfma16<F16>(w[ks][c], Bf, acc[c][i]);
-      }
-    }
+    tap_plain<F16, KS, CT, NF1, RS>(acc, w, inp);
   };
   {
     // K is odd and >= 3: taps 0 .. K-2 in pairs, tap K-1 on set a; conv1 then starts on set b
@@ -191,20 +161,9 @@ __global__ __launch_bounds__(256, 2) void resblock2_kernel(const A a) {
   }
   // ---- conv1: output frame f = fg * NF2 * 16 + j * 16 + l15 <-> lrelu(x1) row f + G1; taps K .. 2K-1 of the sequence
   f32x4 acc2[CT][NF2];
-#pragma unroll
-  for (int c = 0; c < CT; ++c)
-#pragma unroll
-    for (int j = 0; j < NF2; ++j) acc2[c][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc2);
   auto tap1 = [&](const unsigned char* inp, const bf16x8 (&w)[KS][CT]) __attribute__((always_inline)) {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-      for (int j = 0; j < NF2; ++j) {
-        const bf16x8 Bf = *(const bf16x8*)(inp + j * 16 * RS + ks * 64);
-#pragma unroll
-        for (int c = 0; c < CT; ++c) acc2[c][j] = mfma16<F16>(w[ks][c], Bf, acc2[c][j]);
-      }
-    }
+    tap_plain<F16, KS, CT, NF2, RS>(acc2, w, inp);
   };
   {
     const unsigned char* inl = TW + (fg * NF2 * 16 + l15 + G1) * RS + q * 16;
@@ -231,36 +190,11 @@ __global__ __launch_bounds__(256, 2) void resblock2_kernel(const A a) {
       const int co = (cgi * CT + c) * 16 + q * 4;
       unsigned char* rp = RW + f * RS + co * 2;
       const uint2 x1 = *(const uint2*)rp;
-      f32x4 v = acc2[c][j] + bv1[c];
-      {
-        float r0, r1, r2, r3;
-        unpack2<F16>(x1.x, r0, r1); unpack2<F16>(x1.y, r2, r3);
-        v += f32x4{r0, r1, r2, r3};
-      }
-      if (a.mode) {
-        {
-          float o0, o1, o2, o3;
-          unpack2<F16>(rout[c][j].x, o0, o1); unpack2<F16>(rout[c][j].y, o2, o3);
-          v += f32x4{o0, o1, o2, o3};
-        }
-        if (a.mode == 2) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { v[e] *= a.scale; v[e] = fmaxf(v[e], v[e] * a.final_slope); }
-        }
-      }
-      *(uint2*)rp = make_uint2(pack2<F16>(v[0], v[1]), pack2<F16>(v[2], v[3]));
+      *(uint2*)rp = mrf_finish<F16>(acc2[c][j] + bv1[c], x1.x, x1.y, rout[c][j].x, rout[c][j].y, a.mode, a.scale, a.final_slope);
     }
   }
   __syncthreads();
-  bf16_t* __restrict__ ob = a.out + (int64_t)bi * slen * C;
-  constexpr int NCO = (TT * CH8 + NT - 1) / NT;
-#pragma unroll
-  for (int it = 0; it < NCO; ++it) {
-    const int idx = it * NT + tid;
-    const int rr = idx / CH8, ch = idx - rr * CH8;
-    const int t = t0 + rr;
-    if (idx < TT * CH8 && t < len) *(uint4*)(ob + (int64_t)t * C + ch * 8) = *(const uint4*)(RW + rr * RS + ch * 16);
-  }
+  copy_out_rows<C, TT, NT, RS>(a.out + (int64_t)bi * slen * C, RW, t0, len, tid);
 }
 
 // conv1 halo G1 = 8 * FG * EW of each instance: C = 128 (FG = 1): 8 / 16 / 40; C = 64 (FG = 2): 16 / 48; C = 32 (FG = 4): 32 / 64
@@ -300,25 +234,14 @@ extern "C" int ttsk_hifi_resblock2_supported(int C, int K, int d0, int d1) {
 static int resblock2_impl(const void* x16, const void* w0_pack, const float* bias0, const void* w1_pack, const float* bias1,
                           void* out16, int f16, int B, int len, int C, int K, int d0, int d1, float slope, int mode, float scale,
                           float final_slope, const RowLens* rl, void* stream) {
-  TTSK_REQUIRE(x16 && w0_pack && bias0 && w1_pack && bias1 && out16, "ttsk_hifi_resblock2: null pointer");
-  TTSK_REQUIRE(B > 0 && len > 0 && B <= 65535 && len <= (1 << 30) && x16 != out16, "ttsk_hifi_resblock2: bad sizes / in-place output");
-  TTSK_REQUIRE(ttsk_hifi_resblock2_supported(C, K, d0, d1), "ttsk_hifi_resblock2: no instance for C=%d K=%d d=(%d,%d)", C, K, d0, d1);
-  TTSK_REQUIRE(mode >= 0 && mode <= 2 && (final_slope > 0.f || mode != 2), "ttsk_hifi_resblock2: bad mode / final_slope");
-  TTSK_REQUIRE(slope > 0.f && slope < 1.f, "ttsk_hifi_resblock2: LeakyReLU slope %g outside (0, 1)", slope);
-  TTSK_REQUIRE(((((uintptr_t)x16) | ((uintptr_t)w0_pack) | ((uintptr_t)w1_pack) | ((uintptr_t)bias0) | ((uintptr_t)bias1) | ((uintptr_t)out16)) & 15) == 0,
-               "ttsk_hifi_resblock2: 16-byte alignment");
+  if (const int rc = pair_args_check("ttsk_hifi_resblock2", x16, w0_pack, bias0, w1_pack, bias1, out16, B, len, 1 << 30,
+                                     ttsk_hifi_resblock2_supported(C, K, d0, d1), "ttsk_hifi_resblock2: no instance for C=%d K=%d d=(%d,%d)",
+                                     C, K, d0, d1, slope, mode, final_slope))
+    return rc;
   const Rb2Args a{(const bf16_t*)x16, (const bf16_t*)w0_pack, (const bf16_t*)w1_pack, bias0, bias1, (bf16_t*)out16, len, K, d0, d1, slope,
                   mode, scale, final_slope};
   const int h1 = (K - 1) / 2 * d1;
-  hipStream_t s = (hipStream_t)stream;
-  if (rl) {
-    WithRows<Rb2Args> ar;
-    static_cast<Rb2Args&>(ar) = a;
-    ar.rl = *rl;
-    dispatch_rb2(ar, B, f16, C, h1, s);
-  } else {
-    dispatch_rb2(a, B, f16, C, h1, s);
-  }
+  launch_with_rows(a, rl, [&](const auto& args) { dispatch_rb2(args, B, f16, C, h1, (hipStream_t)stream); });
   TTSK_CHECK_LAUNCH();
   return TTSK_OK;
 }
